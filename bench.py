@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """MTIP phasing benchmark: iterations/sec at 128 q-shells x L_max = 32 (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps once and prints the result line.  Everything else the benchmark
+measures -- the CPU baseline, the median over several timed windows, the hipEvent family brackets and the roofline, the
+whole-step traffic figures, the concurrency probe of the streams and the end-of-run reduce -- runs with --full only.
 
 One process per GPU (for N > 1 launched by torch.distributed.run; RANK / LOCAL_RANK / WORLD_SIZE from the
 environment).  Every rank phases `--restarts-per-gpu` independent restarts (BASELINE config 4: 64 restarts
@@ -47,7 +51,13 @@ def parse():
     p.add_argument('--no-roofline', action='store_true')
     p.add_argument('--repeats', type=int, default=0,
                    help='timed windows (each: fresh state, W warm-up steps, K timed steps); the line reports the MEDIAN window. '
-                        '0 = 5 when K <= 50 (a 20-step window lasts 13 ms: one shot is not a measurement), 3 up to 1000 steps, else 1')
+                        '0 = one window; with --full 5 when K <= 50 (a 20-step window lasts 13 ms: one shot is not a measurement), '
+                        '3 up to 1000 steps, else 1')
+    p.add_argument('--full', action='store_true',
+                   help='also the CPU baseline, the repeated windows, the kernel-family brackets / roofline, the whole-step traffic, '
+                        'the stream-concurrency probe and the end-of-run reduce (off: only what value and ms_per_step need)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help="after the timed steps write what the last step left (rank 0's restarts) as DIR/<name>.npy")
     p.add_argument('--dist-backend', default='nccl', help="'gloo' + --same-device rehearses the multi-rank path on a one-GPU box")
     p.add_argument('--same-device', action='store_true', help='every rank uses GPU 0 (rehearsal only)')
     return p.parse_args()
@@ -105,6 +115,33 @@ def phase_of(warmup, steps):
             'schedule': 'tutorial schedule from its first step: 5 x (60 HIO, SW, 40 ER) + (SW, 100 ER), repeated'}
 
 
+DUMP_SAMPLE = 131072        # grid points per restart in the density dumps (a fixed, seeded sample: 8 restarts ~ 38 MB in all)
+
+
+def dump_outputs(engines, out_dir):
+    """what the timed path left after its last step, for every restart of this rank in engine order, as out_dir/<name>.npy:
+    the real-space and reciprocal densities and the support at a fixed seeded sample of grid points (complex values as
+    [..., 2] = real, imaginary), the error of the last step and the best error so far (float64; support as float32)"""
+    os.makedirs(out_dir, exist_ok=True)
+    e0 = engines[0]
+    G = int(np.prod(e0.shape))
+    idx = np.arange(G) if G <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(G, DUMP_SAMPLE, replace=False))
+    out = {'sample_index': idx.astype(np.float64), 'density': [], 'reciprocal_density': [], 'support': [],
+           'error_last_step': [], 'best_error': []}
+    for e in engines:
+        best, n_done = e.best_error()
+        out['best_error'].append(best)
+        out['error_last_step'].append(e.fetch_errors(n_done - 1, 1)[0][0] if n_done else np.full(e.B, np.nan))
+        for b in range(e.B):
+            for name, get in (('density', e.density), ('reciprocal_density', e.reciprocal_density)):
+                v = get(b).reshape(-1)[idx]
+                out[name].append(np.stack([v.real, v.imag], -1))
+            out['support'].append(e.support(b).reshape(-1)[idx].astype(np.float32))
+    for name, v in out.items():
+        v = v if name == 'sample_index' else (np.concatenate(v) if name in ('error_last_step', 'best_error') else np.stack(v))
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 def cpu_baseline(a, N, L, B):
     """The oracle (numpy restatement of the reference algorithm), one process per restart with one BLAS thread each like the
     reference (xframe/__init__.py:5-8, reconstruct.py:141-157), a bounded sample of HIO ft_stab steps.  Runs BEFORE this
@@ -145,7 +182,7 @@ def main():
     np.seterr(all='ignore')
     from xframe_amd.fxs import synthetic as S0
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:       # reported at N = 1 only; before any GPU call of this process
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:   # reported at N = 1 only; before any GPU call of this process
         cpu = cpu_baseline(a, *S0._SIZES[a.config], a.restarts_per_gpu)
     import torch
     dist = None
@@ -268,7 +305,7 @@ def main():
         torch.cuda.synchronize(dev)
 
     from xframe_amd.fxs.engine import streams_side_by_side
-    side_by_side = streams_side_by_side(engines)              # < n_eng: two engines share a hardware queue
+    side_by_side = streams_side_by_side(engines) if a.full else None   # < n_eng: two engines share a hardware queue
     # diagnostic: K more streams of this process that have run one kernel and then sit idle during the timed region (as the
     # streams of a communication library do): does a hardware queue that is merely there cost the engines anything?
     idle_streams = []
@@ -281,7 +318,8 @@ def main():
 
     # ---- R windows of (fresh state, W warm-up steps, exactly K timed steps between barrier + synchronize); the line reports the
     #      median window, so ms_per_step x steps is a time that was measured, and lists them all
-    R = a.repeats if a.repeats > 0 else (5 if a.steps <= 50 else (3 if a.steps <= 1000 else 1))
+    R = a.repeats if a.repeats > 0 else (1 if not a.full else (5 if a.steps <= 50 else (3 if a.steps <= 1000 else 1)))
+    profiling = a.full and not a.no_roofline                    # hipEvent family brackets (roofline, kernel_families_ms)
     windows = []
     enqueue = []
     n_bracketed = max(1, R // 2)                                # windows that carry family brackets: fewer than half, so the median has none
@@ -295,7 +333,7 @@ def main():
             dist.barrier()
         host['enqueue_s'] = 0.0
         host['chunks'] = 0
-        if not a.no_roofline:
+        if profiling:
             if rep == 0:
                 e0.profile(True)                                # resets the timers; they accumulate over the bracketed windows
                 e0.lib.mtip_profile(e0.ctx, 0)
@@ -313,7 +351,7 @@ def main():
             el = float(t.item())
         windows.append(el)
         enqueue.append(host['enqueue_s'])
-        if not a.no_roofline:
+        if profiling:
             engines[0].lib.mtip_profile(engines[0].ctx, 0)
     order = np.argsort(windows)
     mid = int(order[(R - 1) // 2])                              # the median window (the lower one of an even count)
@@ -322,19 +360,23 @@ def main():
     its = world * B * a.steps / elapsed
     ms_per_step = 1e3 * elapsed / a.steps
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(engines, a.dump_outputs)
+
     # ---- end-of-run reduce of rotation-invariant summaries (outside the timed region)
-    t_red = time.perf_counter()
-    best_err = np.concatenate([e.best_error()[0] for e in engines])
-    n_done = e0.best_error()[1]
-    sweeps = e0.jacobi_sweeps()
-    closing = e0.jacobi_closing_step()
-    bl_sum = np.zeros((L + 1, N, N), complex)
-    n_bl = 0
-    for e in engines[:2]:                                       # bounded sample: the download is PCIe bound
-        bl_sum += e.last_deg2_invariant(0)
-        n_bl += 1
-    bl_mean = average_invariants(bl_sum, n_bl, device=dev if (dist is not None and a.dist_backend == 'nccl') else None)
-    reduce_s = time.perf_counter() - t_red
+    if a.full:
+        t_red = time.perf_counter()
+        best_err = np.concatenate([e.best_error()[0] for e in engines])
+        n_done = e0.best_error()[1]
+        sweeps = e0.jacobi_sweeps()
+        closing = e0.jacobi_closing_step()
+        bl_sum = np.zeros((L + 1, N, N), complex)
+        n_bl = 0
+        for e in engines[:2]:                                   # bounded sample: the download is PCIe bound
+            bl_sum += e.last_deg2_invariant(0)
+            n_bl += 1
+        bl_mean = average_invariants(bl_sum, n_bl, device=dev if (dist is not None and a.dist_backend == 'nccl') else None)
+        reduce_s = time.perf_counter() - t_red
 
     # ---- roofline of the dominant kernel family: hipEvent brackets on engine 0's stream, recorded over the timed
     #      region itself (asynchronous event pairs, resolved after the final synchronisation)
@@ -342,7 +384,7 @@ def main():
     fam_ms = {}
     Bp = e0.B
     e0_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-    if not a.no_roofline:
+    if profiling:
         for fam in ('sht_fwd', 'sht_inv', 'sht_inv_modulus', 'sht_inv_real', 'sht_chain', 'sht_chain_modulus', 'sht_chain_real', 'hankel',
                     'proj', 'polar', 'real_update', 'deg2_metric'):
             ms, n = e0.profile_get(fam)
@@ -441,21 +483,22 @@ def main():
                 roofline['note'] = ('dominant kernel family (HBM bound), timed with hipEvents over the timed region on the stream '
                                     'of engine 0; traffic = FETCH_SIZE x 2 + WRITE_SIZE of profiles/pmc_traffic.json when it was '
                                     'collected at this batch size')
-    step_bytes = algorithmic_bytes_per_step(N, L, e0.n_theta, e0.n_phi, True)
-    whole_step = {'algorithmic_bytes_per_step_per_restart': step_bytes,
-                  'achieved_GBps_per_gpu': step_bytes * B * a.steps / elapsed / 1e9,
-                  'frac_of_8TBps': step_bytes * B * a.steps / elapsed / 8e12,
-                  'pmc_bytes_per_step_per_restart': None}
-    try:        # what a step physically moves: FETCH_SIZE x 2 + WRITE_SIZE summed over the kernels of one step (profiles/pmc_traffic.json)
-        with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
-            pmc_w = json.load(f)
-        if pmc_w.get('config') == a.config and pmc_w.get('hbm_bytes_per_step_per_restart'):
-            pb = float(pmc_w['hbm_bytes_per_step_per_restart'])
-            whole_step['pmc_bytes_per_step_per_restart'] = pb
-            whole_step['pmc_GBps_per_gpu'] = pb * B * a.steps / elapsed / 1e9
-            whole_step['pmc_frac_of_8TBps'] = pb * B * a.steps / elapsed / 8e12
-    except (OSError, ValueError, KeyError):
-        pass
+    if a.full:
+        step_bytes = algorithmic_bytes_per_step(N, L, e0.n_theta, e0.n_phi, True)
+        whole_step = {'algorithmic_bytes_per_step_per_restart': step_bytes,
+                      'achieved_GBps_per_gpu': step_bytes * B * a.steps / elapsed / 1e9,
+                      'frac_of_8TBps': step_bytes * B * a.steps / elapsed / 8e12,
+                      'pmc_bytes_per_step_per_restart': None}
+        try:        # what a step physically moves: FETCH_SIZE x 2 + WRITE_SIZE summed over the kernels of one step (profiles/pmc_traffic.json)
+            with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
+                pmc_w = json.load(f)
+            if pmc_w.get('config') == a.config and pmc_w.get('hbm_bytes_per_step_per_restart'):
+                pb = float(pmc_w['hbm_bytes_per_step_per_restart'])
+                whole_step['pmc_bytes_per_step_per_restart'] = pb
+                whole_step['pmc_GBps_per_gpu'] = pb * B * a.steps / elapsed / 1e9
+                whole_step['pmc_frac_of_8TBps'] = pb * B * a.steps / elapsed / 8e12
+        except (OSError, ValueError, KeyError):
+            pass
 
     if rank == 0:
         line = {
@@ -463,7 +506,7 @@ def main():
             'value': its, 'unit': 'MTIP iterations/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
             'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'repeats': {'windows_ms': [1e3 * w for w in windows], 'reported': 'median', 'spread_rel': (max(windows) - min(windows)) / elapsed,
-                        'bracketed_windows': list(range(n_bracketed)) if not a.no_roofline else [],
+                        'bracketed_windows': list(range(n_bracketed)) if profiling else [],
                         'note': 'every window: fresh seeded state, W warm-up steps, then exactly K timed steps between barrier + '
                                 'synchronize; value and ms_per_step are the median window; the hipEvent family brackets behind `roofline` '
                                 'sample the first step of up to four chunks of the bracketed windows (a bracketed step costs ~0.5 ms)'},
@@ -472,18 +515,23 @@ def main():
                                    f'{B} restarts per GPU on {n_eng} streams, tutorial schedule (HIO/SW/ER, ft_stab on), '
                                    f'{"reference-order" if a.exact else "fused"} step',
                        'restarts_per_gpu': B, 'restarts_total': B * world, 'streams_per_gpu': n_eng,
-                       'streams_side_by_side': round(side_by_side, 2),
+                       'streams_side_by_side': round(side_by_side, 2) if side_by_side is not None else None,
                        'engines_take_turns': turns is not None,      # mtip_run_group_async (ProjectWorker's default) / --no-turns
                        'parallelism': f'restart-sharded x{world}', 'step_mode': 'exact' if a.exact else 'fused'},
-            'roofline': roofline, 'cpu_baseline': cpu, 'whole_step': whole_step, 'kernel_families_ms': fam_ms,
+            'roofline': roofline, 'cpu_baseline': cpu,
             'phase': phase_of(a.warmup, a.steps),
-            'setup_seconds': setup_s, 'final_reduce_seconds': reduce_s,
+            'setup_seconds': setup_s,
             'host_enqueue_ms_per_step': 1e3 * host['enqueue_s'] / max(a.steps, 1),
-            'best_error_rank0': [float(x) for x in best_err], 'steps_done_per_restart': int(n_done),
-            'mean_B0_trace': float(np.trace(bl_mean[0]).real),
-            'jacobi_sweeps_last_step_restart0': [int(x) for x in sweeps[0]],
-            'jacobi_closing_step_last_step_restart0': [int(x) for x in closing[0]],   # 0 confirming sweep, 1 / 2 first / second order polar step
         }
+        if a.full:
+            line.update({
+                'whole_step': whole_step, 'kernel_families_ms': fam_ms,
+                'final_reduce_seconds': reduce_s,
+                'best_error_rank0': [float(x) for x in best_err], 'steps_done_per_restart': int(n_done),
+                'mean_B0_trace': float(np.trace(bl_mean[0]).real),
+                'jacobi_sweeps_last_step_restart0': [int(x) for x in sweeps[0]],
+                'jacobi_closing_step_last_step_restart0': [int(x) for x in closing[0]],   # 0 confirming sweep, 1 / 2 first / second order polar step
+            })
         print(json.dumps(line))
     for e in engines:
         e.close()

@@ -5,7 +5,7 @@ out=gpurun_out/r4g
 mkdir -p $out
 for spec in "1 1" "2 2" "3 3" "4 4" "6 3,3" "9 3,3,3" "8 3,3,2"; do
   set -- $spec
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --restarts-per-gpu $1 --engine-sizes $2 > $out/b_$2.json 2> $out/b_$2.err
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --restarts-per-gpu $1 --engine-sizes $2 > $out/b_$2.json 2> $out/b_$2.err
 done
 python - <<PY
 import json, glob

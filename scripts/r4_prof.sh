@@ -5,11 +5,11 @@ tag=${1:-r4p}
 shift || true
 out=gpurun_out/$tag
 mkdir -p $out
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > $out/bench_d1.json 2> $out/bench_d1.err
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > $out/bench_d2.json 2> $out/bench_d2.err
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" > $out/bench_d1.json 2> $out/bench_d1.err
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" > $out/bench_d2.json 2> $out/bench_d2.err
 export TMPDIR=/tmp
 cd /tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --no-cpu-baseline --repeats 1 "$@" > $out/bench_rocprof.json 2> $out/bench_rocprof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --full --no-cpu-baseline --repeats 1 "$@" > $out/bench_rocprof.json 2> $out/bench_rocprof.err
 python scripts/kernel_stats.py $out/stats > $out/kernel_stats.txt; head -30 $out/kernel_stats.txt
 python - <<PY
 import json

@@ -3,7 +3,7 @@
 set -e
 out=gpurun_out/r4q; mkdir -p $out
 for q in 4 6 8 16; do for t in "" "--no-turns"; do
-  GPU_MAX_HW_QUEUES=$q timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --engine-sizes 2,2,2,2 $t > $out/q${q}${t}.json 2> $out/q${q}${t}.err
+  GPU_MAX_HW_QUEUES=$q timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --engine-sizes 2,2,2,2 $t > $out/q${q}${t}.json 2> $out/q${q}${t}.err
 done; done
 python - <<PY
 import json, glob

@@ -5,8 +5,8 @@ tag=${1:-r4z}
 out=gpurun_out/$tag
 mkdir -p $out
 for sz in 3,3,2 4,2,2 2,4,2 2,2,4 4,4 2,2,2,2 6,2; do
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --engine-sizes $sz > $out/bench_d_$sz.json 2> $out/bench_d_$sz.err
-  timeout -k 10 200 python bench.py --no-cpu-baseline --engine-sizes $sz --repeats 1 > $out/bench_600_$sz.json 2> $out/bench_600_$sz.err
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --engine-sizes $sz > $out/bench_d_$sz.json 2> $out/bench_d_$sz.err
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --engine-sizes $sz --repeats 1 > $out/bench_600_$sz.json 2> $out/bench_600_$sz.err
 done
 python - <<PY
 import json

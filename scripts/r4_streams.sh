@@ -5,8 +5,8 @@ tag=${1:-r4s}
 out=gpurun_out/$tag
 mkdir -p $out
 for st in 2 3 4; do
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --streams $st > $out/bench_d_s$st.json 2> $out/bench_d_s$st.err
-  timeout -k 10 200 python bench.py --no-cpu-baseline --streams $st --repeats 1 > $out/bench_600_s$st.json 2> $out/bench_600_s$st.err
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --streams $st > $out/bench_d_s$st.json 2> $out/bench_d_s$st.err
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --streams $st --repeats 1 > $out/bench_600_s$st.json 2> $out/bench_600_s$st.err
 done
 python - <<PY
 import json

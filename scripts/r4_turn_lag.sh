@@ -1,8 +1,8 @@
 set -e
 out=gpurun_out/r4t2; mkdir -p $out
 for lag in 1 2; do
-  MTIP_TURN_LAG=$lag timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/d_lag$lag.json 2> $out/d_lag$lag.err
-  MTIP_TURN_LAG=$lag timeout -k 10 300 python bench.py --no-cpu-baseline > $out/s_lag$lag.json 2> $out/s_lag$lag.err
+  MTIP_TURN_LAG=$lag timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/d_lag$lag.json 2> $out/d_lag$lag.err
+  MTIP_TURN_LAG=$lag timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/s_lag$lag.json 2> $out/s_lag$lag.err
 done
 python - <<PY
 import json, glob

@@ -8,12 +8,12 @@ tail -2 $out/tests.log
 for spec in "3,3,2 --no-turns" "3,3,2" "2,2,2,2" "4,4" "3,3,2" "2,3,3" "4,2,2"; do
   set -- $spec
   tag=$(echo "$1$2" | tr ',' '_')
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --engine-sizes $1 $2 > $out/d_$tag.json 2> $out/d_$tag.err
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --engine-sizes $1 $2 > $out/d_$tag.json 2> $out/d_$tag.err
 done
 for spec in "3,3,2 --no-turns" "3,3,2" "2,2,2,2"; do
   set -- $spec
   tag=$(echo "$1$2" | tr ',' '_')
-  timeout -k 10 300 python bench.py --no-cpu-baseline --engine-sizes $1 $2 > $out/s_$tag.json 2> $out/s_$tag.err
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --engine-sizes $1 $2 > $out/s_$tag.json 2> $out/s_$tag.err
 done
 python - <<PY
 import json, glob
