@@ -7,8 +7,8 @@ mkdir -p $out
 timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -x -q -k "transforms or steps or trajectory or config" > $out/pytest_subset.log 2>&1 || { tail -40 $out/pytest_subset.log; exit 1; }
 tail -3 $out/pytest_subset.log
 for ch in 1 0; do
-  MTIP_SHT_CHAIN=$ch timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_d_chain$ch.json 2> $out/bench_d_chain$ch.err
-  MTIP_SHT_CHAIN=$ch timeout -k 10 200 python bench.py --full --no-cpu-baseline > $out/bench_600_chain$ch.json 2> $out/bench_600_chain$ch.err
+  MTIP_SHT_TIER=$((ch + 4)) timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_d_chain$ch.json 2> $out/bench_d_chain$ch.err
+  MTIP_SHT_TIER=$((ch + 4)) timeout -k 10 200 python bench.py --full --no-cpu-baseline > $out/bench_600_chain$ch.json 2> $out/bench_600_chain$ch.err
 done
 python - <<PY
 import json

@@ -2,6 +2,8 @@
 // Blocks of a launch are distributed over a few OS worker threads; inside a block the GPU threads are
 // ucontext fibers scheduled round-robin, yielding at barriers and wave collectives.
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <string>
 #include <sys/mman.h>
 #include <ucontext.h>
 
@@ -198,6 +200,14 @@ static void run_block(Worker* w, int n, dim3 bidx, size_t smem_bytes) {
 }
 
 static std::mutex launch_mutex;
+static std::string launch_log;                       // kernel names of the launches since the last reset, one per line
+
+void log_launch(const char* kernel) {
+    std::lock_guard<std::mutex> guard(launch_mutex);
+    while (*kernel == '(' || *kernel == ' ') ++kernel;
+    launch_log.append(kernel, std::strcspn(kernel, "<)"));
+    launch_log += '\n';
+}
 
 void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& body) {
     std::lock_guard<std::mutex> guard(launch_mutex);
@@ -249,3 +259,18 @@ void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& bod
 
 // tells the Python side that "device" pointers of this library are host pointers (torch CPU tensors, not cuda ones)
 extern "C" int mtip_emulated(void) { return 1; }
+
+// launch log (kernel choice tests): copies up to cap - 1 bytes of it into buf (NUL terminated), returns its full length
+extern "C" int mtip_emul_launch_log(char* buf, int cap) {
+    std::lock_guard<std::mutex> guard(emul::launch_mutex);
+    if (buf != nullptr && cap > 0) {
+        const size_t n = std::min(emul::launch_log.size(), (size_t)cap - 1);
+        std::memcpy(buf, emul::launch_log.data(), n);
+        buf[n] = 0;
+    }
+    return (int)emul::launch_log.size();
+}
+extern "C" void mtip_emul_launch_log_reset(void) {
+    std::lock_guard<std::mutex> guard(emul::launch_mutex);
+    emul::launch_log.clear();
+}

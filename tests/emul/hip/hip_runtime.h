@@ -60,6 +60,7 @@ extern thread_local dim3 b_idx;
 extern thread_local unsigned char* dyn_smem;
 extern dim3 b_dim, g_dim;
 void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& body);
+void log_launch(const char* kernel);
 void block_barrier();
 void wave_barrier();
 WaveBuf& wave_buf();
@@ -77,8 +78,9 @@ inline int wave() { return t_linear / WAVE; }
 static const int warpSize = 64;
 
 #define HIP_DYNAMIC_SHARED(type, var) type* var = reinterpret_cast<type*>(emul::dyn_smem);
+// every launch is logged by kernel name (the text up to the template arguments), read by the tests through mtip_emul_launch_log
 #define hipLaunchKernelGGL(kernel, grid, block, smem, stream, ...) \
-    emul::launch((grid), (block), (smem), [&]() { kernel(__VA_ARGS__); })
+    (emul::log_launch(#kernel), emul::launch((grid), (block), (smem), [&]() { kernel(__VA_ARGS__); }))
 
 static inline void __syncthreads() { emul::block_barrier(); }
 

@@ -6,6 +6,7 @@ Tolerances (SURVEY section 8 d / BASELINE.md section 5, fp64 end to end):
   per operator rel-L2 <= 1e-12 (Hankel, elementwise, GEMMs), <= 1e-10 (SHT; polar factor via V_l U_l),
   one full step <= 1e-9, 20-step trajectory <= 1e-6.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -17,6 +18,7 @@ from oracle.fourier import FourierPair
 from oracle.sht import SHT
 from xframe_amd.fxs import reconstruct as R
 from xframe_amd.fxs import synthetic as S
+from xframe_amd.fxs._lib import MtipError
 from xframe_amd.fxs.engine import Engine
 
 TOL_OP = 1e-12
@@ -29,36 +31,61 @@ def cplx(rng, shape):
     return rng.normal(size=shape) + 1j * rng.normal(size=shape)
 
 
-def transforms_engine(N, L, lib_path, n_batch=2, mode='midpoint'):
+def transforms_engine(N, L, lib_path, n_batch=2, mode='midpoint', n_theta=0, n_phi=0):
     max_q = float(np.max(S.midpoint_points(S.data_cutoff(N), N)))
-    e = Engine({'grid': {'n_radial_points': N, 'max_order': L}, 'fourier_transform': {'type': mode}}, None,
-               n_batch=n_batch, lib_path=lib_path, max_q=max_q)
-    fp = FourierPair(SHT(L), N, max_q, 2.0, mode)
+    e = Engine({'grid': {'n_radial_points': N, 'max_order': L, 'n_theta': n_theta, 'n_phi': n_phi},
+                'fourier_transform': {'type': mode}}, None, n_batch=n_batch, lib_path=lib_path, max_q=max_q)
+    fp = FourierPair(SHT(L, n_theta, n_phi), N, max_q, 2.0, mode)
     return e, fp
 
 
-def check_transforms(N, L, lib_path, seed=0, mode='midpoint', expect_chain=None):
-    e, fp = transforms_engine(N, L, lib_path, mode=mode)
+def launched_kernels(e, prefixes=('k_sht', 'k_fft', 'k_leg')):
+    """names of the kernels (with one of `prefixes`) the CPU emulator launched since the previous call, in launch order; the log
+    is reset.  None for a library without the launch log (the GPU build)."""
+    lib = e.lib
+    if not hasattr(lib, 'mtip_emul_launch_log'):
+        return None
+    n = lib.mtip_emul_launch_log(None, 0)
+    buf = ctypes.create_string_buffer(n + 1)
+    lib.mtip_emul_launch_log(buf, n + 1)
+    lib.mtip_emul_launch_log_reset()
+    return tuple(k for k in buf.value.decode().split('\n') if k.startswith(prefixes))
+
+
+def check_transforms(N, L, lib_path, seed=0, mode='midpoint', expect_chain=None, n_theta=0, n_phi=0, n_batch=2,
+                     expect_kernels=None):
+    """operators against the oracle at one geometry; expect_kernels = (forward, inverse, inverse -> forward): the SHT kernel names
+    one call of each launches (checked where the library logs its launches: the CPU emulator)"""
+    e, fp = transforms_engine(N, L, lib_path, n_batch=n_batch, mode=mode, n_theta=n_theta, n_phi=n_phi)
     sht = fp.sht
     assert (e.n_theta, e.n_phi) == (sht.n_theta, sht.n_phi)
     rng = np.random.default_rng(seed)
-    g = cplx(rng, (2,) + e.shape)
-    co = cplx(rng, (2, N, e.nlm))
+    g = cplx(rng, (n_batch,) + e.shape)
+    co = cplx(rng, (n_batch, N, e.nlm))
+    launched = []
+    launched_kernels(e)
     assert rel_l2(e.sht_forward(g), sht.forward_d(g)) < TOL_SHT
+    launched.append(launched_kernels(e))
     assert rel_l2(e.sht_forward(g, 1), sht.forward_d(g * g.conj())) < TOL_SHT
     assert rel_l2(e.sht_forward(g, 2), sht.forward_d(np.abs(g))) < TOL_SHT
+    launched_kernels(e)
     assert rel_l2(e.sht_inverse(co), sht.inverse_d(co)) < TOL_SHT
+    launched.append(launched_kernels(e))
     # the chained inverse -> forward kernel: the grid is that of the inverse transform, the coefficients those of the oracle's
     # two transforms one after the other
     e.profile(True)
     for pro in (0, 1):
         gi, ci = e.sht_inverse_forward(co, pro)
+        if pro == 0:
+            launched.append(launched_kernels(e))
         ref_g = sht.inverse_d(co)
         assert rel_l2(gi, ref_g) < TOL_SHT
         assert rel_l2(ci, sht.forward_d(ref_g * ref_g.conj() if pro else ref_g)) < TOL_SHT
     if expect_chain is not None:
         assert (e.profile_get('sht_chain')[1] > 0) == expect_chain, e.profile_get('sht_chain')
     e.profile(False)
+    if expect_kernels is not None and launched[0] is not None:
+        assert tuple(launched) == tuple(tuple(k) for k in expect_kernels), launched
     assert rel_l2(e.hankel(co), fp.hankel(co)) < TOL_OP
     assert rel_l2(e.hankel(co, True), fp.ihankel(co)) < TOL_OP
     assert rel_l2(e.fourier_transform(g), fp.ft(g)) < TOL_SHT
@@ -304,6 +331,26 @@ def check_ft_stab_disagreement(g, lib_path=None):
         for k in ('real_density', 'last_real_density', 'reciprocal_density', 'last_reciprocal_density'):
             assert rel_l2(r[k], ref[k]) < 1e-8, k
         assert (r['last_support_mask'] != ref['last_support_mask']).sum() == 0
+
+
+def check_ft_stab_disagreement_refused(g, lib_path=None):
+    """restarts that disagree on ft_stab need the fused one-pass step (the wide inverse's real-space epilogue: MTIP_SHT_TIER >= 4);
+    without it the run call fails before it enqueues anything -- no kernel launched, no step counted"""
+    N, L = int(g['N']), int(g['L'])
+    e = Engine(golden_settings(N, L), data_from_golden(g, L), n_batch=2, lib_path=lib_path, fused=True)
+    for b in range(2):
+        e.set_density(b, g['rho0'])
+    e.init_state()
+    _, first = e.best_error()
+    launched_kernels(e, prefixes=('k_',))
+    try:
+        e.run('HIO', np.array([True, False]), [1.0, 1.0])
+        raise AssertionError('a per-restart ft_stab mask ran without the one-pass step')
+    except MtipError as err:
+        assert 'ft_stab' in str(err), err
+    assert launched_kernels(e, prefixes=('k_',)) in ((), None)
+    assert e.best_error()[1] == first
+    e.close()
 
 
 def check_group_run_identical(g, lib_path, fused=True, sizes=(2, 1, 1)):

@@ -22,12 +22,31 @@ def emul_lib():
     return EMUL_LIB
 
 
-# n_phi = 16, 32, 8, 64, 128, 128, 256; the chained inverse -> forward kernel exists where the register FFTs do and a shell fits one
-# CU's LDS (k_sht_chain.hip: run-time table variants at 16 / 32 / 64, register-table variants <2, 8> and <3, 8> at 128)
-@pytest.mark.parametrize('N,L,chain', [(16, 4, True), (10, 7, True), (8, 2, False), (6, 12, True), (4, 24, True), (3, 32, True),
-                                       (3, 44, False)])
-def test_transforms(emul_lib, N, L, chain):
-    PC.check_transforms(N, L, emul_lib, seed=N + L, expect_chain=chain)
+# Kernel choice (ShtPlan, k_sht.hip) by geometry alone, with the SHT kernels one forward / inverse / inverse -> forward call
+# launches (emulator launch log): the chained kernel where an instantiation exists (n_phi <= 128) and a shell fits one CU's LDS,
+# else the wide inverse + paired forward, the pass-wise register kernels (both directions must fit: L = 55 at 128 x 256), the LDS
+# Stockham kernels (n_phi = 4, 8, not a register-FFT size; L = 63 at 128 x 256, the register inverse does not fit), the generic
+# kernels (odd n_theta, n_phi = 512).  Recorded at the commit before the planner, identical but for 16 x 256: its chain
+# instantiation did not exist (the launch did nothing), it now takes the separate transforms.
+CHAIN = ('k_sht_fwd_pair',), ('k_sht_inv_wide',), ('k_sht_chain',)
+WIDE = ('k_sht_fwd_pair',), ('k_sht_inv_wide',), ('k_sht_inv_wide', 'k_sht_fwd_pair')
+REG = ('k_sht_fwd_reg',), ('k_sht_inv_reg',), ('k_sht_inv_reg', 'k_sht_fwd_reg')
+LDS = ('k_sht_fwd_fused',), ('k_sht_inv_fused',), ('k_sht_inv_fused', 'k_sht_fwd_fused')
+GENERIC = ('k_fft_fwd', 'k_leg_fwd'), ('k_leg_inv', 'k_fft_inv'), ('k_leg_inv', 'k_fft_inv', 'k_fft_fwd', 'k_leg_fwd')
+
+
+def _grid_case(N, L, n_theta, n_phi, n_batch, kernels):
+    return pytest.param(N, L, n_theta, n_phi, n_batch, kernels, id=f'{N}-{L}-{n_theta}x{n_phi}-{n_batch}')
+
+
+@pytest.mark.parametrize('N,L,n_theta,n_phi,n_batch,kernels', [
+    pytest.param(N, L, 0, 0, 2, k, id=f'{N}-{L}-{k is CHAIN}') for N, L, k in
+    [(16, 4, CHAIN), (10, 7, CHAIN), (8, 2, LDS), (6, 12, CHAIN), (4, 24, CHAIN), (3, 32, CHAIN), (3, 44, WIDE)]] + [
+    _grid_case(5, 1, 0, 0, 2, LDS), _grid_case(4, 4, 9, 0, 2, GENERIC), _grid_case(3, 8, 0, 512, 2, GENERIC),
+    _grid_case(2, 55, 128, 256, 1, REG), _grid_case(2, 63, 128, 256, 1, LDS), _grid_case(3, 8, 16, 256, 2, WIDE)])
+def test_transforms(emul_lib, N, L, n_theta, n_phi, n_batch, kernels):
+    PC.check_transforms(N, L, emul_lib, seed=N + L, expect_chain=kernels is CHAIN, n_theta=n_theta, n_phi=n_phi, n_batch=n_batch,
+                        expect_kernels=kernels)
 
 
 def test_transforms_trapz(emul_lib):
@@ -62,6 +81,11 @@ def test_engine_group_rendezvous(emul_lib, golden_mtip16):
 
 def test_ft_stab_disagreement(emul_lib, golden_mtip16):
     PC.check_ft_stab_disagreement(golden_mtip16, emul_lib)
+
+
+def test_ft_stab_disagreement_needs_one_pass_step(emul_lib, golden_mtip16, monkeypatch):
+    monkeypatch.setenv('MTIP_SHT_TIER', '3')
+    PC.check_ft_stab_disagreement_refused(golden_mtip16, emul_lib)
 
 
 @pytest.mark.parametrize('fused', [False, True])

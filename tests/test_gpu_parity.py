@@ -20,6 +20,14 @@ def test_transforms(N, L, chain):
     PC.check_transforms(N, L, None, seed=N + L, expect_chain=chain)
 
 
+# grids that take the register, LDS and generic tiers (tests/test_emul_preflight.py checks the kernel names), and 16 x 256: no
+# chained kernel is instantiated for n_phi = 256, the separate transforms run
+@pytest.mark.parametrize('N,L,n_theta,n_phi,n_batch', [(5, 1, 0, 0, 2), (4, 4, 9, 0, 2), (3, 8, 0, 512, 2), (2, 55, 128, 256, 1),
+                                                       (2, 63, 128, 256, 1), (3, 8, 16, 256, 2)])
+def test_transforms_grid(N, L, n_theta, n_phi, n_batch):
+    PC.check_transforms(N, L, None, seed=N + L, expect_chain=False, n_theta=n_theta, n_phi=n_phi, n_batch=n_batch)
+
+
 def test_transforms_trapz():
     PC.check_transforms(12, 3, None, seed=3, mode='trapz')
 
@@ -330,9 +338,11 @@ def test_config5_properties_full_size():
 
 
 # ---- every MTIP_* switch that selects another kernel of the shipping library gets a forced parity case ------------------
-_TRAJ_SWITCHES = [('MTIP_SHT_MODE', '0'), ('MTIP_SHT_MODE', '1'), ('MTIP_SHT_WIDE', '0'), ('MTIP_FUSE_REAL', '0'),
-                  ('MTIP_DEG2_SIMPLE', '1'), ('MTIP_SHT_FWD_PAIR', '0'),
-                  ('MTIP_PROJ_FUSE', '0'), ('MTIP_PROJ_REAL', '0'), ('MTIP_SHT_CHAIN', '0'), ('MTIP_RP_CORR', '0')]
+# (MTIP_SHT_TIER caps the SHT kernel tier: 0 generic, 1 LDS FFT, 2 pass-wise register FFT, 3 + wide inverse / paired forward,
+# 4 + real-space epilogue, default 5 + chained kernel)
+_TRAJ_SWITCHES = [('MTIP_SHT_TIER', '0'), ('MTIP_SHT_TIER', '1'), ('MTIP_SHT_TIER', '2'), ('MTIP_SHT_TIER', '3'),
+                  ('MTIP_SHT_TIER', '4'), ('MTIP_DEG2_SIMPLE', '1'),
+                  ('MTIP_PROJ_FUSE', '0'), ('MTIP_PROJ_REAL', '0'), ('MTIP_RP_CORR', '0')]
 
 
 @pytest.mark.parametrize('name,value', _TRAJ_SWITCHES)

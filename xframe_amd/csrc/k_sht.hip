@@ -4,7 +4,9 @@
 // Convention: orthonormal Y_lm with Condon-Shortley phase, index l(l+1)+m -- what the reference gets
 // from shtns (xframe/externalLibraries/shtns_plugin.py:20-24, 250-261).
 #include "mtip_internal.h"
+#include "k_sht_common.h"
 #include <cmath>
+#include <cstdlib>
 
 // ------------------------------------------------------------------------------------------------
 // Legendre table  P[(poff[m] + l - m) * nt + t] = Y_lm(theta_t, 0),  m >= 0   (host, one-off)
@@ -300,15 +302,139 @@ static void fft_launch_dims(const mtip_ctx* c, long long nrows, dim3* grid, dim3
     *smem = (size_t)2 * R * c->np * sizeof(double2);
 }
 
-void launch_sht_forward(mtip_ctx* c, const double2* grid, double2* coeff, int prologue, int in_slot) {
-    ProfScope ps(c, "sht_fwd");
-    if (sht_reg_supported(c)) {
-        launch_sht_forward_reg(c, grid, coeff, prologue, in_slot);
-        return;
+// ------------------------------------------------------------------------------------------------------------------------------
+// The SHT plan (ShtPlan, mtip_internal.h): the only place that reads the geometry or the environment to pick an SHT kernel.
+// Tier k is taken where MTIP_SHT_TIER >= k (default 5) and the geometry fits it; the launchers below and in k_sht_reg.hip,
+// k_sht_fused.hip, k_sht_chain.hip only read the plan.
+static constexpr size_t SHT_LDS_MAX = 160 * 1024, SHT_WIDE_LDS_MAX = 158 * 1024;
+
+// wide inverse kernel with `nsplit` workgroups per shell (see the kernel): LDS bytes, 0 if it does not fit; *rp = rows per FFT pass
+static size_t wide_lds(const mtip_ctx* c, int r1, int r2, int nsplit, int* rp) {
+    if (c->nt % (2 * nsplit) != 0) return 0;
+    const int ntl = c->nt / nsplit;
+    if (nsplit > 1 && (ntl / 2) % 32 != 0) return 0;                   // whole 32-theta chunks per workgroup
+    const size_t fixed = (nsplit > 1 ? 0 : (size_t)c->np) + (size_t)ntl * c->nm + c->npairs;
+    // the transpose buffer aliases the coefficient block: shrink the pass until both fit
+    auto bytes = [&](int v) { return (fixed + std::max((size_t)c->nlm, (size_t)v * r1 * (r2 + 1))) * sizeof(double2); };
+    *rp = largest_even_divisor_le(ntl, std::min(SW_THREADS / r2, SW_THREADS / r1));
+    while (*rp >= 2 && bytes(*rp) > SHT_WIDE_LDS_MAX) *rp = largest_even_divisor_le(ntl, *rp - 2);
+    return *rp >= 2 ? bytes(*rp) : 0;
+}
+
+// the chained kernel (k_sht_chain.hip), instantiated for n_phi <= 128: accumulation groups of the Legendre-sum phase are the
+// smallest power-of-two group whose threads hold <= 3 (l, m) pairs each and whose count divides the theta pairs
+static void plan_chain(const mtip_ctx* c, int r1, int r2, ShtPlan& p) {
+    if (c->np > 128) return;
+    const int TP = c->nt / 2;
+    for (int gsz = 64; gsz <= SW_THREADS; gsz *= 2) {
+        const int maxi = div_up(c->npairs, gsz);
+        if (TP % (SW_THREADS / gsz) != 0 || maxi > 3) continue;
+        p.chain_gsz = gsz;
+        p.chain_thg = TP / (SW_THREADS / gsz);
+        // table rows in registers for the 128-point grids, else the run-time variants
+        const bool reg_tab = c->np == 128 && p.chain_thg == 16 && maxi >= 2;
+        p.chain_maxi = reg_tab ? maxi : (maxi == 1 ? 1 : 3);
+        p.chain = !reg_tab ? SHT_CHAIN_RT
+                : (p.chain_maxi == 3 && c->L == 32 && c->nt == 64 && c->chain_chunks > 0) ? SHT_CHAIN_L32 : SHT_CHAIN_REGTAB;
+        break;
     }
-    if (sht_fused_supported(c)) {
+    if (p.chain == SHT_CHAIN_OFF) return;
+    // every wave owns 64 / R2 rows at a time and a transpose buffer for them; it, the panel staging and the groups' partial sums
+    // at the end alias the coefficient block
+    const size_t tb = (size_t)(SW_THREADS / 64) * (64 / r2) * r1 * (r2 + 1);
+    const size_t fixed = (size_t)c->np + (size_t)c->nt * c->nm + c->npairs;
+    p.chain_lds = (fixed + std::max(std::max((size_t)c->nlm, tb), (size_t)SW_THREADS * p.chain_maxi * 2)) * sizeof(double2);
+    if (p.chain_lds > SHT_WIDE_LDS_MAX) p.chain = SHT_CHAIN_OFF;
+}
+
+void plan_sht(mtip_ctx* c) {
+    int cap = 5;
+    if (const char* e = std::getenv("MTIP_SHT_TIER")) cap = std::min(std::max(std::atoi(e), 0), 5);
+    ShtPlan p;
+    const int nt = c->nt, np = c->np;
+    const size_t z = sizeof(double2);
+    // tier 2: register FFTs, taken only where the forward AND the inverse kernel fit
+    int r1 = 0, r2 = 0;
+    if (cap >= 2 && nt % 2 == 0 && reg_radices(np, &r1, &r2)) {
+        p.fwd_rp = largest_even_divisor_le(nt, std::min(2 * SR_THREADS / r2, SR_THREADS / r1));
+        p.inv_rp = largest_even_divisor_le(nt, std::min(SR_THREADS / r2, SR_THREADS / r1));
+        p.fwd_lds = ((size_t)np + (size_t)p.fwd_rp * r1 * (r2 + 1)) * z;
+        p.inv_lds = ((size_t)np + c->nlm + (size_t)p.inv_rp * c->nm + (size_t)p.inv_rp * r1 * (r2 + 1)) * z;
+        if (p.fwd_rp >= 2 && p.inv_rp >= 2 && p.fwd_lds <= SHT_LDS_MAX && p.inv_lds <= SHT_LDS_MAX) {
+            p.fwd = SHT_FWD_REG;
+            p.inv = SHT_INV_REG;
+        }
+    }
+    if (p.fwd == SHT_FWD_REG) {
+        const int per = div_up(c->npairs, SR_THREADS);
+        p.fwd_maxi = per <= 3 ? 3 : per <= 5 ? 5 : 9;
+        // tier 3: the paired forward kernel (half the rows per pass, theta pairs per pass 2, 4 or 8) ...
+        const int th = p.fwd_rp / 4;
+        if (cap >= 3 && p.fwd_rp % 4 == 0 && (th == 2 || th == 4 || th == 8) && (nt / 2) % th == 0 && per <= 5) {
+            p.fwd = SHT_FWD_PAIR;
+            p.fwd_th = th;
+            p.fwd_lds = ((size_t)np + (size_t)(p.fwd_rp / 2) * r1 * (r2 + 1)) * z;
+        }
+        // ... and the wide inverse kernel, one workgroup per shell or else two
+        for (int ns = 1; cap >= 3 && ns <= 2 && p.inv != SHT_INV_WIDE; ++ns) {
+            int rp = 0;
+            const size_t lds = wide_lds(c, r1, r2, ns, &rp);
+            if (lds == 0) continue;
+            p.inv = SHT_INV_WIDE;
+            p.inv_rp = rp;
+            p.inv_nsplit = ns;
+            p.inv_lds = lds;
+        }
+        // tier 4: the wide kernel's real-space epilogue (and coefficient difference on load); tier 5: the chained kernel
+        p.real_update = cap >= 4 && p.inv == SHT_INV_WIDE;
+        p.real_update_blocks = c->N * p.inv_nsplit;
+        if (cap >= 5) plan_chain(c, r1, r2, p);
+    } else if (cap >= 1 && np >= 4 && np <= SF_THREADS && nt % 2 == 0) {
+        // tier 1: LDS Stockham FFTs; a pass is a whole number of row pairs that tiles n_theta
+        p.fwd = SHT_FWD_LDS;
+        p.inv = SHT_INV_LDS;
+        int rp = std::max(2, std::min(SF_THREADS / (np / 2), nt));
+        while (nt % rp) --rp;
+        if (rp & 1) rp = 2;
+        p.fwd_rp = p.inv_rp = rp;
+        const int per = div_up(c->npairs, SF_THREADS);
+        p.fwd_maxi = per <= 3 ? 3 : per <= 5 ? 5 : 9;
+        p.fwd_lds = ((size_t)np / 2 + 2 * (size_t)rp * np + (size_t)rp * c->nm) * z;
+        const int nchunks = std::max(1, div_up((long long)(nt / 2) * ((c->L + 2) / 2), SF_THREADS));
+        p.inv_jl = div_up(nt / 2, nchunks);
+        p.inv_lds = ((size_t)np / 2 + c->nlm + (size_t)2 * p.inv_jl * c->nm + 2 * (size_t)rp * np) * z;
+    } else {
+        p = ShtPlan();                                  // tier 0: generic kernels
+    }
+    c->sht = p;
+}
+
+static const char* epi_name(int mode) {
+    switch (mode) {
+        case EPI_STORE: return "store";
+        case EPI_MODULUS: return "modulus";
+        case EPI_SCALE_SHELL: return "shell scale";
+        case EPI_MODULUS_FIXED: return "fixed modulus";
+        case EPI_REAL_UPDATE: return "real-space update";
+        default: return "unknown";
+    }
+}
+
+int sht_no_kernel(mtip_ctx* c, const char* what, int epi_mode) {
+    c->err = std::string("SHT plan: no kernel for this case: ") + what + ", epilogue " + epi_name(epi_mode) +
+             " (MTIP_SHT_TIER and the angular grid decide which kernels exist)";
+    return MTIP_ESTATE;
+}
+
+int launch_sht_forward(mtip_ctx* c, const double2* grid, double2* coeff, int prologue, int in_slot) {
+    ProfScope ps(c, "sht_fwd");
+    if (c->sht.fwd == SHT_FWD_REG || c->sht.fwd == SHT_FWD_PAIR) {
+        launch_sht_forward_reg(c, grid, coeff, prologue, in_slot);
+        return MTIP_OK;
+    }
+    if (c->sht.fwd == SHT_FWD_LDS) {
         launch_sht_forward_fused(c, grid, coeff, prologue, in_slot);
-        return;
+        return MTIP_OK;
     }
     const long long nrows = (long long)c->B * c->N * c->nt;
     dim3 gr, bl;
@@ -325,19 +451,18 @@ void launch_sht_forward(mtip_ctx* c, const double2* grid, double2* coeff, int pr
     const long long total = (long long)c->B * c->N * c->nlm;
     hipLaunchKernelGGL(k_leg_fwd, dim3((unsigned)div_up(total, 256)), dim3(256), 0, c->stream,
                        (const double2*)c->d_g, coeff, (const double*)c->d_P, (const int*)c->d_poff, c->nt, c->L, total);
+    return MTIP_OK;
 }
 
-void launch_sht_inverse(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
+int launch_sht_inverse(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
+    // the real-space epilogue and the coefficient difference on load exist in the wide kernel only
+    if ((epi.mode == EPI_REAL_UPDATE || epi.coeff_sub != nullptr) && !c->sht.real_update)
+        return sht_no_kernel(c, epi.coeff_sub != nullptr ? "inverse with coefficient difference" : "inverse", epi.mode);
     // timer families by epilogue: they move different amounts of data
     ProfScope ps(c, epi.mode == EPI_REAL_UPDATE ? "sht_inv_real" : (epi.mode == EPI_MODULUS || epi.mode == EPI_MODULUS_FIXED) ? "sht_inv_modulus" : "sht_inv");
-    if (sht_reg_supported(c)) {
-        launch_sht_inverse_reg(c, coeff, grid, epi);
-        return;
-    }
-    if (sht_fused_supported(c)) {
-        launch_sht_inverse_fused(c, coeff, grid, epi);
-        return;
-    }
+    if (c->sht.inv == SHT_INV_REG || c->sht.inv == SHT_INV_WIDE) return launch_sht_inverse_reg(c, coeff, grid, epi);
+    if (c->sht.inv == SHT_INV_LDS) return launch_sht_inverse_fused(c, coeff, grid, epi);
+    if (epi.mode != EPI_STORE && epi.mode != EPI_MODULUS && epi.mode != EPI_SCALE_SHELL) return sht_no_kernel(c, "generic inverse", epi.mode);
     const long long nrows = (long long)c->B * c->N * c->nt;
     const long long total = nrows * c->nm;
     hipLaunchKernelGGL(k_leg_inv, dim3((unsigned)div_up(total, 256)), dim3(256), 0, c->stream, coeff, c->d_g,
@@ -359,4 +484,5 @@ void launch_sht_inverse(mtip_ctx* c, const double2* coeff, double2* grid, const 
             hipLaunchKernelGGL(k_fft_inv<EPI_STORE>, gr, bl, sm, c->stream, g, grid, tw, c->np, c->nt, c->L, c->N, nrows, epi.F, epi.shell_scale, sl, epi.out_slot, c->B);
             break;
     }
+    return MTIP_OK;
 }

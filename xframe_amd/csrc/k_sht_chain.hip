@@ -462,88 +462,41 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-struct ChainGeom {
-    int r1 = 0, r2 = 0, gsz = 0, thg = 0, maxi = 0;     // maxi: the kernel's MAXI (>= pairs per thread)
-    bool reg_tab = false;
-    size_t tb = 0;                      // double2 of the waves' transpose buffers
-    size_t lds = 0;
-    bool ok = false;
-};
-
-static ChainGeom chain_geom(const mtip_ctx* c) {
-    ChainGeom g;
-    if (!sht_reg_supported(c) || !c->sht_wide || c->d_AB == nullptr || c->d_PT == nullptr || c->d_lmtab == nullptr) return g;
-    if (!reg_radices(c->np, &g.r1, &g.r2) || (c->nt & 1)) return g;
-    // every wave owns 64 / R2 rows at a time and a transpose buffer for them; it aliases the coefficient block
-    g.tb = (size_t)(SW_THREADS / 64) * (64 / g.r2) * g.r1 * (g.r2 + 1);
-    const size_t fixed = (size_t)c->np + (size_t)c->nt * c->nm + c->npairs;
-    const int TP = c->nt / 2;                       // theta pairs of a shell
-    // accumulation groups of the Legendre-sum phase: the smallest power-of-two group whose threads hold <= 3 (l, m) pairs each
-    // and whose count divides the theta pairs
-    for (int gsz = 64; gsz <= SW_THREADS; gsz *= 2) {
-        const int ngrp = SW_THREADS / gsz;
-        if (TP % ngrp != 0) continue;
-        const int maxi = div_up(c->npairs, gsz);
-        if (maxi > 3) continue;
-        g.gsz = gsz;
-        g.thg = TP / ngrp;
-        // the instantiation launch_chain_r picks: table rows in registers for the 128-point grids, else the run-time variants
-        g.reg_tab = c->np == 128 && g.thg == 16 && maxi >= 2;
-        g.maxi = g.reg_tab ? maxi : (maxi == 1 ? 1 : 3);
-        break;
-    }
-    if (g.gsz == 0) return g;
-    // transpose buffer / panel staging aliases the coefficient block; the groups' partial sums land there at the end
-    const size_t un = std::max(std::max((size_t)c->nlm, g.tb), (size_t)SW_THREADS * g.maxi * 2);
-    g.lds = (fixed + un) * sizeof(double2);
-    g.ok = g.lds <= 158 * 1024;
-    return g;
-}
-
-bool sht_chain_supported(const mtip_ctx* c) {
-    return c->sht_chain && chain_geom(c).ok;
-}
-
+// the instantiation plan_sht chose (k_sht.hip); a 256-point shell does not fit one CU, so there is none for n_phi = 256
 template <int EPI, int PRE, int R1, int R2>
-static void launch_chain_r(mtip_ctx* c, const ChainGeom& g, const ChainArgs& a) {
+static void launch_chain_r(mtip_ctx* c, const ChainArgs& a) {
+    const ShtPlan& p = c->sht;
     const dim3 gr((unsigned)(c->B * c->N)), bl(SW_THREADS);
-#define CHAIN_GO(MAXI, THG) hipLaunchKernelGGL((k_sht_chain<EPI, PRE, R1, R2, MAXI, THG, false, 0, false>), gr, bl, g.lds, c->stream, a)
+#define CHAIN_GO(MAXI, THG, DBG, LC, CHK) hipLaunchKernelGGL((k_sht_chain<EPI, PRE, R1, R2, MAXI, THG, DBG, LC, CHK>), gr, bl, p.chain_lds, c->stream, a)
     if constexpr (R1 * R2 == 128) {
-        const bool metric_grid = g.reg_tab && g.maxi == 3 && c->L == 32 && c->nt == 64 && c->chain_chunks > 0;
-        if (metric_grid && a.dbg != nullptr) {                   // phase stamps: the metric's grid only
-            hipLaunchKernelGGL((k_sht_chain<EPI, PRE, R1, R2, 3, 16, true, 32, true>), gr, bl, g.lds, c->stream, a);
-            return;
-        }
-        if (metric_grid && c->sht_chain_lc) {                   // the metric's grid: L at compile time, chunk layout of the sums
-            hipLaunchKernelGGL((k_sht_chain<EPI, PRE, R1, R2, 3, 16, false, 32, true>), gr, bl, g.lds, c->stream, a);
-            return;
-        }
-        if (g.reg_tab && g.maxi == 3) { CHAIN_GO(3, 16); return; }
-        if (g.reg_tab && g.maxi == 2) { CHAIN_GO(2, 16); return; }
+        if (p.chain == SHT_CHAIN_L32 && a.dbg != nullptr) CHAIN_GO(3, 16, true, 32, true);     // phase stamps: this grid only
+        else if (p.chain == SHT_CHAIN_L32) CHAIN_GO(3, 16, false, 32, true);
+        else if (p.chain == SHT_CHAIN_REGTAB && p.chain_maxi == 3) CHAIN_GO(3, 16, false, 0, false);
+        else if (p.chain == SHT_CHAIN_REGTAB) CHAIN_GO(2, 16, false, 0, false);
     }
-    if constexpr (R1 * R2 < 256) {                  // a 256-point shell does not fit one CU (chain_geom)
-        if (g.maxi == 1) CHAIN_GO(1, 0);
-        else CHAIN_GO(3, 0);
-    }
+    if (p.chain == SHT_CHAIN_RT && p.chain_maxi == 1) CHAIN_GO(1, 0, false, 0, false);
+    else if (p.chain == SHT_CHAIN_RT) CHAIN_GO(3, 0, false, 0, false);
 #undef CHAIN_GO
 }
 
 template <int EPI, int PRE>
-static void launch_chain_p(mtip_ctx* c, const ChainGeom& g, const ChainArgs& a) {
+static void launch_chain_p(mtip_ctx* c, const ChainArgs& a) {
     switch (c->np) {
-        case 16: launch_chain_r<EPI, PRE, 4, 4>(c, g, a); break;
-        case 32: launch_chain_r<EPI, PRE, 4, 8>(c, g, a); break;
-        case 64: launch_chain_r<EPI, PRE, 8, 8>(c, g, a); break;
-        case 128: launch_chain_r<EPI, PRE, 8, 16>(c, g, a); break;
-        default: launch_chain_r<EPI, PRE, 16, 16>(c, g, a); break;
+        case 16: launch_chain_r<EPI, PRE, 4, 4>(c, a); break;
+        case 32: launch_chain_r<EPI, PRE, 4, 8>(c, a); break;
+        case 64: launch_chain_r<EPI, PRE, 8, 8>(c, a); break;
+        default: launch_chain_r<EPI, PRE, 8, 16>(c, a); break;
     }
 }
 
 // grid = epilogue(iSHT(coeff)), coeff_out = SHT(prologue(grid)).  Epilogues: EPI_STORE (prologue |.|^2: the F -> I_lm link of a
-// step), EPI_MODULUS and EPI_REAL_UPDATE (no prologue).  Caller checks sht_chain_supported().
-void launch_sht_chain(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi, int prologue, double2* coeff_out) {
+// step), EPI_MODULUS and EPI_REAL_UPDATE (no prologue, no coeff_sub).
+int launch_sht_chain(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi, int prologue, double2* coeff_out) {
+    if (c->sht.chain == SHT_CHAIN_OFF) return sht_no_kernel(c, "chained inverse -> forward transform (none planned)", epi.mode);
+    const bool store = epi.mode == EPI_STORE && (prologue == MTIP_PRE_NONE || prologue == MTIP_PRE_SQUARE);
+    if (epi.coeff_sub != nullptr || !(store || (prologue == MTIP_PRE_NONE && (epi.mode == EPI_MODULUS || epi.mode == EPI_REAL_UPDATE))))
+        return sht_no_kernel(c, "chained inverse -> forward transform", epi.mode);
     ProfScope ps(c, epi.mode == EPI_REAL_UPDATE ? "sht_chain_real" : epi.mode == EPI_MODULUS ? "sht_chain_modulus" : "sht_chain");
-    const ChainGeom g = chain_geom(c);
     ChainArgs a;
     a.coeff = coeff;
     a.grid = grid;
@@ -568,12 +521,13 @@ void launch_sht_chain(mtip_ctx* c, const double2* coeff, double2* grid, const In
     a.lmc = c->d_lmc;
     a.gw = c->d_gw;
     a.norm = 2.0 * 3.14159265358979323846 / c->np;
-    a.gsz = g.gsz;
-    a.thg = g.thg;
+    a.gsz = c->sht.chain_gsz;
+    a.thg = c->sht.chain_thg;
     a.dbg = c->d_chain_dbg ? c->d_chain_dbg + (size_t)(epi.mode == EPI_REAL_UPDATE ? 2 : epi.mode == EPI_MODULUS ? 1 : 0) * c->B * c->N * MTIP_CHAIN_DBG_SLOTS
                            : nullptr;
-    if (epi.mode == EPI_REAL_UPDATE) launch_chain_p<EPI_REAL_UPDATE, MTIP_PRE_NONE>(c, g, a);
-    else if (epi.mode == EPI_MODULUS) launch_chain_p<EPI_MODULUS, MTIP_PRE_NONE>(c, g, a);
-    else if (prologue == MTIP_PRE_SQUARE) launch_chain_p<EPI_STORE, MTIP_PRE_SQUARE>(c, g, a);
-    else launch_chain_p<EPI_STORE, MTIP_PRE_NONE>(c, g, a);
+    if (epi.mode == EPI_REAL_UPDATE) launch_chain_p<EPI_REAL_UPDATE, MTIP_PRE_NONE>(c, a);
+    else if (epi.mode == EPI_MODULUS) launch_chain_p<EPI_MODULUS, MTIP_PRE_NONE>(c, a);
+    else if (prologue == MTIP_PRE_SQUARE) launch_chain_p<EPI_STORE, MTIP_PRE_SQUARE>(c, a);
+    else launch_chain_p<EPI_STORE, MTIP_PRE_NONE>(c, a);
+    return MTIP_OK;
 }

@@ -86,6 +86,7 @@ __device__ __forceinline__ void half_fft(const double2 (&x)[R], int half, double
 }
 
 #define SW_THREADS 512
+#define SF_THREADS 256                  // LDS Stockham kernels (k_sht_fused.hip)
 
 static inline bool reg_radices(int np, int* r1, int* r2) {
     switch (np) {

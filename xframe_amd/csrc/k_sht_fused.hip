@@ -14,8 +14,7 @@
 // L = 32): forward lanes walk consecutive pair indices (coalesced), inverse threads walk l for fixed (theta, m).
 // Symmetries used: Y_l,-m(theta,0) = (-1)^m Y_lm(theta,0);  Y_lm(pi - theta, 0) = (-1)^(l+m) Y_lm(theta, 0).
 #include "mtip_internal.h"
-
-#define SF_THREADS 256
+#include "k_sht_common.h"
 
 __device__ __forceinline__ void stockham_pass_lds(double2*& x, double2*& y, const double2* __restrict__ tw, int np, int T,
                                                   int i, bool active, bool inverse) {
@@ -254,33 +253,17 @@ __global__ void __launch_bounds__(SF_THREADS) k_sht_inv_fused(const double2* __r
 }
 
 // ------------------------------------------------------------------------------------------------------
-bool sht_fused_supported(const mtip_ctx* c) {
-    return c->np <= SF_THREADS && c->np >= 4 && (c->nt % 2) == 0 && c->d_PT != nullptr && !c->sht_unfused;
-}
-
-static int fused_rpe(const mtip_ctx* c) {
-    int rp = SF_THREADS / (c->np / 2);
-    if (rp > c->nt) rp = c->nt;
-    if (rp < 2) rp = 2;                  // np = 512: T = 256 -> one row per pass is not supported (needs a pair)
-    while (c->nt % rp) --rp;             // passes must tile n_theta; rp stays even because n_theta is even
-    if (rp & 1) rp = 2;
-    return rp;
-}
-
 template <int PRE>
 static void launch_fwd_t(mtip_ctx* c, const double2* grid, double2* coeff, int in_slot) {
-    const int rpe = fused_rpe(c);
-    const int T = c->np / 2;
-    const size_t smem = ((size_t)T + 2 * (size_t)rpe * c->np + (size_t)rpe * c->nm) * sizeof(double2);
+    const ShtPlan& p = c->sht;
     const double norm = 2.0 * 3.14159265358979323846 / c->np;
     const int* sl = in_slot >= 0 ? c->d_slot : nullptr;
     const dim3 gr((unsigned)(c->B * c->N)), bl(SF_THREADS);
-    const int per = div_up(c->npairs, SF_THREADS);
 #define FWD_ARGS grid, coeff, (const double*)c->d_PT, (const int*)c->d_lmtab, (const double2*)c->d_tw, (const double*)c->d_gw, \
-                 c->np, c->nt, c->L, c->npairs, rpe, norm, sl, in_slot, c->B, c->N
-    if (per <= 3) hipLaunchKernelGGL((k_sht_fwd_fused<PRE, 3>), gr, bl, smem, c->stream, FWD_ARGS);
-    else if (per <= 5) hipLaunchKernelGGL((k_sht_fwd_fused<PRE, 5>), gr, bl, smem, c->stream, FWD_ARGS);
-    else hipLaunchKernelGGL((k_sht_fwd_fused<PRE, 9>), gr, bl, smem, c->stream, FWD_ARGS);
+                 c->np, c->nt, c->L, c->npairs, p.fwd_rp, norm, sl, in_slot, c->B, c->N
+    if (p.fwd_maxi == 3) hipLaunchKernelGGL((k_sht_fwd_fused<PRE, 3>), gr, bl, p.fwd_lds, c->stream, FWD_ARGS);
+    else if (p.fwd_maxi == 5) hipLaunchKernelGGL((k_sht_fwd_fused<PRE, 5>), gr, bl, p.fwd_lds, c->stream, FWD_ARGS);
+    else hipLaunchKernelGGL((k_sht_fwd_fused<PRE, 9>), gr, bl, p.fwd_lds, c->stream, FWD_ARGS);
 #undef FWD_ARGS
 }
 
@@ -290,22 +273,18 @@ void launch_sht_forward_fused(mtip_ctx* c, const double2* grid, double2* coeff, 
     else launch_fwd_t<MTIP_PRE_NONE>(c, grid, coeff, in_slot);
 }
 
-void launch_sht_inverse_fused(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
-    const int rpe = fused_rpe(c);
-    const int T = c->np / 2;
-    const int nth = c->nt / 2;
-    const int ipt = (c->L + 2) / 2;
-    const int nchunks = std::max(1, div_up((long long)nth * ipt, SF_THREADS));
-    const int jl = div_up(nth, nchunks);
-    const size_t smem = ((size_t)T + c->nlm + (size_t)2 * jl * c->nm + 2 * (size_t)rpe * c->np) * sizeof(double2);
+int launch_sht_inverse_fused(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
+    const ShtPlan& p = c->sht;
     const int* sl = epi.out_slot >= 0 ? c->d_slot : nullptr;
     const dim3 gr((unsigned)(c->B * c->N)), bl(SF_THREADS);
 #define INV_ARGS coeff, grid, (const double*)c->d_PT, (const int*)c->d_poff, (const double2*)c->d_tw, c->np, c->nt, c->L, \
-                 c->npairs, rpe, jl, c->N, epi.F, epi.shell_scale, sl, epi.out_slot, c->B
+                 c->npairs, p.inv_rp, p.inv_jl, c->N, epi.F, epi.shell_scale, sl, epi.out_slot, c->B
     switch (epi.mode) {
-        case EPI_MODULUS: hipLaunchKernelGGL(k_sht_inv_fused<EPI_MODULUS>, gr, bl, smem, c->stream, INV_ARGS); break;
-        case EPI_SCALE_SHELL: hipLaunchKernelGGL(k_sht_inv_fused<EPI_SCALE_SHELL>, gr, bl, smem, c->stream, INV_ARGS); break;
-        default: hipLaunchKernelGGL(k_sht_inv_fused<EPI_STORE>, gr, bl, smem, c->stream, INV_ARGS); break;
+        case EPI_STORE: hipLaunchKernelGGL(k_sht_inv_fused<EPI_STORE>, gr, bl, p.inv_lds, c->stream, INV_ARGS); break;
+        case EPI_MODULUS: hipLaunchKernelGGL(k_sht_inv_fused<EPI_MODULUS>, gr, bl, p.inv_lds, c->stream, INV_ARGS); break;
+        case EPI_SCALE_SHELL: hipLaunchKernelGGL(k_sht_inv_fused<EPI_SCALE_SHELL>, gr, bl, p.inv_lds, c->stream, INV_ARGS); break;
+        default: return sht_no_kernel(c, "LDS-FFT inverse", epi.mode);
     }
 #undef INV_ARGS
+    return MTIP_OK;
 }

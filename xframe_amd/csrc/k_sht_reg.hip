@@ -637,54 +637,34 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_inv_wide(const double2* __re
 }
 
 // ------------------------------------------------------------------------------------------------------
-bool sht_inverse_fuses_real_update(const mtip_ctx* c);
-
-bool sht_reg_supported(const mtip_ctx* c) {
-    int r1, r2;
-    if (c->sht_mode < 2 || c->d_PT == nullptr || c->d_twN == nullptr || (c->nt & 1)) return false;
-    if (!reg_radices(c->np, &r1, &r2)) return false;
-    const int rpf = largest_even_divisor_le(c->nt, std::min(2 * SR_THREADS / r2, SR_THREADS / r1));
-    const int rpi = largest_even_divisor_le(c->nt, std::min(SR_THREADS / r2, SR_THREADS / r1));
-    if (rpf < 2 || rpi < 2) return false;
-    const size_t lds_f = ((size_t)c->np + (size_t)rpf * r1 * (r2 + 1)) * sizeof(double2);
-    const size_t lds_i = ((size_t)c->np + c->nlm + (size_t)rpi * c->nm + (size_t)rpi * r1 * (r2 + 1)) * sizeof(double2);
-    return lds_f <= 160 * 1024 && lds_i <= 160 * 1024;
-}
-
 template <int PRE, int R1, int R2>
 static void launch_fwd_r(mtip_ctx* c, const double2* grid, double2* coeff, int in_slot) {
-    const int RP = largest_even_divisor_le(c->nt, std::min(2 * SR_THREADS / R2, SR_THREADS / R1));
-    const size_t smem = ((size_t)c->np + (size_t)RP * R1 * (R2 + 1)) * sizeof(double2);
+    const ShtPlan& p = c->sht;
     const double norm = 2.0 * 3.14159265358979323846 / c->np;
     const int* sl = in_slot >= 0 ? c->d_slot : nullptr;
     const dim3 gr((unsigned)(c->B * c->N)), bl(SR_THREADS);
-    const int per = div_up(c->npairs, SR_THREADS);
-    // k_sht_fwd_pair: half the rows per pass, the table rows of a pass prefetched (one round trip per pass).  Measured at
-    // 128 x L32 (hipEvent brackets, k_sht_fwd_reg / this kernel with one / with two shells per workgroup): 8 restarts per launch
-    // 54.5 / 49.9 / 50.4 us, 3 restarts per launch 37.6 / 33.9 / 42.8 us -- one shell per workgroup it is
-    const int th = RP / 4;
-    const bool pair_geom = RP % 4 == 0 && (th == 2 || th == 4 || th == 8) && (c->nt / 2) % std::max(th, 1) == 0 && per <= 5;
-    if (c->sht_fwd_pair && pair_geom) {
-        const size_t smem_p = ((size_t)c->np + (size_t)(RP / 2) * R1 * (R2 + 1)) * sizeof(double2);
+    if (p.fwd == SHT_FWD_PAIR) {
+        // k_sht_fwd_pair: half the rows per pass, the table rows of a pass prefetched (one round trip per pass).  Measured at
+        // 128 x L32 (hipEvent brackets, k_sht_fwd_reg / this kernel with one / with two shells per workgroup): 8 restarts per launch
+        // 54.5 / 49.9 / 50.4 us, 3 restarts per launch 37.6 / 33.9 / 42.8 us -- one shell per workgroup it is
 #define PAIR_ARGS grid, coeff, (const double*)c->d_PT, (const int*)c->d_lmtab, (const double2*)c->d_twN, (const double*)c->d_gw, \
                   c->nt, c->L, c->npairs, norm, sl, in_slot, c->B, c->N
 #define PAIR_NS(MAXI, TH)                                                                                                        \
-        if constexpr (TH * R2 <= SR_THREADS && 2 * TH * R1 <= SR_THREADS) {                                                      \
-            hipLaunchKernelGGL((k_sht_fwd_pair<PRE, R1, R2, MAXI, TH, 1>), gr, bl, smem_p, c->stream, PAIR_ARGS);                 \
-            return;                                                                                                              \
-        }
+        if constexpr (TH * R2 <= SR_THREADS && 2 * TH * R1 <= SR_THREADS)                                                        \
+            hipLaunchKernelGGL((k_sht_fwd_pair<PRE, R1, R2, MAXI, TH, 1>), gr, bl, p.fwd_lds, c->stream, PAIR_ARGS);
 #define PAIR_TH(MAXI)                                                                                                            \
-        if (th == 8) { PAIR_NS(MAXI, 8) } else if (th == 4) { PAIR_NS(MAXI, 4) } else { PAIR_NS(MAXI, 2) }
-        if (per <= 3) { PAIR_TH(3) } else { PAIR_TH(5) }
+        if (p.fwd_th == 8) { PAIR_NS(MAXI, 8) } else if (p.fwd_th == 4) { PAIR_NS(MAXI, 4) } else { PAIR_NS(MAXI, 2) }
+        if (p.fwd_maxi == 3) { PAIR_TH(3) } else { PAIR_TH(5) }
 #undef PAIR_TH
 #undef PAIR_NS
 #undef PAIR_ARGS
+        return;
     }
 #define FWD_ARGS grid, coeff, (const double*)c->d_PT, (const int*)c->d_lmtab, (const double2*)c->d_twN, (const double*)c->d_gw, \
-                 c->nt, c->L, c->npairs, RP, norm, sl, in_slot, c->B, c->N
-    if (per <= 3) hipLaunchKernelGGL((k_sht_fwd_reg<PRE, R1, R2, 3>), gr, bl, smem, c->stream, FWD_ARGS);
-    else if (per <= 5) hipLaunchKernelGGL((k_sht_fwd_reg<PRE, R1, R2, 5>), gr, bl, smem, c->stream, FWD_ARGS);
-    else hipLaunchKernelGGL((k_sht_fwd_reg<PRE, R1, R2, 9>), gr, bl, smem, c->stream, FWD_ARGS);
+                 c->nt, c->L, c->npairs, p.fwd_rp, norm, sl, in_slot, c->B, c->N
+    if (p.fwd_maxi == 3) hipLaunchKernelGGL((k_sht_fwd_reg<PRE, R1, R2, 3>), gr, bl, p.fwd_lds, c->stream, FWD_ARGS);
+    else if (p.fwd_maxi == 5) hipLaunchKernelGGL((k_sht_fwd_reg<PRE, R1, R2, 5>), gr, bl, p.fwd_lds, c->stream, FWD_ARGS);
+    else hipLaunchKernelGGL((k_sht_fwd_reg<PRE, R1, R2, 9>), gr, bl, p.fwd_lds, c->stream, FWD_ARGS);
 #undef FWD_ARGS
 }
 
@@ -705,55 +685,23 @@ void launch_sht_forward_reg(mtip_ctx* c, const double2* grid, double2* coeff, in
     else launch_fwd_p<MTIP_PRE_NONE>(c, grid, coeff, in_slot);
 }
 
-// LDS of the wide inverse kernel for `nsplit` workgroups per shell (see the kernel); *rp_out = rows per FFT pass
-static size_t wide_lds_n(const mtip_ctx* c, int r1, int r2, int nsplit, int* rp_out) {
-    if (c->nt % (2 * nsplit) != 0) return (size_t)1 << 40;
-    const int ntl = c->nt / nsplit;
-    if (nsplit > 1 && (ntl / 2) % 32 != 0) return (size_t)1 << 40;      // whole 32-theta chunks per workgroup
-    const size_t fixed = (nsplit > 1 ? 0 : (size_t)c->np) + (size_t)ntl * c->nm + c->npairs;
-    int rp = largest_even_divisor_le(ntl, std::min(SW_THREADS / r2, SW_THREADS / r1));
-    // the transpose buffer aliases the coefficient block: shrink the pass until both fit
-    while (rp >= 2 && (fixed + std::max((size_t)c->nlm, (size_t)rp * r1 * (r2 + 1))) * sizeof(double2) > 158 * 1024)
-        rp = largest_even_divisor_le(ntl, rp - 2);
-    if (rp_out) *rp_out = rp;
-    if (rp < 2) return (size_t)1 << 40;
-    return (fixed + std::max((size_t)c->nlm, (size_t)rp * r1 * (r2 + 1))) * sizeof(double2);
-}
-
-// smallest split (1, 2) whose working set fits one CU's LDS
-static size_t wide_lds(const mtip_ctx* c, int r1, int r2, int* rp_out, int* nsplit_out = nullptr) {
-    for (int ns = 1; ns <= 2; ++ns) {
-        int rp = 0;
-        const size_t lds = wide_lds_n(c, r1, r2, ns, &rp);
-        if (lds <= 158 * 1024) {
-            if (rp_out) *rp_out = rp;
-            if (nsplit_out) *nsplit_out = ns;
-            return lds;
-        }
-    }
-    if (rp_out) *rp_out = 0;
-    if (nsplit_out) *nsplit_out = 1;
-    return (size_t)1 << 40;
-}
-
 template <int EPI, int R1, int R2>
 static void launch_inv_r(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
-    int rpw = 0, nsplit = 1;
-    const size_t lds_w = wide_lds(c, R1, R2, &rpw, &nsplit);
-    if (c->sht_wide && c->d_AB != nullptr && lds_w <= 158 * 1024) {
+    const ShtPlan& p = c->sht;
+    if (p.inv == SHT_INV_WIDE) {
         const int* slw = (epi.out_slot >= 0 || EPI == EPI_REAL_UPDATE) ? c->d_slot : nullptr;
-        hipLaunchKernelGGL((k_sht_inv_wide<EPI, R1, R2>), dim3((unsigned)(c->B * c->N * nsplit)), dim3(SW_THREADS), lds_w, c->stream,
+        hipLaunchKernelGGL((k_sht_inv_wide<EPI, R1, R2>), dim3((unsigned)(c->B * c->N * p.inv_nsplit)), dim3(SW_THREADS), p.inv_lds, c->stream,
                            coeff, grid, (const double*)c->d_P, (const int*)c->d_poff, (const double2*)c->d_AB,
-                           (const double*)c->d_cost, c->npairs, (const double2*)c->d_twN, c->nt, c->L, rpw, c->N, epi.F, epi.shell_scale, slw, epi.out_slot, c->B, epi.coeff_sub, epi.real, nsplit);
+                           (const double*)c->d_cost, c->npairs, (const double2*)c->d_twN, c->nt, c->L, p.inv_rp, c->N, epi.F, epi.shell_scale, slw, epi.out_slot, c->B, epi.coeff_sub, epi.real, p.inv_nsplit);
         return;
     }
-    const int RP = largest_even_divisor_le(c->nt, std::min(SR_THREADS / R2, SR_THREADS / R1));
-    const size_t smem = ((size_t)c->np + c->nlm + (size_t)RP * c->nm + (size_t)RP * R1 * (R2 + 1)) * sizeof(double2);
-    const int* sl = epi.out_slot >= 0 ? c->d_slot : nullptr;
-    const dim3 gr((unsigned)(c->B * c->N)), bl(SR_THREADS);
-    hipLaunchKernelGGL((k_sht_inv_reg<EPI, R1, R2>), gr, bl, smem, c->stream, coeff, grid, (const double*)c->d_PT,
-                       (const int*)c->d_poff, (const double2*)c->d_twN, c->nt, c->L, c->npairs, RP, c->N, epi.F,
-                       epi.shell_scale, sl, epi.out_slot, c->B);
+    if constexpr (EPI != EPI_REAL_UPDATE) {            // the pass-wise kernel has no real-space epilogue
+        const int* sl = epi.out_slot >= 0 ? c->d_slot : nullptr;
+        const dim3 gr((unsigned)(c->B * c->N)), bl(SR_THREADS);
+        hipLaunchKernelGGL((k_sht_inv_reg<EPI, R1, R2>), gr, bl, p.inv_lds, c->stream, coeff, grid, (const double*)c->d_PT,
+                           (const int*)c->d_poff, (const double2*)c->d_twN, c->nt, c->L, c->npairs, p.inv_rp, c->N, epi.F,
+                           epi.shell_scale, sl, epi.out_slot, c->B);
+    }
 }
 
 template <int EPI>
@@ -767,27 +715,13 @@ static void launch_inv_p(mtip_ctx* c, const double2* coeff, double2* grid, const
     }
 }
 
-void launch_sht_inverse_reg(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
+int launch_sht_inverse_reg(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
     switch (epi.mode) {
+        case EPI_STORE: launch_inv_p<EPI_STORE>(c, coeff, grid, epi); break;
         case EPI_MODULUS: launch_inv_p<EPI_MODULUS>(c, coeff, grid, epi); break;
         case EPI_SCALE_SHELL: launch_inv_p<EPI_SCALE_SHELL>(c, coeff, grid, epi); break;
-        case EPI_REAL_UPDATE: launch_inv_p<EPI_REAL_UPDATE>(c, coeff, grid, epi); break;
-        default: launch_inv_p<EPI_STORE>(c, coeff, grid, epi); break;
+        case EPI_REAL_UPDATE: launch_inv_p<EPI_REAL_UPDATE>(c, coeff, grid, epi); break;     // wide kernel (launch_sht_inverse)
+        default: return sht_no_kernel(c, "register-FFT inverse", epi.mode);
     }
-}
-
-// error partial sums the fused real-space epilogue writes per restart (one per workgroup)
-int sht_inverse_real_update_blocks(const mtip_ctx* c) {
-    int r1, r2, ns = 1;
-    if (!reg_radices(c->np, &r1, &r2)) return c->N;
-    wide_lds(c, r1, r2, nullptr, &ns);
-    return c->N * ns;
-}
-
-// the fused real-space epilogue and the on-load coefficient difference exist in the wide inverse kernel only
-bool sht_inverse_fuses_real_update(const mtip_ctx* c) {
-    int r1, r2;
-    if (!sht_reg_supported(c) || !c->sht_wide || c->d_AB == nullptr || !c->fuse_real_update) return false;
-    if (!reg_radices(c->np, &r1, &r2)) return false;
-    return wide_lds(c, r1, r2, nullptr) <= 158 * 1024;
+    return MTIP_OK;
 }

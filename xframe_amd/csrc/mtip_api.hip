@@ -132,11 +132,6 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     A(dev_alloc(c, &c->d_lmc, 768));
     if (const char* e = std::getenv("MTIP_PROJ_FUSE")) c->proj_fuse = std::atoi(e) != 0;
     if (const char* e = std::getenv("MTIP_DEG2_SIMPLE")) c->deg2_simple = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MTIP_SHT_FWD_PAIR")) c->sht_fwd_pair = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MTIP_FUSE_REAL")) c->fuse_real_update = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MTIP_SHT_WIDE")) c->sht_wide = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MTIP_SHT_CHAIN")) c->sht_chain = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MTIP_SHT_CHAIN_LC")) c->sht_chain_lc = std::atoi(e) != 0;
     if (const char* e = std::getenv("MTIP_JAC_RESIDENT")) c->jac_resident = std::atoi(e) != 0;
     if (const char* e = std::getenv("MTIP_JAC_TG")) c->jac_tg = std::atoi(e) == 8 ? 8 : 16;
     if (const char* e = std::getenv("MTIP_HANKEL_CT")) {
@@ -145,8 +140,6 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     }
     if (rc == MTIP_OK) rc = build_hankel_tiles(c);
     A(dev_alloc(c, &c->d_twN, c->np));
-    if (const char* e = std::getenv("MTIP_SHT_MODE")) c->sht_mode = std::atoi(e);
-    c->sht_unfused = c->sht_mode < 1;
     A(dev_alloc(c, &c->d_tw, c->np / 2));
     A(dev_alloc(c, &c->d_r, N));
     A(dev_alloc(c, &c->d_q, N));
@@ -275,6 +268,7 @@ int mtip_set_angular_grid(mtip_ctx* c, const double* cos_theta, const double* ga
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_cost, cos_theta, c->nt * sizeof(double), hipMemcpyHostToDevice));
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_gw, gauss_weights, c->nt * sizeof(double), hipMemcpyHostToDevice));
     build_legendre_tables(c, cos_theta);
+    plan_sht(c);
     c->have_angular = true;
     return MTIP_OK;
 }
@@ -479,11 +473,17 @@ static int require_loop(mtip_ctx* c) {
 }
 
 // grid -> grid Fourier transform, fourier_transforms.py:57-85 (in_slot/out via epilogue possible)
-static void ft_pipeline(mtip_ctx* c, const double2* in, int in_slot, double2* out, int inverse, int prologue,
-                        const InvEpilogue& epi, double2* ca, double2* cb) {
-    launch_sht_forward(c, in, ca, prologue, in_slot);
+#define TRY(call)                      \
+    do {                               \
+        const int r__ = (call);        \
+        if (r__ != MTIP_OK) return r__; \
+    } while (0)
+
+static int ft_pipeline(mtip_ctx* c, const double2* in, int in_slot, double2* out, int inverse, int prologue,
+                       const InvEpilogue& epi, double2* ca, double2* cb) {
+    TRY(launch_sht_forward(c, in, ca, prologue, in_slot));
     launch_hankel(c, ca, cb, inverse);
-    launch_sht_inverse(c, cb, out, epi);
+    return launch_sht_inverse(c, cb, out, epi);
 }
 
 static int ensure_hist(mtip_ctx* c, long long need) {
@@ -545,35 +545,28 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
     // Chained kernels (k_sht_chain.hip): in the fused step every inverse SHT hands its shell to the forward SHT that reads the
     // same grid next -- F -> SHT(|F|^2), F' -> SHT(F'), rho_new -> SHT(rho_new) of the NEXT step (kept in d_c0n, valid while
     // nothing but k_finish_step's rotation touches the current density)
-    const bool one_pass_diff = c->cfg.fused && ft_stab && hankel_has_difference(c) && sht_inverse_fuses_real_update(c);
-    const bool chain = c->cfg.fused && sht_chain_supported(c);
+    const bool one_pass_diff = c->cfg.fused && ft_stab && hankel_has_difference(c) && c->sht.real_update;
+    const bool chain = c->cfg.fused && c->sht.chain != SHT_CHAIN_OFF;
     if (phases & STEP_HEAD) {
         // 1  F = FT(rho_cur)
         const double2* c0 = cc[0];
         if (chain && c->c0n_valid) c0 = c->d_c0n;
-        else launch_sht_forward(c, c->d_rho, cc[0], MTIP_PRE_NONE, SL_CUR);
+        else TRY(launch_sht_forward(c, c->d_rho, cc[0], MTIP_PRE_NONE, SL_CUR));
         c->c0n_valid = false;
         launch_hankel(c, c0, cc[1], 0);
-        if (chain && fxs) launch_sht_chain(c, cc[1], c->d_F, store, MTIP_PRE_SQUARE, cc[2]);
-        else launch_sht_inverse(c, cc[1], c->d_F, store);
+        if (chain && fxs) TRY(launch_sht_chain(c, cc[1], c->d_F, store, MTIP_PRE_SQUARE, cc[2]));
+        else TRY(launch_sht_inverse(c, cc[1], c->d_F, store));
         if (fxs) {
             // 2-3 I_lm = SHT(|F|^2)
-            if (!chain) launch_sht_forward(c, c->d_F, cc[2], MTIP_PRE_SQUARE);
+            if (!chain) TRY(launch_sht_forward(c, c->d_F, cc[2], MTIP_PRE_SQUARE));
             if (c->deg2_enable) launch_deg2_metric(c, cc[2], c->d_deg2_hist + (size_t)c->n_steps_done * c->B * (c->L + 1));
-            if (c->im_which) {
-                const int rm = launch_invariant_metrics(c, cc[2], c->n_steps_done);
-                if (rm != MTIP_OK) return rm;
-            }
+            if (c->im_which) TRY(launch_invariant_metrics(c, cc[2], c->n_steps_done));
         }
     }
     if (phases & STEP_PROJ) {
         // 4-5 projection
-        if (fxs) {
-            const int rp = launch_project_coefficients(c, cc[2], cc[2], true);    // in place: I_lm is not needed afterwards; SHT of the real |F|^2
-            if (rp != MTIP_OK) return rp;
-        } else {
-            launch_modulus_fixed_slots(c, c->d_F);
-        }
+        if (fxs) TRY(launch_project_coefficients(c, cc[2], cc[2], true));   // in place: I_lm is not needed afterwards; SHT of the real |F|^2
+        else launch_modulus_fixed_slots(c, c->d_F);
     }
     if (!(phases & STEP_TAIL)) return MTIP_OK;
     if (fxs) {
@@ -582,19 +575,18 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
         mod.mode = EPI_MODULUS;
         mod.F = c->d_F;
         mod.out_slot = SL_OUT;
-        if (chain) launch_sht_chain(c, cc[2], c->d_Fp, mod, MTIP_PRE_NONE, cc[4]);
-        else launch_sht_inverse(c, cc[2], c->d_Fp, mod);
+        if (chain) TRY(launch_sht_chain(c, cc[2], c->d_Fp, mod, MTIP_PRE_NONE, cc[4]));
+        else TRY(launch_sht_inverse(c, cc[2], c->d_Fp, mod));
         launch_reciprocal_l2_metric(c, c->d_F, c->d_Fp, c->n_steps_done);     // (non-default metric; no launch unless enabled)
     }
     // 9  rho' = IFT(F')
-    if (!(chain && fxs)) launch_sht_forward(c, c->d_Fp, cc[4], MTIP_PRE_NONE, SL_OUT);
+    if (!(chain && fxs)) TRY(launch_sht_forward(c, c->d_Fp, cc[4], MTIP_PRE_NONE, SL_OUT));
     // rho'' = rho + IFT(F' - F) on shells > 0, IFT(F') on shell 0, using SHT(F) == Hankel(SHT(rho)) = cc[1]: with the
     // workgroup-tiled Hankel kernel the difference is taken on load and shell 0 corrected in the same pass
     // per-restart ft_stab (mtip_set_ft_stab_mask: the reference decides the link to enforce_initial_support per reconstruction
     // process, reconstruct.py:836-850): the restarts without it neither subtract SHT(F) here nor add rho_prev back in the epilogue
+    // (run_prelude has checked that such a mask meets the one-pass step)
     const uint8_t* ftm = (ft_stab && c->ftmask_mixed) ? c->d_ftmask : nullptr;
-    if (ftm && !(one_pass_diff && sht_inverse_fuses_real_update(c)))
-        FAIL(c, MTIP_ESTATE, "a per-restart ft_stab mask needs the fused one-pass step (cfg.fused, tiled Hankel kernel, real update in the SHT epilogue)");
     if (one_pass_diff) {
         ProfScope ps(c, "hankel");
         launch_hankel_mfma_sub(c, cc[4], cc[1], cc[5], 1, ftm);
@@ -603,7 +595,7 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
     }
     if (c->cfg.fused && ft_stab) {
         if (!one_pass_diff) launch_hankel(c, cc[1], cc[0], 1);
-        if (sht_inverse_fuses_real_update(c)) {
+        if (c->sht.real_update) {
             // coefficient difference on load, constraints + HIO/ER + error sums in the epilogue: the density of
             // this step is written once and nothing else of grid size moves
             InvEpilogue ru;
@@ -624,28 +616,28 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
             ru.real.beta = beta;
             if (chain && one_pass_diff) {
                 // the new density goes to slot SL_OUT, which k_finish_step makes the current one: its SHT is the next step's
-                launch_sht_chain(c, cc[5], nullptr, ru, MTIP_PRE_NONE, c->d_c0n);
+                TRY(launch_sht_chain(c, cc[5], nullptr, ru, MTIP_PRE_NONE, c->d_c0n));
                 launch_finish_step(c, c->n_steps_done, c->N);
                 c->c0n_valid = true;
             } else {
-                launch_sht_inverse(c, cc[5], nullptr, ru);
-                launch_finish_step(c, c->n_steps_done, sht_inverse_real_update_blocks(c));
+                TRY(launch_sht_inverse(c, cc[5], nullptr, ru));
+                launch_finish_step(c, c->n_steps_done, c->sht.real_update_blocks);
             }
             c->n_steps_done += 1;
             return MTIP_OK;
         }
         launch_coeff_diff(c, cc[5], cc[0], cc[4]);
-        launch_sht_inverse(c, cc[4], c->d_T1, store);
+        TRY(launch_sht_inverse(c, cc[4], c->d_T1, store));
         // prev enters twice: as the add-back (rho_rt = 0 path) -- handled by passing a zero round trip
         launch_real_update(c, c->d_T1, c->d_rho, c->d_T2 /*zeros*/, c->d_rho, method, beta, 1);
     } else {
-        launch_sht_inverse(c, cc[5], c->d_T1, store);
+        TRY(launch_sht_inverse(c, cc[5], c->d_T1, store));
         const double2* rt = nullptr;
         if (ft_stab) {
             // rho_rt = IFT(F)
-            launch_sht_forward(c, c->d_F, cc[0], MTIP_PRE_NONE);
+            TRY(launch_sht_forward(c, c->d_F, cc[0], MTIP_PRE_NONE));
             launch_hankel(c, cc[0], cc[4], 1);
-            launch_sht_inverse(c, cc[4], c->d_T2, store);
+            TRY(launch_sht_inverse(c, cc[4], c->d_T2, store));
             rt = c->d_T2;
         }
         launch_real_update(c, c->d_T1, c->d_rho, rt, c->d_rho, method, beta, 1);
@@ -655,12 +647,18 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
     return MTIP_OK;
 }
 
-// checks and one-time work in front of the steps of a run (shared by mtip_run_async and mtip_run_group_async)
+// checks and one-time work in front of the steps of a run (shared by mtip_run_async and mtip_run_group_async); every check comes
+// before the first launch, so a run that cannot be done enqueues nothing
 static int run_prelude(mtip_ctx* c, int method, int ft_stab, int n_steps, const double* betas) {
     int r = require_loop(c);
     if (r) return r;
     if (method < 0 || method > 3) FAIL(c, MTIP_EINVAL, "unknown method");
     if (n_steps < 0 || (n_steps > 0 && !betas)) FAIL(c, MTIP_EINVAL, "bad n_steps / betas");
+    const bool fxs = (method == MTIP_HIO || method == MTIP_ER);
+    if (c->main_mode == 1 && !(c->deg2_enable && fxs))
+        FAIL(c, MTIP_ESTATE, "main error over deg2_invariant_l2_diff needs that metric enabled (mtip_set_deg2_metric) and an FXS method");
+    if (ft_stab && c->ftmask_mixed && !(c->cfg.fused && hankel_has_difference(c) && c->sht.real_update))
+        FAIL(c, MTIP_ESTATE, "a per-restart ft_stab mask needs the fused one-pass step (cfg.fused, tiled Hankel kernel, real update in the SHT epilogue)");
     (void)hipSetDevice(c->device);
     r = ensure_hist(c, c->n_steps_done + n_steps);
     if (r) return r;
@@ -668,9 +666,6 @@ static int run_prelude(mtip_ctx* c, int method, int ft_stab, int n_steps, const 
         r = build_bref(c);
         if (r) return r;
     }
-    const bool fxs = (method == MTIP_HIO || method == MTIP_ER);
-    if (c->main_mode == 1 && !(c->deg2_enable && fxs))
-        FAIL(c, MTIP_ESTATE, "main error over deg2_invariant_l2_diff needs that metric enabled (mtip_set_deg2_metric) and an FXS method");
     if (!fxs) {
         if (!c->fixed_valid) {
             launch_abs_to_fixed(c);                  // reconstruct.py:899-902
@@ -681,7 +676,7 @@ static int run_prelude(mtip_ctx* c, int method, int ft_stab, int n_steps, const 
     }
     // the separate real-space kernel of the fused ft_stab step reads a zero round trip (the add-back is already in the
     // coefficients); the epilogue path does not use T2 at all
-    if (c->cfg.fused && ft_stab && !sht_inverse_fuses_real_update(c))
+    if (c->cfg.fused && ft_stab && !c->sht.real_update)
         MTIP_HIP_CHECK(c, hipMemsetAsync(c->d_T2, 0, (size_t)c->B * c->G * sizeof(double2), c->stream));
     return MTIP_OK;
 }
@@ -854,8 +849,8 @@ int mtip_init_state(mtip_ctx* c) {
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_slot, slots.data(), slots.size() * sizeof(int), hipMemcpyHostToDevice));
     InvEpilogue to_slot;
     to_slot.out_slot = SL_OUT;
-    ft_pipeline(c, c->d_T1, -1, c->d_Fp, 0, MTIP_PRE_NONE, to_slot, c->d_c[0], c->d_c[1]);
-    ft_pipeline(c, c->d_Fp, SL_CUR, c->d_rho, 1, MTIP_PRE_NONE, to_slot, c->d_c[0], c->d_c[1]);
+    TRY(ft_pipeline(c, c->d_T1, -1, c->d_Fp, 0, MTIP_PRE_NONE, to_slot, c->d_c[0], c->d_c[1]));
+    TRY(ft_pipeline(c, c->d_Fp, SL_CUR, c->d_rho, 1, MTIP_PRE_NONE, to_slot, c->d_c[0], c->d_c[1]));
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     for (int b = 0; b < c->B; ++b) slots[b * SL_N + SL_OUT] = 1;
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_slot, slots.data(), slots.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -992,9 +987,9 @@ int mtip_shrinkwrap(mtip_ctx* c, double sigma, double threshold, double error_li
     scale.mode = EPI_SCALE_SHELL;
     scale.shell_scale = d_gq;
     // |rho| -> FT -> * G_sigma
-    ft_pipeline(c, c->d_rho, SL_CUR, c->d_T1, 0, MTIP_PRE_ABS, scale, c->d_c[0], c->d_c[1]);
+    TRY(ft_pipeline(c, c->d_rho, SL_CUR, c->d_T1, 0, MTIP_PRE_ABS, scale, c->d_c[0], c->d_c[1]));
     // IFT
-    ft_pipeline(c, c->d_T1, -1, c->d_T2, 1, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]);
+    TRY(ft_pipeline(c, c->d_T1, -1, c->d_T2, 1, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]));
     double* tmp = reinterpret_cast<double*>(c->d_T1);
     launch_sw_clamp(c, c->d_T2, tmp);
     launch_sw_threshold(c, tmp, threshold, error_limit);
@@ -1038,7 +1033,7 @@ int mtip_refresh_reciprocal_density(mtip_ctx* c) {
     MTIP_HIP_CHECK(c, mtip_copy(c, slots.data(), c->d_slot, slots.size() * sizeof(int), hipMemcpyDeviceToHost));
     InvEpilogue store;
     c->c0n_valid = false;                // the real half of the latest pair becomes FT(rho)
-    ft_pipeline(c, c->d_rho, SL_CUR, c->d_T1, 0, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]);
+    TRY(ft_pipeline(c, c->d_rho, SL_CUR, c->d_T1, 0, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]));
     for (int b = 0; b < c->B; ++b) {
         int* s = slots.data() + (size_t)b * SL_N;
         const int cur = s[SL_CUR], hist = s[SL_HIST], best = s[SL_BEST];
@@ -1073,8 +1068,8 @@ int mtip_last_deg2_invariant(mtip_ctx* c, int batch, mtip_cdouble* Bl) {
         if (r) return r;
     }
     InvEpilogue store;
-    ft_pipeline(c, c->d_rho, SL_CUR, c->d_T1, 0, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]);
-    launch_sht_forward(c, c->d_T1, c->d_c[2], MTIP_PRE_SQUARE);
+    TRY(ft_pipeline(c, c->d_rho, SL_CUR, c->d_T1, 0, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]));
+    TRY(launch_sht_forward(c, c->d_T1, c->d_c[2], MTIP_PRE_SQUARE));
     launch_deg2(c, c->d_c[2], c->d_Bl);
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     MTIP_HIP_CHECK(c, mtip_copy(c, Bl, c->d_Bl + (size_t)batch * per, per * sizeof(double2), hipMemcpyDeviceToHost));
@@ -1093,7 +1088,7 @@ int mtip_op_sht_forward(mtip_ctx* c, const mtip_cdouble* grid, mtip_cdouble* coe
     (void)hipSetDevice(c->device);
     SYNC();
     H2D(c->d_T1, grid, (size_t)c->B * c->G * sizeof(double2));
-    launch_sht_forward(c, c->d_T1, c->d_c[0], prologue);
+    TRY(launch_sht_forward(c, c->d_T1, c->d_c[0], prologue));
     SYNC();
     D2H(coeff, c->d_c[0], (size_t)c->B * c->C * sizeof(double2));
     return post_launch(c, "mtip_op_sht_forward");
@@ -1107,7 +1102,7 @@ int mtip_op_sht_inverse(mtip_ctx* c, const mtip_cdouble* coeff, mtip_cdouble* gr
     SYNC();
     H2D(c->d_c[0], coeff, (size_t)c->B * c->C * sizeof(double2));
     InvEpilogue store;
-    launch_sht_inverse(c, c->d_c[0], c->d_T1, store);
+    TRY(launch_sht_inverse(c, c->d_c[0], c->d_T1, store));
     SYNC();
     D2H(grid, c->d_T1, (size_t)c->B * c->G * sizeof(double2));
     return post_launch(c, "mtip_op_sht_inverse");
@@ -1121,11 +1116,11 @@ int mtip_op_sht_inverse_forward(mtip_ctx* c, const mtip_cdouble* coeff, mtip_cdo
     SYNC();
     H2D(c->d_c[0], coeff, (size_t)c->B * c->C * sizeof(double2));
     InvEpilogue store;
-    if (sht_chain_supported(c)) {
-        launch_sht_chain(c, c->d_c[0], c->d_T1, store, prologue, c->d_c[1]);
+    if (c->sht.chain != SHT_CHAIN_OFF) {
+        TRY(launch_sht_chain(c, c->d_c[0], c->d_T1, store, prologue, c->d_c[1]));
     } else {
-        launch_sht_inverse(c, c->d_c[0], c->d_T1, store);
-        launch_sht_forward(c, c->d_T1, c->d_c[1], prologue);
+        TRY(launch_sht_inverse(c, c->d_c[0], c->d_T1, store));
+        TRY(launch_sht_forward(c, c->d_T1, c->d_c[1], prologue));
     }
     SYNC();
     D2H(grid, c->d_T1, (size_t)c->B * c->G * sizeof(double2));
@@ -1155,7 +1150,7 @@ int mtip_op_fourier_transform(mtip_ctx* c, const mtip_cdouble* in, mtip_cdouble*
     SYNC();
     H2D(c->d_T1, in, (size_t)c->B * c->G * sizeof(double2));
     InvEpilogue store;
-    ft_pipeline(c, c->d_T1, -1, c->d_T2, inverse ? 1 : 0, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]);
+    TRY(ft_pipeline(c, c->d_T1, -1, c->d_T2, inverse ? 1 : 0, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]));
     SYNC();
     D2H(out, c->d_T2, (size_t)c->B * c->G * sizeof(double2));
     return post_launch(c, "mtip_op_fourier_transform");

@@ -178,6 +178,34 @@ enum { EPI_STORE = 0, EPI_MODULUS = 1, EPI_SCALE_SHELL = 2, EPI_MODULUS_FIXED = 
 
 struct ProfEntry { double ms = 0; long long n = 0; };
 
+// Which SHT kernels run, decided once per context from the geometry (plan_sht, k_sht.hip).  Tier k is taken where the cap
+// MTIP_SHT_TIER (default 5) is >= k and the geometry fits it:  5 the chained inverse -> forward kernel (k_sht_chain), 4 the wide
+// inverse with the real-space epilogue, 3 the wide inverse (k_sht_inv_wide) and the paired forward (k_sht_fwd_pair), 2 the
+// pass-wise register-FFT kernels (k_sht_fwd_reg / k_sht_inv_reg: both directions must fit), 1 the LDS Stockham kernels
+// (k_sht_fused.hip), 0 the generic FFT + Legendre kernels (k_sht.hip).
+enum { SHT_FWD_GENERIC = 0, SHT_FWD_LDS, SHT_FWD_REG, SHT_FWD_PAIR };
+enum { SHT_INV_GENERIC = 0, SHT_INV_LDS, SHT_INV_REG, SHT_INV_WIDE };
+// k_sht_chain instantiations: run-time tables (THG = 0), table rows in registers (THG = 16, n_phi = 128), and the latter with
+// L = 32 at compile time and the chunk layout of the Legendre sums
+enum { SHT_CHAIN_OFF = 0, SHT_CHAIN_RT, SHT_CHAIN_REGTAB, SHT_CHAIN_L32 };
+struct ShtPlan {
+    int fwd = SHT_FWD_GENERIC;
+    int fwd_rp = 0;                    // rows per pass (register / LDS kernels)
+    int fwd_th = 0;                    // theta pairs per pass (paired kernel)
+    int fwd_maxi = 0;                  // (l, m) pairs per thread: the kernel's MAXI
+    size_t fwd_lds = 0;
+    int inv = SHT_INV_GENERIC;
+    int inv_rp = 0;                    // rows per FFT pass
+    int inv_nsplit = 1;                // workgroups per shell (wide)
+    int inv_jl = 0;                    // theta pairs per Legendre chunk (LDS kernel)
+    size_t inv_lds = 0;
+    bool real_update = false;          // the inverse takes EPI_REAL_UPDATE and coeff_sub (wide kernel, tier 4)
+    int real_update_blocks = 0;        // error partial sums per restart that epilogue writes
+    int chain = SHT_CHAIN_OFF;
+    int chain_gsz = 0, chain_thg = 0, chain_maxi = 0;   // accumulation group size, theta pairs per group, MAXI
+    size_t chain_lds = 0;
+};
+
 struct mtip_ctx {
     mtip_cfg cfg{};
     int device = 0;
@@ -198,14 +226,11 @@ struct mtip_ctx {
     int chain_chunks = 0;                             // chunks (threads of an accumulation group with work) in that layout; 0: it does not fit 256
     int* d_lmtab = nullptr;                           // (npairs) l | m << 8
     int npairs = 0;
-    bool sht_unfused = false;                         // MTIP_SHT_MODE=0: two-kernel SHT (A/B testing)
-    int sht_mode = 2;                                 // env MTIP_SHT_MODE: 0 unfused, 1 LDS-Stockham fused, 2 register FFT
+    ShtPlan sht;                                      // SHT kernel choice (plan_sht, at mtip_set_angular_grid)
     double2* d_twN = nullptr;                         // exp(-2 pi i j / n_phi), j < n_phi
     double2* d_tw = nullptr;
     double* d_W = nullptr;
     int n_cu = 256;                                   // compute units of the device (persistent-grid sizing)
-    bool fuse_real_update = true;                     // env MTIP_FUSE_REAL=0: separate coefficient-difference / real-space kernels
-    bool sht_wide = true;                             // env MTIP_SHT_WIDE=0: pass-wise inverse Legendre synthesis
     bool jac_resident = true;                         // env MTIP_JAC_RESIDENT=0: round-robin ordering, both columns via LDS
     int *d_jsched = nullptr, *d_jsched_off = nullptr, *d_jsched_rounds = nullptr;   // resident-column pairing schedule
     int jsched_kmax = 0, jsched_ps = 0;
@@ -229,9 +254,6 @@ struct mtip_ctx {
     int n_pg_tiles[6] = {0, 0, 0, 0, 0, 0};
     long long* d_polar_dbg = nullptr;                 // (B, L+1, MTIP_POLAR_DBG_SLOTS) phase / round timers of k_rproj, allocated by mtip_debug_polar_timing
     int jac_tg = 16;                                  // env MTIP_JAC_TG=8|16: lanes per Jacobi column pair
-    bool sht_fwd_pair = true;                         // env MTIP_SHT_FWD_PAIR=0: k_sht_fwd_reg (table loads inside the accumulation loop)
-    bool sht_chain_lc = true;                         // env MTIP_SHT_CHAIN_LC=0: run-time L also at L = 32 (A/B of the compile-time instantiation)
-    bool sht_chain = true;                            // env MTIP_SHT_CHAIN=0: separate inverse / forward SHT kernels in the fused step (k_sht_chain.hip)
     double2* d_c0n = nullptr;                         // (B, C) SHT of the current density, written by the chained last kernel of a step
     long long* d_chain_dbg = nullptr;                 // (3 kinds, B * Nq, MTIP_CHAIN_DBG_SLOTS) phase stamps of k_sht_chain, allocated by mtip_debug_chain_timing
     bool c0n_valid = false;                           // d_c0n holds SHT(rho[SL_CUR]) of every restart
@@ -314,9 +336,10 @@ struct mtip_ctx {
 };
 
 // ---- launchers (defined next to their kernels) ------------------------------------------------------
-// SHT
+// SHT: the kernels of c->sht; MTIP_OK, or MTIP_ESTATE (c->err set) for an epilogue / prologue the planned kernel does not have
+void plan_sht(mtip_ctx* c);                          // after build_legendre_tables
 // in_slot >= 0: grid is a (3,B,G) slot array read through slot[b][in_slot]
-void launch_sht_forward(mtip_ctx* c, const double2* grid, double2* coeff, int prologue, int in_slot = -1);
+int launch_sht_forward(mtip_ctx* c, const double2* grid, double2* coeff, int prologue, int in_slot = -1);
 struct InvEpilogue {
     int mode = EPI_STORE;
     const double2* F = nullptr;        // EPI_MODULUS*: reciprocal density to rescale
@@ -326,20 +349,16 @@ struct InvEpilogue {
     RealEpi real;                          // EPI_REAL_UPDATE
     int out_slot = -1;                 // >= 0: grid is a (3,B,G) slot array written through slot[b][out_slot]
 };
-void launch_sht_inverse(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi);
+int launch_sht_inverse(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi);
 void build_legendre_tables(mtip_ctx* c, const double* cos_theta);
-bool sht_fused_supported(const mtip_ctx* c);
+int sht_no_kernel(mtip_ctx* c, const char* what, int epi_mode);   // k_sht.hip: sets c->err, returns MTIP_ESTATE
 void launch_sht_forward_fused(mtip_ctx* c, const double2* grid, double2* coeff, int prologue, int in_slot);
-void launch_sht_inverse_fused(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi);
-bool sht_reg_supported(const mtip_ctx* c);
-bool sht_inverse_fuses_real_update(const mtip_ctx* c);    // EPI_REAL_UPDATE / coeff_sub available (wide inverse kernel)
-int sht_inverse_real_update_blocks(const mtip_ctx* c);   // error partial sums per restart written by that epilogue
+int launch_sht_inverse_fused(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi);
 void launch_sht_forward_reg(mtip_ctx* c, const double2* grid, double2* coeff, int prologue, int in_slot);
-void launch_sht_inverse_reg(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi);
+int launch_sht_inverse_reg(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi);
 // k_sht_chain.hip: grid = epilogue(iSHT(coeff)) and coeff_out = SHT(prologue(grid)) in one kernel (EPI_STORE with
-// MTIP_PRE_NONE / MTIP_PRE_SQUARE, EPI_MODULUS, EPI_REAL_UPDATE without coeff_sub)
-bool sht_chain_supported(const mtip_ctx* c);
-void launch_sht_chain(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi, int prologue, double2* coeff_out);
+// MTIP_PRE_NONE / MTIP_PRE_SQUARE, EPI_MODULUS, EPI_REAL_UPDATE without coeff_sub), where c->sht.chain is set
+int launch_sht_chain(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi, int prologue, double2* coeff_out);
 // Hankel
 void launch_hankel(mtip_ctx* c, const double2* in, double2* out, int inverse);
 bool hankel_has_difference(const mtip_ctx* c);       // launch_hankel_mfma_sub is available (workgroup-tiled kernel)
