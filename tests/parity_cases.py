@@ -876,6 +876,11 @@ def check_projection_real_vs_oracle(N, L, lib_path=None, n_batch=2, seed=1, reci
             unk = om.rp.approximate_unknowns(Il)
             ref = np.concatenate(om.rp.mtip_projection(Il, unk), axis=1)
             assert rel_l2(proj[b], ref) < TOL_SHT, (rep, b, rel_l2(proj[b], ref))
+            # per order as well: l = 0 holds much of the norm of these inputs, and an error of one high order is diluted in the
+            # whole-array rel-L2 (about tenfold at 128 x L32)
+            for l in range(L + 1):
+                sl = slice(l * l, (l + 1) ** 2)
+                assert rel_l2(proj[b][:, sl], ref[:, sl]) < TOL_SHT, (rep, b, l, rel_l2(proj[b][:, sl], ref[:, sl]))
             assert proj_c is None or rel_l2(proj[b], proj_c[b]) < TOL_SHT, (rep, b)
             for i, l in enumerate(om.rp.used_orders.values()):
                 # compared through V_l U_l (the unknowns themselves are only defined up to the null space of V_l)
@@ -1903,3 +1908,396 @@ def check_extract_rules_hip(lib_path=None):
 
     check_extract_rules_golden((eig, pm, lambda A, flag: X.nearest_positive_semidefinite_matrix(e, A, flag)))
     e.close()
+
+
+# ---- one-step shadow checks along whole phasing schedules -------------------------------------------------------------------
+SW_BAND = 1e-9          # shrink-wrap: a mask point may differ where the convolved value lies within SW_BAND * (max - min) of the threshold
+POLAR_CUT = 1e-8        # singular directions of A_l with sigma_i / sigma_max above this are compared at TOL_SHT
+EPS = np.finfo(float).eps / 2
+RP_CORR_MAX = 3e-6      # k_projr.hip: largest column-pair |cos| the closing polar step accepts
+
+
+def _schedule_length(opt):
+    loops = opt['main_loop']['sub_loops']
+    n = 0
+    for name in loops['order']:
+        lo = loops[name]
+        per = sum(mo.get('iterations', 0) if isinstance(mo, dict) else 0
+                  for key, mo in ((k, lo['methods'][k]) for k in lo['order']) if key not in ('SW', 'SW_center'))
+        n += per * int(lo['iterations'])
+    return n
+
+
+def _coefficients_of(om, rho):
+    """I_lm of |FT rho|^2, the oracle's transforms, as one (N, nlm) array"""
+    return np.concatenate(om.sht.forward_l(OP.square_grid(om.fp.ft(rho))), axis=1)
+
+
+def wellposed_projection(om, e, Ilm, Ilm_warm=None):
+    """The real-arithmetic projection of one restart's coefficients, compared where it is well posed.
+
+    Per used order l > 0: A_l = V_l^H D^2 I_l (D = diag q), its SVD A_l = W S Z^H, the oracle's polar factor U_l = W Z^H.  Near a
+    fixed point of the loop I_l ~ V_l U_l, so A_l ~ V_l^H D^2 V_l U_l and the condition of V_l enters squared: sigma_min / sigma_max
+    of A_l reaches 1e-24 in a converged ER state.  The polar factor is then not unique to working precision in the directions of
+    small sigma: a rounding error dA ~ c eps sigma_max of A_l (c = N, the length of the inner products that form it) turns U_l by
+    up to min(2, c eps sigma_max / sigma_i) in direction w_i, and V_l U_l by that times a_i = |V_l w_i|.  So the per-order rel-L2 of
+    the projected coefficients is bounded by
+
+        allowance_l = sqrt(sum_i (a_i min(2, c eps sigma_max / sigma_i))^2) / |V_l|_F,     (at least TOL_SHT)
+
+    computed from the oracle's SVD at that state.  Its largest possible value, near sigma_i / sigma_max = c eps, is ~sqrt(c eps)
+    per direction: the kernel and LAPACK pick different members of a near-degenerate family, and neither is wrong.  What does not
+    depend on that choice is checked tightly:
+      * the Procrustes objective |D (V_l U_l - I_l)|_F of the device's U_l equals the oracle's to 1e-12 |D I_l|_F (U_l minimises
+        it: a change of U_l in an ill-posed direction changes it in second order only);
+      * the device's U_l is a partial isometry: every eigenvalue of U_l U_l^H is within (k - 1) RP_CORR_MAX^2 of 1 or of 0 (the
+        kernel stops when no column pair's |cos| exceeds RP_CORR_MAX = 3e-6 before its closing step, which leaves ~RP_CORR_MAX^2
+        per pair -- JL_EARLY^2 = 1e-12 on the classic path; Gershgorin over k rows; measured 1.3e-12 at k = 23), and its rank
+        covers every direction with sigma_i / sigma_max > 1e-13.  Its rows are orthonormal only where A_l has numerical range: k_rproj
+        deflates the columns of X_l below JAC_DEFLATE = 1e-15 of the largest (k_jacobi.h) and leaves U_l zero there, where LAPACK
+        completes U_l with an arbitrary unitary rest.  Both choices lie in the family above (the missing part weighs a_i <= the
+        allowance), and what B_l of the projection loses there is a_i^2 |V_l|^2 ~ 1e-17 of it;
+      * V_l U_l restricted to the directions with sigma_i / sigma_max > POLAR_CUT, where the bound above is below 1e-12 relative,
+        equals the oracle's at TOL_SHT.
+    Ilm_warm: projected once before (the kernel's next call warm-starts from that state's rotations).  Returns per-order rows
+    (l, sigma_min / sigma_max, rel-L2 of the order, allowance, objective deviation, partial-isometry deviation, restricted rel-L2,
+    rank of U_l, directions with sigma_i / sigma_max > 1e-13)."""
+    if Ilm_warm is not None:
+        e.project_coefficients(Ilm_warm[None], real_intensity=True)
+    proj = e.project_coefficients(Ilm[None], real_intensity=True)[0]
+    U_dev = e.unknowns(0)
+    rp = om.rp
+    D2 = np.asarray(rp.radial_points) ** 2
+    Dq = np.sqrt(D2)[:, None]
+    Il = [Ilm[:, l * l:(l + 1) ** 2] for l in range(int(round(np.sqrt(Ilm.shape[1]))))]
+    unk = rp.approximate_unknowns(Il)
+    ref = rp.mtip_projection(Il, unk)
+    rows = []
+    c = len(D2)
+    for i, l in enumerate(rp.used_orders.values()):
+        V = rp.projection_matrices[l]
+        if l == 0 or np.abs(V).max() == 0:
+            continue
+        m = rp.radial_mask[l]
+        A = V.conj().T @ (D2[:, None] * Il[l])
+        W, s, Zh = np.linalg.svd(A, full_matrices=False)
+        U_o, U_d = unk[i], U_dev[l]
+        ratio = s[-1] / s[0] if s[0] > 0 else 0.0
+        a = np.linalg.norm(V @ W, axis=0)
+        turn = np.minimum(2.0, c * EPS * s[0] / np.maximum(s, 1e-300))
+        allowance = max(TOL_SHT, np.sqrt(((a * turn) ** 2).sum()) / np.linalg.norm(V))
+        got = proj[:, l * l:(l + 1) ** 2]
+        order_err = rel_l2(got, ref[l])
+        nI = np.linalg.norm(Dq * Il[l])
+        obj = abs(np.linalg.norm(Dq * (V @ U_d - Il[l])) - np.linalg.norm(Dq * (V @ U_o - Il[l]))) / nI
+        lam = np.linalg.eigvalsh(U_d @ U_d.conj().T)
+        ortho = float(np.max(np.minimum(np.abs(lam), np.abs(lam - 1))))
+        rank, needed = int((lam > 0.5).sum()), int((s > 1e-13 * s[0]).sum())
+        keep = s > POLAR_CUT * s[0]
+        Pw = V @ W[:, keep] @ W[:, keep].conj().T
+        restricted = rel_l2((Pw @ U_d)[m], (Pw @ U_o)[m])
+        rows.append((l, ratio, order_err, allowance, obj, ortho, restricted, rank, needed))
+    return rows
+
+
+def check_wellposed_rows(rows, where=''):
+    for l, ratio, order_err, allowance, obj, ortho, restricted, rank, needed in rows:
+        assert obj <= 1e-12, (where, l, ratio, obj)
+        assert ortho <= (2 * l) * RP_CORR_MAX ** 2 and rank >= needed, (where, l, ratio, ortho, rank, needed)
+        assert restricted <= TOL_SHT, (where, l, ratio, restricted)
+        assert order_err <= allowance, (where, l, ratio, order_err, allowance)
+
+
+class _Shadow:
+    """Wraps one engine's `run`, `shrinkwrap`, `begin_sub_loop` and `select_best` (on the instance): sampled steps are split off
+    into calls of their own and compared with one oracle step from the device's state just before them."""
+
+    def __init__(self, e, om, every, total, keep_states):
+        self.e, self.om, self.every, self.total = e, om, every, total
+        self.n = 0
+        self.enforce = np.ones(e.B, bool)
+        self.forced = {0}
+        self.after_reselect = set()
+        self.steps, self.sws, self.states = [], [], []
+        self.keep_states = keep_states
+        self.signal = None
+        self.orig = {k: getattr(e, k) for k in ('run', 'shrinkwrap', 'begin_sub_loop', 'select_best')}
+        e.run, e.shrinkwrap, e.begin_sub_loop, e.select_best = self.run, self.shrinkwrap, self.begin_sub_loop, self.select_best
+
+    def sampled(self, g):
+        return g % self.every == self.every - 1 or g in self.forced or g == self.total - 1
+
+    def begin_sub_loop(self):
+        self.orig['begin_sub_loop']()
+        self.forced.add(self.n)
+
+    def select_best(self, where=None):
+        self.orig['select_best'](where)
+        self.forced.add(self.n)
+        self.after_reselect.add(self.n)
+
+    def run(self, method, ft_stab, betas, fetch=True):
+        betas = np.atleast_1d(np.asarray(betas, dtype=float))
+        first, i = self.n, 0
+        for k in range(len(betas)):
+            if self.sampled(first + k):
+                if k > i:
+                    self.orig['run'](method, ft_stab, betas[i:k], fetch=False)
+                    self.n += k - i
+                self._shadow_step(method, ft_stab, float(betas[k]))
+                i = k + 1
+        if len(betas) > i:
+            self.orig['run'](method, ft_stab, betas[i:], fetch=False)
+            self.n += len(betas) - i
+        return self.e.fetch_errors(first, len(betas)) if fetch else (None, None)
+
+    def _shadow_step(self, method, ft_stab, beta):
+        e, om = self.e, self.om
+        B = e.B
+        rho0 = [e.density(b) for b in range(B)]
+        sup = [e.support(b) for b in range(B)]
+        self.orig['run'](method, ft_stab, [beta], fetch=False)
+        g = self.n
+        self.n += 1
+        rho1 = [e.density(b) for b in range(B)]
+        F1 = [e.reciprocal_density(b) for b in range(B)]
+        err, deg2 = e.fetch_errors(g, 1)
+        main = e.fetch_main_errors(g, 1)[0]
+        flags = np.broadcast_to(np.asarray(ft_stab, dtype=bool), (B,))
+        phase = 'after reselection' if g in self.after_reselect else method
+        for b in range(B):
+            om.beta = beta
+            om.real_pr.enforce_initial_support = bool(self.enforce[b])
+            om.real_pr.support = sup[b]
+            om.errors = {'real': {n: [] for n in om.real_metrics}, 'reciprocal': {n: [] for n in om.reciprocal_metrics}, 'main': []}
+            F_o, rho_o = om.step(method, np.array(rho0[b]), bool(flags[b]))
+            rec = {'step': g, 'b': b, 'phase': phase, 'rho': rel_l2(rho1[b], rho_o), 'F': rel_l2(F1[b], F_o),
+                   'err': abs(err[0, b] - om.errors['real']['l2_projection_diff'][-1]),
+                   'main': abs(main[b] - om.main_error())}
+            if deg2 is not None and 'deg2_invariant_l2_diff' in om.errors['reciprocal']:
+                ref = np.asarray(om.errors['reciprocal']['deg2_invariant_l2_diff'][-1])
+                dev = deg2[0, b][np.array(tuple(om.rp.used_orders.values()))]
+                sig = self.signal if self.signal is not None else np.ones(len(ref), bool)
+                rec['deg2'] = float(np.max(np.abs(dev[sig] / ref[sig] - 1)))
+            self.steps.append(rec)
+            if b == 0 and self.keep_states and method.startswith('ER'):
+                self.states.append((g, phase, _coefficients_of(om, rho0[b]), _coefficients_of(om, rho1[b]), rho0[b], rho1[b]))
+
+    def shrinkwrap(self, sigma, threshold, error_limit):
+        e, om = self.e, self.om
+        B = e.B
+        rho = [e.density(b) for b in range(B)]
+        last = e.fetch_main_errors(self.n - 1, 1)[0] if self.n > 0 else np.full(B, -1.0)
+        enforced = self.orig['shrinkwrap'](sigma, threshold, error_limit)
+        init = np.asarray(e.initial_support, bool)
+        om.sw.gaussian_sigma = sigma
+        om.sw.threshold = threshold
+        for b in range(B):
+            sup = e.support(b)
+            cv = om.fp.ift(om.sw.multiply_with_ft_gaussian(om.fp.ft(OP.abs_value(np.array(rho[b]))))).real
+            cv[cv < 0] = 0
+            lo, hi = cv.min(), cv.max()
+            thr = lo + om.sw.threshold * (hi - lo)
+            mask = cv >= thr
+            want = mask & init if enforced[b] else mask
+            flips = sup != want
+            band = np.abs(cv - thr) <= SW_BAND * (hi - lo)
+            self.sws.append({'step': self.n, 'b': b, 'flips': int(flips.sum()), 'flips_outside_band': int((flips & ~band).sum()),
+                             'in_band': int(band.sum()), 'enforce_ok': bool(enforced[b]) == bool(last[b] > error_limit)})
+        self.enforce = np.array(enforced, bool)
+        self.forced.add(self.n)
+        return enforced
+
+
+PHASES = ('HIO', 'ER', 'after SW', 'after reselection')
+
+
+def _phase_maxima(shadows):
+    out = {}
+    for sh in shadows:
+        sw_steps = {s['step'] for s in sh.sws}
+        for r in sh.steps:
+            keys = [r['phase']] + (['after SW'] if r['step'] in sw_steps else [])
+            for k in keys:
+                d = out.setdefault(k, {})
+                for q in ('rho', 'F', 'err', 'main', 'deg2'):
+                    if q in r:
+                        d[q] = max(d.get(q, 0.0), r[q])
+                d['n'] = d.get('n', 0) + 1
+    return out
+
+
+def check_shadowed_schedule(opt, data, lib_path=None, fused=True, every=10, initial_densities=None, seeds=None, n_restarts=1,
+                            n_engines=1, label='', wellposed=True, check_split=True):
+    """One-step shadow checks along a whole schedule.  HIO is chaotic: after ~20 steps two runs that differ in the last bit are
+    different samples, so a long device trajectory cannot be compared with a long oracle trajectory.  One step can: the step is a
+    pure function of (density, support, enforce flag, beta, method, ft_stab), and oracle.mtip.MTIP.step is that function.
+
+    The product's loop runs unchanged (reconstruct.MTIP, or ProjectWorker with `n_engines` engine groups stepping through
+    mtip_run_group_async); each engine's `run` / `shrinkwrap` / `begin_sub_loop` / `select_best` are wrapped on the instance
+    (_Shadow).  Sampled: every `every`-th step, the first step of every sub-loop, the step after every shrink-wrap and after every
+    best-density reselection, and the last step.  A sampled step is split off into a call of its own; before it the device's
+    density, support and the enforce / ft_stab flag / beta the loop passes are taken per restart, after it the new density, the
+    new reciprocal density and the step's error values are compared with one oracle step from that snapshot:
+      * rho_new and F_new: rel-L2 <= TOL_STEP in every phase; the real l2_projection_diff and the main error within TOL_STEP
+        absolute (the metric is itself a ratio of norms |w - P w| / |w|: a rel-L2 deviation d of the step's w moves it by at most
+        ~2 d, however small the metric is near convergence -- where a relative tolerance would grow as 1 / metric), the deg2
+        metric (where enabled, orders with signal) to 1e-7 relative, the tolerance of the golden single steps (check_steps_golden);
+      * shrink-wrap: the device's mask against MTIP.sw_step of the same density (and the enforce decision against the last main
+        error); a point may differ only where the oracle's convolved value is within SW_BAND * (max - min) of the threshold.
+    ER floor: one step from a converged ER state agrees to ~1e-10 in F, not 1e-15 as in HIO.  That is conditioning, not kernel
+    error: see wellposed_projection, which is applied to the restart-0 state of every sampled ER step (projection warm-started
+    from the state one step before, on an engine of its own) -- its tight checks hold, and the order-wise deviation stays within the
+    allowance derived there from sigma_min / sigma_max.  The whole step needs no allowance of its own: the ill-posed directions
+    carry weights a_i ~ sqrt(sigma_i / sigma_max) |V_l|, so they enter F_new far below TOL_STEP.
+
+    Splitting chunks must not change the trajectory: the run is repeated unwrapped with the same initial densities, and the main
+    error histories must be equal bit for bit (the device's steps read only the state a step leaves, whether or not the host
+    splits the enqueue).  Returns (per-phase maxima, shadows, wellposed rows)."""
+    import threading
+    total = _schedule_length(opt)
+    N = int(opt['grid']['n_radial_points'])
+    sig = None
+    if 'deg2_invariant_l2_diff' in opt['main_loop']['error']['methods']['reciprocal'].get('calculate', []):
+        pm = data['data_projection_matrices']
+        used = list(OM.MTIP(opt, data).rp.used_orders.values())
+        norms = np.array([np.linalg.norm(np.asarray(pm[l])) if l < len(pm) else 0.0 for l in used])
+        sig = norms > 1e-9 * norms.max()
+    shadows = []
+    lock = threading.Lock()
+
+    def attach(m):
+        sh = _Shadow(m.engine, OM.MTIP(opt, data), every, total, wellposed)
+        sh.signal = sig
+        with lock:
+            shadows.append(sh)
+
+    def run_once(shadowed):
+        if n_engines == 1:
+            R.MTIP.preinit(opt, data)
+            m = R.MTIP(n_restarts=n_restarts, initial_densities=initial_densities, seeds=seeds, lib_path=lib_path, fused=fused)
+            m.generate_phasing_loop()
+            if shadowed:
+                attach(m)
+            res = m.phasing_loop()
+            m.engine.close()
+            return list(res)
+        o = OM.deep_update(opt, {'multi_process': {'use': True, 'n_parallel_reconstructions': n_restarts},
+                                 'GPU': {'use': True, 'n_gpu_workers': n_engines}})
+        orig_gen = R.MTIP.generate_phasing_loop
+
+        def gen(self):                     # the engine exists once this returns: wrap it before the loop starts
+            orig_gen(self)
+            if shadowed:
+                attach(self)
+        R.MTIP.generate_phasing_loop = gen
+        try:
+            w = R.ProjectWorker(o, data, seeds=seeds, lib_path=lib_path)
+            res, _ = w.run()
+        finally:
+            R.MTIP.generate_phasing_loop = orig_gen
+        assert len(w.mtip_instances) == n_engines
+        tc = w.results['stats']['turn_calls']
+        assert tc is not None and tc['group'] >= 2, tc
+        for m in w.mtip_instances:
+            m.engine.close()
+        return list(res)
+
+    res = run_once(True)
+    maxima = _phase_maxima(shadows)
+    rows = []
+    if wellposed:
+        e = Engine(opt, data, n_batch=1, lib_path=lib_path, fused=fused)
+        for sh in shadows:
+            for g, phase, I0, I1, _, _ in sh.states:
+                rows += [(g, phase) + r for r in wellposed_projection(sh.om, e, I1, I0)]
+        e.close()
+    sws = [s for sh in shadows for s in sh.sws]
+    print(f'\nshadow {label}: {sum(len(sh.steps) for sh in shadows)} oracle steps over {total} steps x {n_restarts} restarts, '
+          f'{len(sws)} shrink-wraps')
+    for k in PHASES:
+        if k in maxima:
+            d = maxima[k]
+            print(f'  {k:18s} n={d["n"]:4d}  rho {d["rho"]:.2e}  F {d["F"]:.2e}  err {d["err"]:.2e}  main {d["main"]:.2e}'
+                  + (f'  deg2 {d["deg2"]:.2e}' if 'deg2' in d else ''))
+    if sws:
+        print(f'  {"SW":18s} n={len(sws):4d}  flips {sum(s["flips"] for s in sws)} (outside the band '
+              f'{sum(s["flips_outside_band"] for s in sws)}, points in the band {sum(s["in_band"] for s in sws)})')
+    if rows:
+        a = np.array([r[2:] for r in rows], dtype=float)
+        print(f'  {"ER projection":18s} n={len(rows):4d}  min sigma ratio {a[:, 1].min():.1e}  order rel-L2 {a[:, 2].max():.2e} '
+              f'(max / allowance {np.max(a[:, 2] / a[:, 3]):.2f})  objective {a[:, 4].max():.1e}  isometry {a[:, 5].max():.1e}  '
+              f'restricted {a[:, 6].max():.1e}  rank deficit of U_l up to {int(np.max(a[:, 8] * 0 + (2 * a[:, 0] + 1) - a[:, 7]))}')
+    for r in (r for sh in shadows for r in sh.steps):
+        assert r['rho'] < TOL_STEP and r['F'] < TOL_STEP, r
+        assert r['err'] < TOL_STEP and r['main'] < TOL_STEP, r
+        assert r.get('deg2', 0.0) < 1e-7, r
+    for s in sws:
+        assert s['flips_outside_band'] == 0 and s['enforce_ok'], s
+    assert sum(s['flips'] for s in sws) <= sum(s['in_band'] for s in sws)
+    for r in rows:
+        check_wellposed_rows([r[2:]], where=r[:2])
+    sampled = {r['step'] for sh in shadows for r in sh.steps}
+    assert total - 1 in sampled and 0 in sampled
+    assert all(s['step'] in sampled for s in sws if s['step'] < total)
+    if check_split:
+        plain = run_once(False)
+        for a, b in zip(res, plain):
+            assert np.array_equal(a['error_dict']['main'], b['error_dict']['main'])
+            assert np.array_equal(a['last_real_density'], b['last_real_density'])
+    return maxima, shadows, rows
+
+
+def shadow_golden_schedule(g, n_hio=60, n_er=40, n_main=2, n_refine=40):
+    """16 x L4 golden problem, the tutorial schedule's shape with shortened counts: n_main x (HIO, SW, ER) then (SW, ER); the
+    main loop reselects its best density at its end (best iteration > 1), the B_l metric is recorded"""
+    N, L = int(g['N']), int(g['L'])
+    opt = golden_settings(N, L, {'main_loop': {'error': {'methods': {'reciprocal': {
+        'calculate': ['deg2_invariant_l2_diff'], 'deg2_invariant_l2_diff': {'order': 2}}}}}})
+    loops = opt['main_loop']['sub_loops']
+    loops['order'] = ['main', 'refinement']
+    loops['main'].update({'order': ['HIO', 'SW', 'ER'], 'iterations': n_main, 'best_density_not_in_first_n_iterations': 1})
+    loops['main']['methods']['HIO']['iterations'] = n_hio
+    loops['main']['methods']['ER']['iterations'] = n_er
+    loops['refinement'].update({'order': ['SW', 'ER'], 'iterations': 1})
+    loops['refinement']['methods']['ER']['iterations'] = n_refine
+    return opt, data_from_golden(g, L)
+
+
+def shadow_config_schedule(cfg, data=None, lib_path=None, hio_sw_er=None):
+    """settings of a BASELINE config (synthetic invariants made with the device transforms); hio_sw_er = (n_hio, n_er): one
+    HIO, SW, ER iteration instead of the config's own schedule"""
+    if data is None:
+        data, _ = synthetic_problem(cfg, lib_path)
+    opt = OM.deep_update(OM.default_settings(), S.config_overrides(cfg))
+    if hio_sw_er is not None:
+        loops = opt['main_loop']['sub_loops']
+        loops['order'] = ['main']
+        loops['main']['order'] = ['HIO', 'SW', 'ER']
+        loops['main']['methods'].update({'HIO': {'iterations': hio_sw_er[0], 'ft_stab': True}, 'SW': 1,
+                                         'ER': {'iterations': hio_sw_er[1], 'ft_stab': True}})
+        loops['main']['iterations'] = 1
+    return opt, data
+
+
+def converged_er_fixture():
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'converged_er_N16_L4.npz'))
+
+
+def check_projection_converged_er_state(g, lib_path=None, fused=True):
+    """The projection of a converged ER state (tests/golden/converged_er_N16_L4.npz: densities the shadow harness saved one step
+    apart at the last step of the 16 x L4 schedule, sigma_min / sigma_max of A_4 ~ 1e-27) through the well-posed comparisons of
+    wellposed_projection, cold and warm-started from the state one step before; the plain rel-L2 of the whole array is not a
+    well-posed test here"""
+    f = converged_er_fixture()
+    opt, data = shadow_golden_schedule(g)
+    om = OM.MTIP(opt, data)
+    I0, I1 = _coefficients_of(om, f['rho_prev']), _coefficients_of(om, f['rho'])
+    e = Engine(opt, data, n_batch=1, lib_path=lib_path, fused=fused)
+    cold = wellposed_projection(om, e, I1)
+    warm = wellposed_projection(om, e, I1, I0)
+    e.close()
+    assert min(r[1] for r in cold) < 1e-20, 'the fixture is not a rank-deficient state'
+    check_wellposed_rows(cold, 'cold')
+    check_wellposed_rows(warm, 'warm')
+    return cold, warm

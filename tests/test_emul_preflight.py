@@ -322,3 +322,19 @@ def test_wide_projection_matrices(emul_lib):
 
 def test_extract_rules_golden(emul_lib):
     PC.check_extract_rules_hip(emul_lib)
+
+
+@pytest.mark.parametrize('fused', [True, False])
+def test_shadowed_schedule(emul_lib, golden_mtip16, fused):
+    """one-step shadow checks along a whole schedule (PC.check_shadowed_schedule): 16 x L4, 2 x (60 HIO, SW, 40 ER) with the best
+    density reselected at the end of the main loop, then SW, 40 ER; 2 restarts, every 5th step plus the boundary steps sampled.
+    About 2.5 minutes per step order (the repeated unsplit run included)."""
+    opt, data = PC.shadow_golden_schedule(golden_mtip16)
+    maxima, _, rows = PC.check_shadowed_schedule(opt, data, emul_lib, fused=fused, every=5, n_restarts=2,
+                                                 initial_densities=[golden_mtip16['rho0']] * 2, label=f'16 x L4 fused={fused}')
+    assert {'HIO', 'ER', 'after SW', 'after reselection'} <= set(maxima)
+    assert min(r[3] for r in rows) < 1e-20                 # the ER states reached are rank deficient (A_4)
+
+
+def test_projection_converged_er_state(emul_lib, golden_mtip16):
+    PC.check_projection_converged_er_state(golden_mtip16, emul_lib)

@@ -361,3 +361,59 @@ def test_switch_projection_vs_oracle(env, monkeypatch):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     PC.check_projection_vs_oracle(40, 18)
+
+
+
+# ---- one-step shadow checks along whole schedules (PC.check_shadowed_schedule) -------------------------------------------
+# Budgets: the oracle step costs ~0.2 s per restart at 128 x L32, ~0.03 s at 64 x L16, a few seconds at 256 x L48.
+@pytest.mark.parametrize('fused', [True, False])
+def test_shadowed_tutorial_schedule_benchmark_problem(fused):
+    """(a) the benchmark's problem (config 4 settings, 128 x L32): the full 600-step tutorial schedule 5 x (60 HIO, SW, 40 ER) +
+    (SW, 100 ER), 3 restarts, every 10th step plus the boundary steps shadowed, the well-posed projection checks on restart 0's
+    sampled ER states.  Budget: 4 minutes per step order."""
+    import time
+    t0 = time.perf_counter()
+    opt, data = PC.shadow_config_schedule(4)
+    PC.check_shadowed_schedule(opt, data, fused=fused, every=10, seeds=[4000, 4001, 4002], n_restarts=3,
+                               label=f'config 4 fused={fused}')
+    assert time.perf_counter() - t0 < 240
+
+
+def test_shadowed_tutorial_schedule_three_engines():
+    """(b) the same schedule through ProjectWorker with three engine groups on one GPU (6 restarts, two per engine): the steps
+    are enqueued by mtip_run_group_async with its turn lag, every 20th step plus the boundary steps shadowed.  Budget: 4 minutes."""
+    import time
+    t0 = time.perf_counter()
+    opt, data = PC.shadow_config_schedule(4)
+    PC.check_shadowed_schedule(opt, data, every=20, seeds=[4100 + i for i in range(6)], n_restarts=6, n_engines=3,
+                               label='config 4, three engines', wellposed=False)
+    assert time.perf_counter() - t0 < 240
+
+
+@pytest.mark.parametrize('tier', ['0', '1', '2', '3', '4'])
+def test_shadowed_schedule_sht_tiers(tier, monkeypatch):
+    """(c) every MTIP_SHT_TIER cap below the default chained kernel at 64 x L16 (config 2: 2 x (60 HIO, 40 ER)): each step of the
+    run against the oracle at 1e-9, every 20th step plus the boundary steps, 2 restarts -- chained against non-chained kernels
+    over the whole run, not 20 steps.  Budget: 1 minute per tier."""
+    import time
+    monkeypatch.setenv('MTIP_SHT_TIER', tier)
+    t0 = time.perf_counter()
+    opt, data = PC.shadow_config_schedule(2)
+    PC.check_shadowed_schedule(opt, data, every=20, seeds=[4200, 4201], n_restarts=2, label=f'config 2 tier {tier}',
+                               wellposed=False)
+    assert time.perf_counter() - t0 < 60
+
+
+def test_shadowed_schedule_config5():
+    """(d) config 5 geometry (256 x L48, 1 restart): 40 HIO, SW, 40 ER, every 10th step plus the boundary steps -- k_rproj's
+    768-thread tight layout (97 columns) inside a loop, with the well-posed projection checks on the sampled ER states.
+    Budget: 5 minutes."""
+    import time
+    t0 = time.perf_counter()
+    opt, data = PC.shadow_config_schedule(5, hio_sw_er=(40, 40))
+    PC.check_shadowed_schedule(opt, data, every=10, seeds=[4300], n_restarts=1, label='config 5')
+    assert time.perf_counter() - t0 < 300
+
+
+def test_projection_converged_er_state(golden_mtip16):
+    PC.check_projection_converged_er_state(golden_mtip16, None)
