@@ -330,6 +330,61 @@ int mtip2d_op_step_ex(mtip2d_ctx* ctx, int method, int ft_stab, double beta, con
 /* the SW sketch (reconstruct.py:598-605, fxs_Projections.py:245-258, 294-298): support mask (n_batch, Nq, n_phi) from rho */
 int mtip2d_op_shrinkwrap(mtip2d_ctx* ctx, const mtip_cdouble* rho, double sigma, double threshold, uint8_t* mask);
 
+/* ---- the resident 2-D loop (csrc/k_polar2d.hip, second half): the batch of restarts stays in HBM, a step is five fused kernels and
+ * nothing crosses the host inside mtip2d_run*.  The calls mirror the 3-D ones above; the operator-level calls keep working beside
+ * them (they share work grids on the context's stream, not the state).  A call in the wrong state returns MTIP_ESTATE with a
+ * message and enqueues nothing. */
+/* starting density of restart `batch` (Nq, n_phi) (reconstruct.py:957-966); mtip2d_init_state then starts the state from
+ * F0 = FT(rho0), rho0' = IFT(F0) (962-963), best error = inf, supports = the initial support, empty histories */
+int mtip2d_set_density(mtip2d_ctx* ctx, int batch, const mtip_cdouble* rho);
+/* initial support S0 (Nq, n_phi) bytes, shared by the batch (fxs_Projections.py:60-93); resets every restart's support to it */
+int mtip2d_set_initial_support(mtip2d_ctx* ctx, const uint8_t* support);
+/* effective support of one restart (the support setter's result, fxs_Projections.py:53-58) */
+int mtip2d_set_support(mtip2d_ctx* ctx, int batch, const uint8_t* support);
+int mtip2d_init_state(mtip2d_ctx* ctx);
+/* ft_stab per restart for the runs that follow with ft_stab = 1 (reconstruct.py:836-850: one decision per reconstruction
+ * process); NULL = every restart.  Read inside the step: the step is not run twice. */
+int mtip2d_set_ft_stab_mask(mtip2d_ctx* ctx, const uint8_t* mask);
+/* reciprocal metrics evaluated in every step: which = 1 deg2_invariant_l2_diff (2-D flavour, fxs_IO_methods.py:370-400;
+ * deg2_reference (n_used, Nq, Nq) with the number-of-particles rule already applied, deg2_norms (n_used): value -1 where 0) |
+ * 2 l2_projection_diff of (F, F') (301-310) with l2_weights (Nq, n_phi); 0 switches them off */
+int mtip2d_set_reciprocal_metrics(mtip2d_ctx* ctx, uint32_t which, const mtip_cdouble* deg2_reference, const double* deg2_norms,
+                                  const double* l2_weights);
+/* generate_main_error_routine (fxs_IO_methods.py:746-765): type 0 mean, 1 min, 2 max, 3 prod over the listed metrics, items[i] =
+ * 0 real l2_projection_diff, 1 deg2_invariant_l2_diff (one value per used order), 2 reciprocal l2_projection_diff; a scalar next
+ * to the per-order metric is refused (the reference raises, 758).  Default: the real metric alone. */
+int mtip2d_set_main_error(mtip2d_ctx* ctx, int type, int n_items, const int32_t* items);
+/* n_steps steps of method 0 HIO, 1 ER, 2 HIO_non_FXS, 3 ER_non_FXS (reconstruct.py:854-951) for every restart, betas[n_steps];
+ * errors, reciprocal metrics, main error and best tracking (934-938) stay on the device.  The *_non_FXS methods take |F| of the
+ * pair before the most recent step as their intensity, once per block of such runs (899-904: an FXS run or a new sub-loop drops it).
+ * mtip2d_run returns after real_err (n_steps x n_batch, may be NULL) is on the host; mtip2d_run_async only enqueues. */
+int mtip2d_run(mtip2d_ctx* ctx, int method, int ft_stab, int n_steps, const double* betas, double* real_err);
+int mtip2d_run_async(mtip2d_ctx* ctx, int method, int ft_stab, int n_steps, const double* betas);
+/* histories of the steps [first_step, first_step + n_steps): the real l2_projection_diff (fxs_IO_methods.py:97-128), the main
+ * error (746-765), the reciprocal metrics (deg2 (n_steps, n_batch, n_used) and / or l2 (n_steps, n_batch); NULL = not wanted) */
+int mtip2d_fetch_errors(mtip2d_ctx* ctx, int64_t first_step, int64_t n_steps, double* real_err);
+int mtip2d_fetch_main_errors(mtip2d_ctx* ctx, int64_t first_step, int64_t n_steps, double* main_err);
+int mtip2d_fetch_reciprocal_metrics(mtip2d_ctx* ctx, int64_t first_step, int64_t n_steps, double* deg2, double* l2);
+/* one shrink-wrap update of the resident density (reconstruct.py:598-605, 877-885; fxs_Projections.py:245-258, 294-298):
+ * enforce_b = last main error_b > error_limit, taken on the device (no step yet: not enforced); enforced[n_batch] or NULL */
+int mtip2d_shrinkwrap(mtip2d_ctx* ctx, double sigma, double threshold, double error_limit, uint8_t* enforced);
+/* 'SW_center' tail (reconstruct.py:606-613, 886-897), literally: the latest pair becomes (reciprocal, real) = (rho, FT(rho)) */
+int mtip2d_refresh_reciprocal_density(mtip2d_ctx* ctx);
+/* top of a sub-loop (reconstruct.py:852-866): the stale pair is re-read from the state, the *_non_FXS intensity forgotten */
+int mtip2d_begin_sub_loop(mtip2d_ctx* ctx);
+/* take the best pair and its support as the latest ones (reconstruct.py:945-949), for all restarts or those with select[b] != 0 */
+int mtip2d_select_best(mtip2d_ctx* ctx);
+int mtip2d_select_best_where(mtip2d_ctx* ctx, const uint8_t* select);
+/* which = 0 latest, 1 best (reconstruct.py:934-938); (Nq, n_phi) per restart */
+int mtip2d_get_density(mtip2d_ctx* ctx, int batch, int which, mtip_cdouble* rho);
+int mtip2d_get_reciprocal_density(mtip2d_ctx* ctx, int batch, int which, mtip_cdouble* F);
+int mtip2d_get_support(mtip2d_ctx* ctx, int batch, int which, uint8_t* support);
+/* unknowns (n_used) of the last FXS step (fxs_Projections.py:723-745) */
+int mtip2d_get_unknowns(mtip2d_ctx* ctx, int batch, mtip_cdouble* unknowns);
+/* best main error per restart (n_batch doubles, reconstruct.py:934-938) and the number of steps done; either may be NULL */
+int mtip2d_get_best_error(mtip2d_ctx* ctx, double* best_error, int64_t* n_steps_done);
+int mtip2d_synchronize(mtip2d_ctx* ctx);
+
 /* ---- timing ----------------------------------------------------------------------------------- */
 /* average duration (ms) and launch count of kernel family `name` ("sht_fwd", "sht_inv", "hankel",
  * "proj", "real_update", ...) measured with hipEvents on the ctx stream since the last reset;

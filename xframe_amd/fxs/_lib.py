@@ -109,6 +109,29 @@ _SIGNATURES = {
     'mtip2d_op_step': (C.c_int, [c_void, C.c_int, C.c_int, C.c_double, c_void, c_void, c_void, c_void, c_void, c_void]),
     'mtip2d_op_step_ex': (C.c_int, [c_void, C.c_int, C.c_int, C.c_double, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     'mtip2d_op_shrinkwrap': (C.c_int, [c_void, c_void, C.c_double, C.c_double, c_void]),
+    'mtip2d_set_density': (C.c_int, [c_void, C.c_int, c_void]),
+    'mtip2d_set_initial_support': (C.c_int, [c_void, c_void]),
+    'mtip2d_set_support': (C.c_int, [c_void, C.c_int, c_void]),
+    'mtip2d_init_state': (C.c_int, [c_void]),
+    'mtip2d_set_ft_stab_mask': (C.c_int, [c_void, c_void]),
+    'mtip2d_set_reciprocal_metrics': (C.c_int, [c_void, C.c_uint32, c_void, c_void, c_void]),
+    'mtip2d_set_main_error': (C.c_int, [c_void, C.c_int, C.c_int, c_void]),
+    'mtip2d_run': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void, c_void]),
+    'mtip2d_run_async': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void]),
+    'mtip2d_fetch_errors': (C.c_int, [c_void, C.c_int64, C.c_int64, c_void]),
+    'mtip2d_fetch_main_errors': (C.c_int, [c_void, C.c_int64, C.c_int64, c_void]),
+    'mtip2d_fetch_reciprocal_metrics': (C.c_int, [c_void, C.c_int64, C.c_int64, c_void, c_void]),
+    'mtip2d_shrinkwrap': (C.c_int, [c_void, C.c_double, C.c_double, C.c_double, c_void]),
+    'mtip2d_refresh_reciprocal_density': (C.c_int, [c_void]),
+    'mtip2d_begin_sub_loop': (C.c_int, [c_void]),
+    'mtip2d_select_best': (C.c_int, [c_void]),
+    'mtip2d_select_best_where': (C.c_int, [c_void, c_void]),
+    'mtip2d_get_density': (C.c_int, [c_void, C.c_int, C.c_int, c_void]),
+    'mtip2d_get_reciprocal_density': (C.c_int, [c_void, C.c_int, C.c_int, c_void]),
+    'mtip2d_get_support': (C.c_int, [c_void, C.c_int, C.c_int, c_void]),
+    'mtip2d_get_unknowns': (C.c_int, [c_void, C.c_int, c_void]),
+    'mtip2d_get_best_error': (C.c_int, [c_void, c_void, C.POINTER(C.c_int64)]),
+    'mtip2d_synchronize': (C.c_int, [c_void]),
     'mtip_op_so3_find_rotation': (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
     'mtip_op_rotate_coefficients_grid': (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_hermitian_eig': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),

@@ -4,7 +4,8 @@
 (``ft_grid_pairs.py:282-291, 325-336``) and the 2-D reciprocal projection (``fxs_Projections.py:723-745, 803-826, 855-863``),
 through the ``mtip2d_*`` entry points of ``include/mtip_hip.h`` (``csrc/k_polar2d.hip``); the radial rules besides midpoint (trapz,
 gauss, Zernike: ``hankel_transforms.py:133-176, 335-375, 492-535``) are host weight tables for the same device contraction.  The 2-D
-phasing loop on these operators is ``reconstruct2d.py``; no CPU fallback."""
+phasing loop on these operators is ``reconstruct2d.py``; ``Engine2D`` also carries the resident loop (``set_density`` ... ``run``, the 3-D
+engine's names on ``mtip2d_run`` and friends: the state of a batch of restarts stays in HBM between the steps); no CPU fallback."""
 import ctypes as C
 
 import numpy as np
@@ -227,3 +228,152 @@ class Engine2D:
         mask = np.empty((self.B,) + self.shape, np.uint8)
         self._ck(self.lib.mtip2d_op_shrinkwrap(self.ctx, _lib.ptr(r), float(sigma), float(threshold), _lib.ptr(mask)))
         return mask.astype(bool)
+
+    # ---- the resident loop (mtip2d_set_density ... mtip2d_run, csrc/k_polar2d.hip): the names of the 3-D engine
+    METHOD_ID = {'HIO': 0, 'ER': 1, 'HIO_non_FXS': 2, 'ER_non_FXS': 3}
+    MAIN_TYPE = {'mean': 0, 'min': 1, 'max': 2, 'prod': 3}
+    MAIN_ITEM = {'real': 0, 'deg2_invariant_l2_diff': 1, 'l2_projection_diff': 2}
+
+    def set_density(self, batch, rho):
+        r = _lib.as_c128(rho)
+        assert r.shape == self.shape
+        self._ck(self.lib.mtip2d_set_density(self.ctx, int(batch), _lib.ptr(r)))
+
+    def set_initial_support(self, support):
+        s = _lib.as_u8(np.asarray(support, dtype=bool))
+        assert s.shape == self.shape
+        self._ck(self.lib.mtip2d_set_initial_support(self.ctx, _lib.ptr(s)))
+
+    def set_support(self, batch, support):
+        s = _lib.as_u8(np.asarray(support, dtype=bool))
+        assert s.shape == self.shape
+        self._ck(self.lib.mtip2d_set_support(self.ctx, int(batch), _lib.ptr(s)))
+
+    def init_state(self):
+        """the state starts from IFT(FT(guess)) of the densities given to `set_density` (reconstruct.py:962-963)"""
+        self._ck(self.lib.mtip2d_init_state(self.ctx))
+        self.n_steps = 0
+
+    def set_ft_stab_mask(self, mask):
+        """ft_stab per restart for the runs that follow (bool per restart), None = every restart"""
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask, dtype=bool).astype(np.uint8))
+        assert m is None or m.shape == (self.B,)
+        self._ck(self.lib.mtip2d_set_ft_stab_mask(self.ctx, _lib.ptr(m)))
+        self._ft_mask_set = m is not None
+
+    def set_reciprocal_metrics(self, deg2_reference=None, deg2_norms=None, l2_weights=None):
+        """deg2_invariant_l2_diff with its reference table (n_used, Nq, Nq) and norms (n_used), and / or the reciprocal
+        l2_projection_diff with its weights (Nq, n_phi); nothing given: both off"""
+        which = (1 if deg2_reference is not None else 0) | (2 if l2_weights is not None else 0)
+        ref = None if deg2_reference is None else _lib.as_c128(deg2_reference)
+        nrm = None if deg2_reference is None else _lib.as_f64(deg2_norms)
+        w = None if l2_weights is None else _lib.as_f64(l2_weights)
+        assert ref is None or (ref.shape == (self.n_used, self.N, self.N) and nrm.shape == (self.n_used,))
+        assert w is None or w.shape == self.shape
+        self._ck(self.lib.mtip2d_set_reciprocal_metrics(self.ctx, which, _lib.ptr(ref), _lib.ptr(nrm), _lib.ptr(w)))
+        self.metrics = which
+
+    def set_main_error(self, kind, items):
+        """main error = kind ('mean', 'min', 'max', 'prod') over `items`: 'real', 'deg2_invariant_l2_diff', 'l2_projection_diff'"""
+        it = np.ascontiguousarray([self.MAIN_ITEM[i] for i in items], dtype=np.int32)
+        self._ck(self.lib.mtip2d_set_main_error(self.ctx, self.MAIN_TYPE[kind], len(it), _lib.ptr(it)))
+
+    def run(self, method, ft_stab, betas, fetch=True):
+        """n = len(betas) steps of `method` in one call; ft_stab: bool, or a bool per restart (read inside the step).  With fetch the
+        real errors (n, B) of these steps come back, else nothing crosses the host"""
+        betas = _lib.as_f64(np.atleast_1d(betas))
+        n = len(betas)
+        mixed = None
+        if isinstance(ft_stab, np.ndarray):
+            flags = np.asarray(ft_stab, dtype=bool).reshape(self.B)
+            if flags.all() or not flags.any():
+                ft_stab = bool(flags.all())
+            else:
+                mixed, ft_stab = flags, True
+        if mixed is not None:
+            self.set_ft_stab_mask(mixed)
+        elif getattr(self, '_ft_mask_set', False):
+            self.set_ft_stab_mask(None)
+        mid = self.METHOD_ID[method]
+        if not fetch:
+            self._ck(self.lib.mtip2d_run_async(self.ctx, mid, int(bool(ft_stab)), n, _lib.ptr(betas)))
+            self.n_steps += n
+            return None
+        err = np.empty((n, self.B))
+        self._ck(self.lib.mtip2d_run(self.ctx, mid, int(bool(ft_stab)), n, _lib.ptr(betas), _lib.ptr(err)))
+        self.n_steps += n
+        return err
+
+    def fetch_errors(self, first, n):
+        err = np.empty((n, self.B))
+        self._ck(self.lib.mtip2d_fetch_errors(self.ctx, first, n, _lib.ptr(err)))
+        return err
+
+    def fetch_main_errors(self, first, n):
+        err = np.empty((n, self.B))
+        self._ck(self.lib.mtip2d_fetch_main_errors(self.ctx, first, n, _lib.ptr(err)))
+        return err
+
+    def fetch_reciprocal_metrics(self, first, n):
+        """{name: (n, B, n_used) or (n, B)} of the enabled reciprocal metrics"""
+        which = getattr(self, 'metrics', 0)
+        deg2 = np.empty((n, self.B, self.n_used)) if which & 1 else None
+        l2 = np.empty((n, self.B)) if which & 2 else None
+        self._ck(self.lib.mtip2d_fetch_reciprocal_metrics(self.ctx, first, n, _lib.ptr(deg2), _lib.ptr(l2)))
+        out = {}
+        if deg2 is not None:
+            out['deg2_invariant_l2_diff'] = deg2
+        if l2 is not None:
+            out['l2_projection_diff'] = l2
+        return out
+
+    def shrinkwrap_state(self, sigma, threshold, error_limit):
+        """shrink-wrap of the resident density; the enforce decision (last main error > error_limit) per restart comes back"""
+        enforced = np.empty(self.B, np.uint8)
+        self._ck(self.lib.mtip2d_shrinkwrap(self.ctx, float(sigma), float(threshold), float(error_limit), _lib.ptr(enforced)))
+        return enforced.astype(bool)
+
+    def begin_sub_loop(self):
+        self._ck(self.lib.mtip2d_begin_sub_loop(self.ctx))
+
+    def refresh_reciprocal_density(self):
+        """'SW_center' tail (reconstruct.py:891-894), literally: the last pair becomes (reciprocal, real) = (rho, FT(rho))"""
+        self._ck(self.lib.mtip2d_refresh_reciprocal_density(self.ctx))
+
+    def select_best(self, where=None):
+        if where is None:
+            self._ck(self.lib.mtip2d_select_best(self.ctx))
+        else:
+            w = np.ascontiguousarray(np.asarray(where, dtype=bool).astype(np.uint8))
+            assert w.shape == (self.B,)
+            self._ck(self.lib.mtip2d_select_best_where(self.ctx, _lib.ptr(w)))
+
+    def _get(self, fn, best, dtype):
+        out = np.empty((self.B,) + self.shape, dtype)
+        for b in range(self.B):
+            self._ck(fn(self.ctx, b, int(bool(best)), _lib.ptr(out[b])))
+        return out
+
+    def density(self, best=False):
+        return self._get(self.lib.mtip2d_get_density, best, complex)
+
+    def reciprocal_density(self, best=False):
+        return self._get(self.lib.mtip2d_get_reciprocal_density, best, complex)
+
+    def support(self, best=False):
+        return self._get(self.lib.mtip2d_get_support, best, np.uint8).astype(bool)
+
+    def unknowns(self):
+        out = np.empty((self.B, self.n_used), complex)
+        for b in range(self.B):
+            self._ck(self.lib.mtip2d_get_unknowns(self.ctx, b, _lib.ptr(out[b])))
+        return out
+
+    def best_error(self):
+        err = np.empty(self.B)
+        n = C.c_int64(0)
+        self._ck(self.lib.mtip2d_get_best_error(self.ctx, _lib.ptr(err), C.byref(n)))
+        return err, int(n.value)
+
+    def synchronize(self):
+        self._ck(self.lib.mtip2d_synchronize(self.ctx))

@@ -75,10 +75,12 @@ class MTIP:
     def generate_phasing_loop(self):
         t_engine = time.perf_counter()
         if MTIP.dimensions == 2:
-            # the polar loop: host-orchestrated on the batched device operators (reconstruct2d.py)
+            # the polar loop (reconstruct2d.py): host-orchestrated on the batched device operators, or with GPU.resident_2d on the
+            # resident engine (mtip2d_run)
             from .reconstruct2d import MTIP2D
             self.loop2d = MTIP2D(self.opt, MTIP.mtip_data, n_restarts=self.n_restarts, initial_densities=self.initial_densities,
-                                 seeds=self.seeds, device=self.device, lib_path=self.lib_path)
+                                 seeds=self.seeds, device=self.device, lib_path=self.lib_path,
+                                 resident=bool(self.opt.get('GPU', {}).get('resident_2d', False)))     # opt-in: the resident 2-D engine
             self.engine = self.loop2d.engine
             self._engine_seconds = time.perf_counter() - t_engine
             self.rprojection = self.loop2d.rsetup

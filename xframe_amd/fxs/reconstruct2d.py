@@ -12,7 +12,11 @@ reference's own 2-D `MTIP` run) and, for the loop's sub-variants -- `SW_center`,
 -- and `SO_freedom` with the `fix_orientation` output modifier, by `tests/golden/mtip2d_variants_N12_M6.npz` (the reference's own
 2-D runs of each); the radial rules `trapz`, `gauss`, `Zernike` are host weight tables for the same device contraction (fixture G23 from
 the reference's own functions).  Not built for 2-D: the other reciprocal metrics; the `low_resolution_autocorrelation` guess raises upstream in 2-D (reconstruct.py:1186 iterates over
-`low_resolution_intensity_coefficients`, which is False for dimensions == 2) and raises here."""
+`low_resolution_intensity_coefficients`, which is False for dimensions == 2) and raises here.
+
+With `resident=True` (the worker's `GPU.resident_2d`, default off) the same sub-loops run on the resident engine instead
+(`Engine2D.run` = `mtip2d_run`: the batch stays in HBM, a step is five fused kernels, consecutive steps of one method are one call,
+errors / metrics / best tracking on the device): `_loop_resident`, after the 3-D host loop; the result dicts are the same."""
 import numpy as np
 
 from . import hostsetup as hs
@@ -123,7 +127,7 @@ class MTIP2D:
     """the 2-D loop for a batch of restarts; settings as for the 3-D worker (`dimensions: 2`), data = the 2-D invariants
     (`data_projection_matrices` (n_orders, Nq), `average_intensity`, `data_radial_points`)"""
 
-    def __init__(self, settings, data, n_restarts=1, initial_densities=None, seeds=None, device=0, lib_path=None):
+    def __init__(self, settings, data, n_restarts=1, initial_densities=None, seeds=None, device=0, lib_path=None, resident=False):
         opt = self.opt = resolve(settings)
         if opt.get('dimensions', 3) != 2:
             raise ValueError('MTIP2D is the dimensions == 2 loop')
@@ -177,6 +181,7 @@ class MTIP2D:
         self.default_sigma = np.pi / np.max(e.qs)                     # fxs_Projections.py:189-190
         self.initial_densities = initial_densities
         self.seeds = seeds
+        self.resident = bool(resident)                                # the loop on the resident engine (mtip2d_run): _loop_resident
 
     # -- density guess (reconstruct.py:1115-1174 with the PolarIntegrator, 1126-1127)
     def _initial_density(self, i):
@@ -344,6 +349,10 @@ class MTIP2D:
 
     def phasing_loop(self):
         """create_initial_state + the sub-loops + generate_output (reconstruct.py:957-1035) for the batch: list of result dicts"""
+        return self._generate_output(*(self._loop_resident() if self.resident else self._loop_operators()))
+
+    def _loop_operators(self):
+        """the sub-loops, one operator-level call per step (`Engine2D.step`), histories and best tracking on the host"""
         e, B, opt = self.engine, self.B, self.opt
         rho0 = np.stack([self._initial_density(b) for b in range(B)])
         F0 = e.fourier_transform(rho0)
@@ -443,7 +452,105 @@ class MTIP2D:
                 hist = hist[1:] + [(np.where(sel, best['pair'][0], hist[-1][0]), np.where(sel, best['pair'][1], hist[-1][1]))]
                 support = np.where(sel, best['mask'], support)
             iterations.append(iteration)
-        best_pair, last_pair = best['pair'], hist[-1]
+        return rho0, best['pair'], hist[-1], best['err'], best['mask'], support, err_real, err_main, err_recip, unknowns, iterations
+
+    def _loop_resident(self):
+        """the same sub-loops on the resident engine, after the 3-D host loop (reconstruct.py:216-269): consecutive steps of one
+        method are ONE `run`, errors, metrics and best tracking stay on the device; the host keeps what upstream decides on the host
+        (ramps, the ft_stab link from the enforce flags, iteration counts)"""
+        e, B, opt = self.engine, self.B, self.opt
+        for b in range(B):
+            e.set_density(b, self._initial_density(b))
+        e.set_initial_support(self.initial_support)
+        ref = norms = w_l2 = None
+        if 'deg2_invariant_l2_diff' in self.reciprocal_metrics:
+            ref = self._deg2_ref.copy()                               # as _reciprocal_errors builds it
+            zero_id = self.rsetup.used_orders[0]
+            ref[zero_id] = self._deg2_ref[zero_id] / self.rsetup.number_of_particles
+            norms = self._deg2_norm
+        if 'l2_projection_diff' in self.reciprocal_metrics:
+            w_l2 = polar_integrator_weights(e.rs, e.phis)
+            w_l2[self.N - 2, :] = 0.0
+        e.set_reciprocal_metrics(ref, norms, w_l2)
+        items = ['real'] * len(self.main_real) + list(self.main_reciprocal)
+        ragged = 'deg2_invariant_l2_diff' in items and len(set(items)) > 1
+        if not ragged:
+            e.set_main_error(self.main_type, items)
+        e.init_state()
+        rho0 = e.density()
+        self._sig_ramps, self._thr_ramps = self._sw_ramps()
+        self.sw_sigma, self.sw_threshold = self.default_sigma, 0.06
+        hio_opt = opt['projections']['real']['HIO']
+        eis_opt = opt['projections']['real']['projections']['support']['enforce_initial_support']
+        limit = eis_opt['if_error_bigger_than'] if eis_opt['apply'] else np.inf
+        loops = opt['main_loop']['sub_loops']
+        eis_list, iterations = [], []
+        n_steps, fxs_steps = 0, 0
+        best_err_h, best_iter_h = np.full(B, np.inf), np.zeros(B, int)
+        for loop_number, loop_name in enumerate(loops['order']):
+            lo = loops[loop_name]
+            methods = {}
+            for key in lo['order']:
+                mo = lo['methods'][key]
+                methods[key] = ({'iterations': mo.get('iterations', 0), 'options': mo} if isinstance(mo, dict) else {'iterations': mo, 'options': {}})
+                if key not in ('HIO', 'ER', 'SW', 'SW_center', 'HIO_non_FXS', 'ER_non_FXS'):
+                    raise NotImplementedError('2-D loop method %r' % (key,))
+                if key.endswith('_non_FXS') and self.reciprocal_metrics:
+                    raise NotImplementedError('2-D %s with reciprocal metrics enabled: the reference raises' % key)
+            beta_cfg = hio_opt['beta'][loop_number] if len(hio_opt['beta']) - 1 >= loop_number else [0.5, 0.5, -1 / 700, 1600]
+            ramp = hs.ExponentialRamp(*beta_cfg)
+            if 'SW' in methods:
+                self._update_shrink_wrap(0, loop_number)
+            e.begin_sub_loop()                                        # stale = hist, latest_intensity = None (reconstruct.py:859, 866)
+            loop_first_step, step_iteration = n_steps, []
+            step = sw_step = iteration = 0
+            for iteration in range(1, lo['iterations'] + 1):
+                for key in lo['order']:
+                    if key == 'SW':
+                        eis_list.append(e.shrinkwrap_state(self.sw_sigma, self.sw_threshold, limit))
+                        sw_step += 1
+                        self._update_shrink_wrap(sw_step, loop_number)
+                        continue
+                    if key == 'SW_center':
+                        if n_steps == 0:
+                            raise IndexError("SW_center before any phasing step: error_dict['main'][-1] of an empty list (reconstruct.py:887)")
+                        eis_list.append(e.fetch_main_errors(n_steps - 1, 1)[0] > limit)
+                        for _ in range(methods[key]['iterations']):
+                            e.shrinkwrap_state(self.sw_sigma, self.sw_threshold, limit)     # (the same decision: no step in between)
+                            e.refresh_reciprocal_density()
+                            sw_step += 1
+                            self._update_shrink_wrap(sw_step, loop_number)
+                        continue
+                    repeats = methods[key]['iterations']
+                    ft_stab = self._change_to_ft_stab(methods[key]['options'], key, eis_list)
+                    if ragged and repeats:
+                        raise ValueError('main error over metrics of different shapes (inhomogeneous array upstream, fxs_IO_methods.py:758)')
+                    betas = np.array([ramp.eval(step + i) for i in range(repeats)], dtype=float)
+                    e.run(key, ft_stab, betas, fetch=False)           # (a block of no steps still takes / drops the non-FXS intensity)
+                    step += repeats
+                    n_steps += repeats
+                    step_iteration += [iteration] * repeats
+                    if not key.endswith('_non_FXS'):
+                        fxs_steps += repeats
+            if n_steps > loop_first_step:                             # the best ITERATION is followed on the host (reconstruct.py:934-938)
+                errs = e.fetch_main_errors(loop_first_step, n_steps - loop_first_step)
+                for i, it in enumerate(step_iteration):
+                    better = best_err_h > errs[i]
+                    best_err_h = np.where(better, errs[i], best_err_h)
+                    best_iter_h = np.where(better, it, best_iter_h)
+            reselect = best_iter_h > lo.get('best_density_not_in_first_n_iterations', np.inf)      # 945-949
+            if np.any(reselect):
+                e.select_best(reselect)
+            iterations.append(iteration)
+        err_real, err_main = e.fetch_errors(0, n_steps), e.fetch_main_errors(0, n_steps)
+        err_recip = e.fetch_reciprocal_metrics(0, n_steps) if self.reciprocal_metrics else {}
+        unknowns = e.unknowns() if fxs_steps else None
+        return (rho0, (e.reciprocal_density(True), e.density(True)), (e.reciprocal_density(), e.density()), e.best_error()[0], e.support(True),
+                e.support(), err_real, err_main, err_recip, unknowns, iterations)
+
+    def _generate_output(self, rho0, best_pair, last_pair, best_err, best_mask, support, err_real, err_main, err_recip, unknowns, iterations):
+        """output modifiers + generate_output (reconstruct.py:721-765, 985-1035) on the pairs a loop leaves"""
+        e, B, opt = self.engine, self.B, self.opt
         self.neg_center_pos = None
         om = opt.get('output_density_modifiers', {})
         # assemble_output_modifier (reconstruct.py:721-755): shift_center, and with SO_freedom in use + fix_orientation the sketch
@@ -473,11 +580,11 @@ class MTIP2D:
         out = []
         for b in range(B):
             out.append({'real_density': best_pair[1][b], 'last_real_density': last_pair[1][b], 'reciprocal_density': best_pair[0][b],
-                        'last_reciprocal_density': last_pair[0][b], 'final_error': float(best['err'][b]), 'initial_density': rho0[b],
+                        'last_reciprocal_density': last_pair[0][b], 'final_error': float(best_err[b]), 'initial_density': rho0[b],
                         'initial_support': self.initial_support.copy(),
                         'error_dict': {'main': err_main[:, b].copy(), 'real': {'l2_projection_diff': err_real[:, b].copy()},
                                        'reciprocal': {n_: np.array(v_)[:, b].copy() for n_, v_ in err_recip.items()}},
-                        'support_mask': best['mask'][b], 'last_support_mask': support[b], 'loop_iterations': int(np.sum(iterations) + 1),
+                        'support_mask': best_mask[b], 'last_support_mask': support[b], 'loop_iterations': int(np.sum(iterations) + 1),
                         'fxs_unknowns': None if unknowns is None else unknowns[b],
                         'n_particles': np.full((n_steps, 1), self.rsetup.number_of_particles), 'n_particles_gradients': np.array([]),
                         'n_particles_fraction': np.array([]), 'grid_pair': grids, 'projection_matrices': masked,
