@@ -282,6 +282,26 @@ int mtip_op_hermitian_eig(mtip_ctx* ctx, int n, int n_mat, const mtip_cdouble* A
 /* the same for REAL symmetric matrices up to 128 x 128 (B_l of a real intensity has no imaginary part; the rules of
  * fxs_invariant_tools.py:1114-1131 stay on the host): LDS-resident solver, eigenvalues accurate to eps |A|_F as LAPACK's */
 int mtip_op_symmetric_eig(mtip_ctx* ctx, int n, int n_mat, const double* A, double* eigvals, double* eigvecs);
+/* cross-correlation -> degree-2 invariants, the step in front of the two above (csrc/k_extract.hip):
+ *   dimensions 3: ccd_to_deg2_invariant_3d_back_substitution (fxs_invariant_tools.py:578-645; 60-74 the Legendre products):
+ *     C_m = rfft(C)_m / n_delta (mathLibrary.py:484-490) for m = 0, stride, 2 stride, .. <= max_order, then per pair (q1, q2) from the
+ *     highest order down  B_l = C_l / c_l^l,  C_m -= B_l c_l^m,  c_l^m = P_l^m(q1) P_l^m(q2) / (2l + 1)
+ *   dimensions 2: ccd_to_deg2_invariant_2d (813-839): B_m = C_m
+ * The sizes are those of the data (not of the context's grid): cc (n_q, n_q, n_delta) float64 (the reference takes .real),
+ * b_out (max_order + 1, n_q, n_q) complex128 with the orders that are not multiples of order_stride (1 or 2) written as zeros
+ * (417-419).  flags: the modify_cc switches of modify_cross_correlation (235-289) for unmasked data, applied in its order while
+ * cc is read -- MTIP_CC_SUBTRACT_AVERAGE needs average_intensity (n_q); MTIP_CC_PI_PERIODICITY needs an even n_delta and
+ * bad_angles (n_delta): 1 where phi < pi/2 or phi >= 3 pi/2 (267); MTIP_CC_Q1Q2_SYMMETRIC.
+ * legendre (dimensions 3): (n_q, n_m (n_m + 1) / 2), n_m = max_order / stride + 1: gsl_sf_legendre_sphPlm(li stride, mi stride,
+ * cos theta_q) at li (li + 1) / 2 + mi, theta_q = ewald_sphere_theta_pi (physicsLibrary.py:94-95; line 602 takes it whatever pi_in_q
+ * says).  Every buffer may be host memory or memory of the context's device.  Built for n_q <= 4096, 2 max_order <= n_delta <= 4096
+ * and at most 64 extracted orders; beyond that MTIP_EINVAL with a message in mtip_last_error. */
+#define MTIP_CC_SUBTRACT_AVERAGE 1u
+#define MTIP_CC_PI_PERIODICITY 2u
+#define MTIP_CC_Q1Q2_SYMMETRIC 4u
+int mtip_op_cc_to_deg2(mtip_ctx* ctx, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
+                       const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
+                       mtip_cdouble* b_out);
 
 /* ---- the 2-D (polar) variant, operator level --------------------------------------
  * Grids (n_batch, Nq, n_phi) complex128 with n_phi = 2 M + 1 (harmonic_transforms.py:44-47); harmonic coefficients in numpy's

@@ -13,37 +13,6 @@
 #define AV_THREADS 256
 #define AV_NSTAT 12
 
-// a caller's array as device memory: itself when it is device memory, else a temporary that is filled / copied back
-struct DevView {
-    mtip_ctx* c = nullptr;
-    void* dev = nullptr;
-    void* host = nullptr;
-    size_t bytes = 0;
-    bool temp = false, writeback = false;
-    hipError_t err = hipSuccess;
-    DevView(mtip_ctx* c_, const void* p, size_t n, bool read, bool write) : c(c_), bytes(n), writeback(write) {
-        if (p == nullptr || n == 0) return;
-        hipPointerAttribute_t at;
-        const bool is_dev = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
-        (void)hipGetLastError();                    // (an unregistered host pointer sets the sticky error on some runtimes)
-        if (is_dev) {
-            dev = const_cast<void*>(p);
-            return;
-        }
-        temp = true;
-        host = const_cast<void*>(p);
-        err = hipMalloc(&dev, n);
-        if (err == hipSuccess && read) err = mtip_copy(c, dev, p, n, hipMemcpyHostToDevice);
-    }
-    hipError_t finish() {                           // after the stream has been synchronised
-        if (temp && writeback && err == hipSuccess) err = mtip_copy(c, host, dev, bytes, hipMemcpyDeviceToHost);
-        return err;
-    }
-    ~DevView() {
-        if (temp && dev) (void)hipFree(dev);
-    }
-};
-
 // ---- moments, integrals and extrema of n grids (partials per workgroup, then a fixed-order reduction: reproducible) ----------
 // per grid: [0] sum w Re, [1..3] sum w Re {x, y, z}, [4] sum w Re^2, [5] sum w (Re - Re ref)^2, [6] max Re, [7] min Re,
 // [8], [9] sum of the entries "> 0" in numpy's lexicographic order on complex numbers (Re > 0, or Re == 0 and Im > 0), [10] their count

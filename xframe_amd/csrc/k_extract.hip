@@ -11,6 +11,7 @@
 // their small eigenvalues.
 // A one-off setup computation (L+1 matrices of Nq x Nq): matrices stay in global memory (L2 resident), 8 lanes per pair.
 #include "mtip_internal.h"
+#include <cmath>
 
 #define HE_TG 8
 #define HE_MAX_SWEEPS 60
@@ -587,4 +588,290 @@ extern "C" int mtip_op_symmetric_eig(mtip_ctx* c, int n, int n_mat, const double
     if (dU) (void)hipFree(dU);
     if (dl) (void)hipFree(dl);
     return rc;
+}
+
+// ---- cross-correlation -> B_l -----------------------------------------------------------------------------------------------
+// The part of `extract` in front of the eigen-decompositions above: cross-correlation C(q1, q2, Delta) -> degree-2 invariants
+//   xframe/projects/fxs/projectLibrary/fxs_invariant_tools.py:578-645   ccd_to_deg2_invariant_3d_back_substitution
+//                                                             60-74     ccd_associated_legendre_matrices_single_l
+//                                                             813-839   ccd_to_deg2_invariant_2d
+//                                                             235-289   modify_cross_correlation (subtract_average_intensity,
+//                                                                       pi_periodicity, q1q2_symmetric; unmasked data)
+//   xframe/library/mathLibrary.py:484-490                               circularHarmonicTransform_real_forward (rfft / n)
+// One kernel.  A workgroup owns CX_TP pairs (q1, q2 .. q2 + CX_TP - 1): their rows are one contiguous piece of C; each of its waves
+// owns CX_PW of them.  The rows are read once, in chunks of CX_DC folded samples that sit in the registers of the wave (sample
+// c0 + lane in lane `lane`, the next chunk loading while this one is summed); lane mi accumulates the harmonic m = mi * stride of the
+// CX_PW pairs, reading the samples lane by lane (v_readlane: no LDS traffic); the triangular system  C_m = sum_l B_l c_l^m  is then
+// solved inside the wave from the highest order down (the value of lane li goes to all lanes, lanes below it subtract); B_l leaves
+// through LDS so that consecutive lanes write consecutive q2.  Nothing of the size of C is written.
+//
+// Folding (the sum is a table contraction, n_Delta is arbitrary):
+//   * stride 2 and even n_Delta: the samples Delta and Delta + n/2 share the twiddle of every even m:  y[d] = x[d] + x[d + n/2],
+//     n' = n / 2, m' = m / 2; otherwise y = x, n' = n, m' = m
+//   * d and n' - d share the cosine and differ in the sign of the sine:  E[d] = y[d] + y[n'-d], O[d] = y[d] - y[n'-d] for
+//     0 < d < n'/2, E = y, O = 0 at d = 0 and d = n'/2
+//   C_m = (1/n) (sum_d E[d] cos(2 pi m' d / n') - i sum_d O[d] sin(2 pi m' d / n')),  d = 0 .. floor(n'/2)
+// The twiddles come from a table of n' entries made on the host in extended precision, indexed by (m' d) mod n' (kept by
+// addition); it sits in LDS up to CX_TW_LDS entries and in global memory (L2) beyond.
+
+#define CX_WAVES 4
+#define CX_PW 4                        // pairs per wave (register block)
+#define CX_TP (CX_WAVES * CX_PW)       // pairs per workgroup
+#define CX_DC 64                       // folded samples per register chunk: one per lane
+#define CX_TW_LDS 1024                 // twiddle entries held in LDS
+#define CX_MAX_M 64                    // harmonics per pair: one lane each
+#define CX_MAX_NQ 4096
+#define CX_MAX_ND 4096
+
+struct CcArgs {
+    const double* cc;                  // (nq, nq, nd)
+    const double* avg;                 // (nq) average intensity (MTIP_CC_SUBTRACT_AVERAGE)
+    const uint8_t* bad;                // (nd) angles zeroed by MTIP_CC_PI_PERIODICITY
+    const double* leg;                 // (nq, ntri) P_l^m(cos theta_q), l = li stride, m = mi stride, at li (li + 1) / 2 + mi
+    const double2* tw;                 // (np) (cos, sin)(2 pi k / np)
+    double2* out;                      // (n_out, nq, nq)
+    int nq, nd, np, half, nfold, stride, mstep, n_m, n_out, backsub, flags, ntri;
+    double inv_n;
+};
+
+// one sample after subtract_average_intensity and pi_periodicity (fxs_invariant_tools.py:245-247, 264-269)
+__device__ __forceinline__ double cx_val(const CcArgs& a, int q1, int q2, int d) {
+    const double* row = a.cc + ((size_t)q1 * a.nq + q2) * a.nd;
+    const double sub = (a.flags & MTIP_CC_SUBTRACT_AVERAGE) ? a.avg[q1] * a.avg[q2] : 0.0;
+    double v = row[d] - sub;
+    if (a.flags & MTIP_CC_PI_PERIODICITY) {
+        const int h = a.nd >> 1, d2 = d >= h ? d - h : d + h;          // the copy rolled by n / 2
+        const double w = row[d2] - sub;
+        v = (a.bad[d] ? 0.0 : v) + (a.bad[d2] ? 0.0 : w);
+    }
+    return v;
+}
+// ... after q1q2_symmetric (271-279): the mean with C(q2, q1, -Delta), index 0 kept
+__device__ __forceinline__ double cx_sample(const CcArgs& a, int q1, int q2, int d) {
+    double v = cx_val(a, q1, q2, d);
+    if (a.flags & MTIP_CC_Q1Q2_SYMMETRIC) v = (cx_val(a, q2, q1, d == 0 ? 0 : a.nd - d) + v) / 2;
+    return v;
+}
+__device__ __forceinline__ double cx_y(const CcArgs& a, int q1, int q2, int d) {
+    double v = cx_sample(a, q1, q2, d);
+    if (a.half) v += cx_sample(a, q1, q2, d + a.np);
+    return v;
+}
+
+// the (E, O) pair of folded sample d of one pair of shells (zeros beyond the folded range or the last shell)
+__device__ __forceinline__ void cx_load(const CcArgs& a, int q1, int q2, int d, double& E, double& O) {
+    E = O = 0.0;
+    if (d < a.nfold && q2 < a.nq) {
+        const double y = cx_y(a, q1, q2, d);
+        if (d == 0 || 2 * d == a.np) {
+            E = y;
+        } else {
+            const double z = cx_y(a, q1, q2, a.np - d);
+            E = y + z;
+            O = y - z;
+        }
+    }
+}
+// how many samples of y the entry E[d] holds
+__device__ __forceinline__ double cx_weight(const CcArgs& a, int d) { return d >= a.nfold ? 0.0 : (d == 0 || 2 * d == a.np) ? 1.0 : 2.0; }
+// the value lane `src` (wave-uniform) holds, for every lane
+__device__ __forceinline__ double cx_lane(double v, int src) {
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+    const int lo = __builtin_amdgcn_readlane((int)__double_as_longlong(v), src);
+    return __hiloint2double(hi, lo);
+}
+
+__global__ void __launch_bounds__(CX_WAVES * 64) k_cc_deg2(CcArgs a) {
+    __shared__ double2 s_buf[CX_MAX_M * CX_TP];        // B of (order slot, pair) on its way out
+    __shared__ double2 s_tw[CX_TW_LDS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int q1 = blockIdx.y, q2base = blockIdx.x * CX_TP, q2w = q2base + wave * CX_PW;
+    const bool tw_lds = a.np <= CX_TW_LDS;
+    if (tw_lds)
+        for (int k = tid; k < a.np; k += CX_WAVES * 64) s_tw[k] = a.tw[k];
+    __syncthreads();
+    const int mp = lane < a.n_m ? lane * a.mstep : 0;  // m' of this lane
+    int k = 0;                                         // (m' d) mod n'
+    // A chunk of 64 folded samples lives in the registers of the wave, sample c0 + lane in lane `lane`; the sums read it lane by lane.
+    double E[CX_PW], O[CX_PW], En[CX_PW], On[CX_PW], re[CX_PW], im[CX_PW], shift[CX_PW];
+#pragma unroll
+    for (int p = 0; p < CX_PW; ++p) cx_load(a, q1, q2w + p, lane, E[p], O[p]);
+    // A constant taken off the samples leaves every harmonic m != 0 unchanged (the twiddles of a full period sum to zero) and m = 0
+    // gets it back below.  With the mean of the first chunk as that constant the sums no longer carry the large angle-independent
+    // part of a cross-correlation through their rounding: the weak high harmonics keep their digits.
+    {
+        const double w0 = cx_weight(a, lane);
+#pragma unroll
+        for (int p = 0; p < CX_PW; ++p) {
+            double se = E[p], sw = w0;
+            for (int o = 32; o > 0; o >>= 1) {
+                se += __shfl_xor(se, o);
+                sw += __shfl_xor(sw, o);
+            }
+            shift[p] = se / sw;
+            re[p] = im[p] = 0.0;
+        }
+    }
+    for (int c0 = 0; c0 < a.nfold; c0 += CX_DC) {
+        const bool more = c0 + CX_DC < a.nfold;
+        if (more)
+#pragma unroll
+            for (int p = 0; p < CX_PW; ++p) cx_load(a, q1, q2w + p, c0 + CX_DC + lane, En[p], On[p]);
+        const double wd = cx_weight(a, c0 + lane);
+#pragma unroll
+        for (int p = 0; p < CX_PW; ++p) E[p] -= wd * shift[p];
+        const int lim = min(CX_DC, a.nfold - c0);
+        for (int dd = 0; dd < lim; ++dd) {
+            const double2 t = tw_lds ? s_tw[k] : a.tw[k];
+            k += mp;
+            if (k >= a.np) k -= a.np;
+#pragma unroll
+            for (int p = 0; p < CX_PW; ++p) {
+                re[p] += cx_lane(E[p], dd) * t.x;
+                im[p] -= cx_lane(O[p], dd) * t.y;
+            }
+        }
+        if (more)
+#pragma unroll
+            for (int p = 0; p < CX_PW; ++p) {
+                E[p] = En[p];
+                O[p] = On[p];
+            }
+    }
+#pragma unroll
+    for (int p = 0; p < CX_PW; ++p) {
+        if (lane == 0) re[p] += shift[p] * (double)a.np;
+        re[p] *= a.inv_n;
+        im[p] *= a.inv_n;
+    }
+    if (a.backsub) {
+        // B_l = C_l / c_l^l,  C_m -= B_l c_l^m (m < l),  c_l^m = P_l^m(q1) P_l^m(q2) / (2 l + 1)   (fxs_invariant_tools.py:629-632)
+        // lane li prepares 1 / c_l^l of its own order once: one division per pair instead of one per pair and order
+        const double* leg1 = a.leg + (size_t)q1 * a.ntri;
+        double rdiag[CX_PW];
+        {
+            const int dg = lane * (lane + 1) / 2 + lane;
+            const bool act = lane < a.n_m;
+            const double p1 = act ? leg1[dg] : 1.0;
+#pragma unroll
+            for (int p = 0; p < CX_PW; ++p) {
+                const int q2 = min(q2w + p, a.nq - 1);
+                const double p2 = act ? a.leg[(size_t)q2 * a.ntri + dg] : 1.0;
+                rdiag[p] = 1.0 / (p1 * p2 / (double)(2 * lane * a.stride + 1));
+            }
+        }
+        for (int li = a.n_m - 1; li >= 0; --li) {
+            const int tri = li * (li + 1) / 2;
+            const double inv_norm = 1.0 / (double)(2 * li * a.stride + 1);
+            const bool act = lane < li;
+            const double p1 = act ? leg1[tri + lane] * inv_norm : 0.0;
+#pragma unroll
+            for (int p = 0; p < CX_PW; ++p) {
+                const int q2 = min(q2w + p, a.nq - 1);
+                const double cm = act ? p1 * a.leg[(size_t)q2 * a.ntri + tri + lane] : 0.0;
+                const double r = cx_lane(rdiag[p], li);
+                const double br = cx_lane(re[p], li) * r, bi = cx_lane(im[p], li) * r;
+                if (act) {
+                    re[p] -= br * cm;
+                    im[p] -= bi * cm;
+                } else if (lane == li) {
+                    re[p] = br;
+                    im[p] = bi;
+                }
+            }
+        }
+    }
+    if (lane < a.n_m)
+#pragma unroll
+        for (int p = 0; p < CX_PW; ++p) s_buf[lane * CX_TP + wave * CX_PW + p] = make_double2(re[p], im[p]);
+    __syncthreads();
+    // every order 0 .. n_out - 1 is written: the ones that were not extracted as zeros (fxs_invariant_tools.py:417-419)
+    for (int idx = tid; idx < a.n_out * CX_TP; idx += CX_WAVES * 64) {
+        const int l = idx / CX_TP, p = idx - l * CX_TP, q2 = q2base + p;
+        if (q2 >= a.nq) continue;
+        const int li = l / a.stride;
+        const bool have = (l - li * a.stride) == 0 && li < a.n_m;
+        a.out[((size_t)l * a.nq + q1) * a.nq + q2] = have ? s_buf[li * CX_TP + p] : make_double2(0.0, 0.0);
+    }
+}
+
+extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
+                                  const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
+                                  mtip_cdouble* b_out) {
+    if (!c) return MTIP_EINVAL;
+    char msg[320];
+    const int s = order_stride;
+    const int n_m = (s == 1 || s == 2) && max_order >= 0 ? max_order / s + 1 : 0;
+    if (!cc || !b_out || (dimensions != 2 && dimensions != 3) || (s != 1 && s != 2) || max_order < 0 || n_q < 1 || n_delta < 2 ||
+        (flags & ~(uint32_t)(MTIP_CC_SUBTRACT_AVERAGE | MTIP_CC_PI_PERIODICITY | MTIP_CC_Q1Q2_SYMMETRIC))) {
+        c->err = "cc_to_deg2: null buffer, dimensions not 2 or 3, order stride not 1 or 2, or unknown flag";
+        return MTIP_EINVAL;
+    }
+    if (n_q > CX_MAX_NQ || n_delta > CX_MAX_ND || n_m > CX_MAX_M || n_delta < 2 * max_order) {
+        snprintf(msg, sizeof msg,
+                 "cc_to_deg2: built for n_q <= %d, 2 max_order <= n_delta <= %d and at most %d extracted orders (max_order <= %d at "
+                 "stride 2, <= %d at stride 1); got n_q = %d, n_delta = %d, max_order = %d, stride = %d",
+                 CX_MAX_NQ, CX_MAX_ND, CX_MAX_M, 2 * CX_MAX_M - 1, CX_MAX_M - 1, n_q, n_delta, max_order, s);
+        c->err = msg;
+        return MTIP_EINVAL;
+    }
+    if (((flags & MTIP_CC_SUBTRACT_AVERAGE) && !average_intensity) || ((flags & MTIP_CC_PI_PERIODICITY) && !bad_angles) ||
+        (dimensions == 3 && !legendre)) {
+        c->err = "cc_to_deg2: a table the flags / dimensions ask for is null (average_intensity, bad_angles, legendre)";
+        return MTIP_EINVAL;
+    }
+    if ((flags & MTIP_CC_PI_PERIODICITY) && (n_delta & 1)) {
+        c->err = "cc_to_deg2: pi_periodicity needs an even number of angles (fxs_invariant_tools.py:265)";
+        return MTIP_EINVAL;
+    }
+    (void)hipSetDevice(c->device);
+    CcArgs a{};
+    a.nq = n_q;
+    a.nd = n_delta;
+    a.half = (s == 2 && (n_delta & 1) == 0) ? 1 : 0;
+    a.np = a.half ? n_delta / 2 : n_delta;
+    a.mstep = a.half ? 1 : s;
+    a.nfold = a.np / 2 + 1;
+    a.stride = s;
+    a.n_m = n_m;
+    a.n_out = max_order + 1;
+    a.backsub = dimensions == 3;
+    a.flags = (int)flags;
+    a.ntri = n_m * (n_m + 1) / 2;
+    a.inv_n = 1.0 / (double)n_delta;
+    std::vector<double2> tw((size_t)a.np);
+    for (int k = 0; k < a.np; ++k) {
+        const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)a.np;
+        tw[k] = make_double2((double)cosl(ang), (double)sinl(ang));
+    }
+    const size_t nqq = (size_t)n_q * n_q;
+    DevView v_cc(c, cc, nqq * n_delta * sizeof(double), true, false);
+    DevView v_avg(c, (flags & MTIP_CC_SUBTRACT_AVERAGE) ? average_intensity : nullptr, (size_t)n_q * sizeof(double), true, false);
+    DevView v_bad(c, (flags & MTIP_CC_PI_PERIODICITY) ? bad_angles : nullptr, (size_t)n_delta, true, false);
+    DevView v_leg(c, a.backsub ? legendre : nullptr, (size_t)n_q * a.ntri * sizeof(double), true, false);
+    DevView v_tw(c, tw.data(), tw.size() * sizeof(double2), true, false);
+    DevView v_out(c, b_out, nqq * a.n_out * sizeof(double2), false, true);
+    for (DevView* v : {&v_cc, &v_avg, &v_bad, &v_leg, &v_tw, &v_out})
+        if (v->err != hipSuccess) {
+            c->err = std::string("cc_to_deg2: ") + hipGetErrorString(v->err);
+            return v->err == hipErrorOutOfMemory ? MTIP_ENOMEM : MTIP_EHIP;
+        }
+    a.cc = (const double*)v_cc.dev;
+    a.avg = (const double*)v_avg.dev;
+    a.bad = (const uint8_t*)v_bad.dev;
+    a.leg = (const double*)v_leg.dev;
+    a.tw = (const double2*)v_tw.dev;
+    a.out = (double2*)v_out.dev;
+    {
+        ProfScope ps(c, "cc_deg2");
+        hipLaunchKernelGGL(k_cc_deg2, dim3((unsigned)div_up(n_q, CX_TP), (unsigned)n_q), dim3(CX_WAVES * 64), 0, c->stream, a);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = v_out.finish();
+    if (e != hipSuccess) {
+        c->err = std::string("cc_to_deg2: ") + hipGetErrorString(e);
+        return MTIP_EHIP;
+    }
+    return MTIP_OK;
 }

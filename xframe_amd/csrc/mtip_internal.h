@@ -450,4 +450,35 @@ static inline hipError_t mtip_copy(mtip_ctx* c, void* dst, const void* src, size
     return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
 }
 
+// a caller's array as device memory: itself when it is device memory, else a temporary that is filled / copied back
+struct DevView {
+    mtip_ctx* c = nullptr;
+    void* dev = nullptr;
+    void* host = nullptr;
+    size_t bytes = 0;
+    bool temp = false, writeback = false;
+    hipError_t err = hipSuccess;
+    DevView(mtip_ctx* c_, const void* p, size_t n, bool read, bool write) : c(c_), bytes(n), writeback(write) {
+        if (p == nullptr || n == 0) return;
+        hipPointerAttribute_t at;
+        const bool is_dev = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
+        (void)hipGetLastError();                    // (an unregistered host pointer sets the sticky error on some runtimes)
+        if (is_dev) {
+            dev = const_cast<void*>(p);
+            return;
+        }
+        temp = true;
+        host = const_cast<void*>(p);
+        err = hipMalloc(&dev, n);
+        if (err == hipSuccess && read) err = mtip_copy(c, dev, p, n, hipMemcpyHostToDevice);
+    }
+    hipError_t finish() {                           // after the stream has been synchronised
+        if (temp && writeback && err == hipSuccess) err = mtip_copy(c, host, dev, bytes, hipMemcpyDeviceToHost);
+        return err;
+    }
+    ~DevView() {
+        if (temp && dev) (void)hipFree(dev);
+    }
+};
+
 static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }

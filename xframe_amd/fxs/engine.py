@@ -334,6 +334,52 @@ class Engine:
             evs.append(w)
         return pms, evs
 
+    # ------------------------------------------------------------------ extract: cross-correlation -> B_l (fxs_invariant_tools.py:578-645, 813-839)
+    def cc_to_deg2(self, cc, max_order, order_stride=2, dimensions=3, legendre=None, average_intensity=None, bad_angles=None,
+                   q1q2_symmetric=False):
+        """mtip_op_cc_to_deg2: cc (Nq, Nq, n_delta) float64, a numpy array or a torch tensor on this engine's device (then B_l
+        comes back as a tensor on it).  Returns B_l (max_order + 1, Nq, Nq) complex128, the orders that are not multiples of
+        order_stride as zeros.  legendre: (Nq, n_m (n_m + 1) / 2) table for dimensions 3 (``extract.legendre_table``);
+        average_intensity (Nq): subtract_average_intensity; bad_angles (n_delta) bool: pi_periodicity."""
+        on_device = not isinstance(cc, np.ndarray) and hasattr(cc, 'data_ptr')
+        if on_device:
+            import torch
+            if cc.dtype != torch.float64 or not cc.is_cuda:
+                raise TypeError('cc_to_deg2: a tensor must be float64 on the GPU (the reference takes .real of the data)')
+            cc = cc.contiguous()
+        else:
+            cc = np.asarray(cc)
+            cc = _lib.as_f64(cc.real if np.iscomplexobj(cc) else cc)
+        if cc.ndim != 3 or cc.shape[0] != cc.shape[1]:
+            raise ValueError('cc_to_deg2: cc must have shape (Nq, Nq, n_delta), got %r' % (tuple(cc.shape),))
+        nq, nd = int(cc.shape[0]), int(cc.shape[2])
+        flags = 0
+        avg = bad = leg = None
+        if average_intensity is not None:
+            avg = _lib.as_f64(average_intensity)
+            assert avg.shape == (nq,), avg.shape
+            flags |= 1
+        if bad_angles is not None:
+            bad = _lib.as_u8(np.asarray(bad_angles, dtype=bool))
+            assert bad.shape == (nd,), bad.shape
+            flags |= 2
+        if q1q2_symmetric:
+            flags |= 4
+        if legendre is not None:
+            leg = _lib.as_f64(legendre)
+            n_m = int(max_order) // int(order_stride) + 1
+            assert leg.shape == (nq, n_m * (n_m + 1) // 2), leg.shape
+        shape = (int(max_order) + 1, nq, nq)
+        if on_device:
+            out = torch.empty(shape, dtype=torch.complex128, device=cc.device)
+            p_in, p_out = self._tp(cc), self._tp(out)
+        else:
+            out = np.empty(shape, complex)
+            p_in, p_out = _lib.ptr(cc), _lib.ptr(out)
+        self._ck(self.lib.mtip_op_cc_to_deg2(self.ctx, nq, nd, int(max_order), int(order_stride), int(dimensions), flags, p_in,
+                                             _lib.ptr(avg), _lib.ptr(bad), _lib.ptr(leg), p_out))
+        return out
+
     # ------------------------------------------------------------------ rotational alignment (average.py:920-960)
     def _so3_setup(self):
         if not getattr(self, '_so3_ready', False):

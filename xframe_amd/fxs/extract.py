@@ -122,3 +122,221 @@ def apply_invariant_constraints(engine, b_coeff, q_id_limits, bl_enforce_psd=Tru
         if hi > lo:
             out[o, lo:hi, lo:hi] = nearest_positive_semidefinite_matrix(engine, b_coeff[o, lo:hi, lo:hi])
     return out
+
+
+# ---- cross-correlation -> B_l -> V_l: the route in front of the functions above ----------------------------------------------------
+# xframe/projects/fxs/extract.py:95-168 (extract_bl_from_cc), 332-414 (masks), 496-532 (extract) and
+# xframe/projects/fxs/projectLibrary/fxs_invariant_tools.py:374-422 (cross_correlation_to_deg2_invariant), 578-645 (back-substitution),
+# 813-839 (2-D), 235-289 (modify_cross_correlation), 1259-1269 (error estimate).  The arithmetic on the cross-correlation runs in
+# one kernel (csrc/k_extract.hip, Engine.cc_to_deg2); everything here is settings bookkeeping.  What the reference offers and this
+# route does not build raises NotImplementedError with the option and the reference line: no CPU fallback.
+_BUILT_MODIFY_CC = ('subtract_average_intensity', 'pi_periodicity', 'q1q2_symmetric')
+_REFERENCE_MODES = ('lstsq', 'legendre', 'back_substitution', 'back_substitution_psd', 'back_substitution_qqsym',
+                    'back_substitution_memory_hungry')               # the keys of fxs_invariant_tools.py:440
+
+
+def legendre_table(radial_points, xray_wavelength, max_order, stride):
+    """(Nq, n_m (n_m + 1) / 2) table of mtip_op_cc_to_deg2: gsl_sf_legendre_sphPlm(li stride, mi stride, cos theta_q) at
+    li (li + 1) / 2 + mi with theta_q = ewald_sphere_theta_pi (physicsLibrary.py:94-95; fxs_invariant_tools.py:602 takes this
+    geometry whatever the dataset's pi_in_q says)."""
+    from .hostsetup import sph_plm
+    qs = np.asarray(radial_points, dtype=float)
+    x = np.cos(np.arccos(qs * xray_wavelength / (4 * np.pi)))        # 602, 65
+    if not np.isfinite(x).all():
+        raise ValueError('q * wavelength / (4 pi) > 1: the radial points do not lie on the Ewald sphere of this wavelength')
+    n_m = int(max_order) // int(stride) + 1
+    li, mi = np.tril_indices(n_m)                                    # row-major lower triangle: li (li + 1) / 2 + mi
+    return np.ascontiguousarray(sph_plm((li * stride)[None, :], (mi * stride)[None, :], x[:, None]))
+
+
+def _check_cc_options(metadata, dim):
+    mask_type = (metadata.get('cc_mask') or {'type': 'none'}).get('type', 'none')
+    if mask_type != 'none':
+        raise NotImplementedError('cc_mask.type %r (fxs_invariant_tools.py:205-232): only unmasked data (type none) is built; the masked '
+                                  'routes interpolate on the host upstream (605-608)' % (mask_type,))
+    for key, value in (metadata.get('modify_cc') or {}).items():
+        if key not in _BUILT_MODIFY_CC and not (isinstance(value, (bool, np.bool_)) and not value):
+            raise NotImplementedError('modify_cc.%s (fxs_invariant_tools.py:235-289): built are %s' % (key, ', '.join(_BUILT_MODIFY_CC)))
+    mode = metadata.get('mode', False)
+    if dim == 3 and mode != 'back_substitution':
+        if isinstance(mode, (bool, np.bool_)):
+            raise NotImplementedError("bl extraction without 'mode' (fxs_invariant_tools.py:414-415 returns the (Nq, Nq, orders) layout of "
+                                      "ccd_to_deg2_invariant_3d): the worker always names the mode (extract.py:134)")
+        if mode not in _REFERENCE_MODES:
+            raise NotImplementedError('bl_extraction_method %r is not a key of the reference\'s mode table and asserts upstream: Given B_l '
+                                      'extraction mode "%s" is unknown. Known modes are %s (fxs_invariant_tools.py:440-446; the settings '
+                                      'file offers legendre_approx)' % (mode, mode, list(_REFERENCE_MODES)))
+        raise NotImplementedError('bl_extraction_method %r (fxs_invariant_tools.py:440): only back_substitution (578-645) is built' % (mode,))
+
+
+def cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
+    """fxs_invariant_tools.py:374-422 with the arithmetic on the device.  metadata as the worker builds it (extract.py:134):
+    'data_grid' {qs, thetas, phis}, 'orders' (arange(max_order + 1)), 'assume_zero_odd_orders', 'modify_cc', 'cc_mask', 'mode',
+    'xray_wavelength' (dim 3), 'average_intensity'.  Returns (b_coeff (max_order + 1, Nq, Nq) complex, odd orders zero when they are
+    assumed zero, qq_mask (Nq, Nq) all true: the unmasked case, 136-139, 609)."""
+    if dim not in (2, 3):
+        raise ValueError('dim must be 2 or 3')
+    _check_cc_options(metadata, dim)
+    orders = np.asarray(metadata['orders'])
+    max_order = int(orders.max())
+    if not np.array_equal(orders, np.arange(max_order + 1)):
+        raise NotImplementedError('orders other than arange(max_order + 1) (the worker passes these, extract.py:134)')
+    n_delta = int(cc.shape[-1])
+    if n_delta < 2 * max_order:
+        # the worker clamps max_order to n_delta // 2 first (extract.py:112-119); the reference's own fallback is broken (388-391)
+        raise ValueError('max_order %d cannot be resolved with %d angular points (need n_delta >= 2 max_order)' % (max_order, n_delta))
+    data_grid = metadata['data_grid']
+    phis = np.asarray(data_grid['phis'], dtype=float)
+    mod = metadata.get('modify_cc') or {}
+    avg = metadata.get('average_intensity', False)
+    avg = np.asarray(getattr(avg, 'data', avg))
+    kw = {}
+    if mod.get('subtract_average_intensity', False) and avg.ndim == 1:                                    # 245
+        kw['average_intensity'] = avg
+    if mod.get('pi_periodicity', False):
+        assert n_delta % 2 == 0, 'for odd number of phi symmetry enforcing is not possible since phi+pi is not an existing grid point.'
+        assert n_delta == len(phis), 'Cross correlation has {} angular datapoints but only {} angle values are given.'.format(n_delta, len(phis))
+        kw['bad_angles'] = (phis < np.pi / 2) | (phis >= 3 * np.pi / 2)                                  # 267
+    stride = 2 if metadata['assume_zero_odd_orders'] else 1
+    if dim == 3:
+        kw['legendre'] = legendre_table(data_grid['qs'], metadata['xray_wavelength'], max_order, stride)
+    b = engine.cc_to_deg2(cc, max_order, order_stride=stride, dimensions=dim, q1q2_symmetric=bool(mod.get('q1q2_symmetric', False)), **kw)
+    if not isinstance(b, np.ndarray):
+        b = b.cpu().numpy()
+    return b, np.ones(b.shape[1:], dtype=bool)
+
+
+def calc_deg_2_invariant_line_mask(radial_points, max_order, line_specifier, invert=False):
+    """extract.py:368-414: the side of one line (or, for a tuple, of two lines: q1 and q2) through two (order, q) points"""
+    qs = np.asarray(radial_points, dtype=float)
+    n_qs = len(qs)
+    grid = np.stack(np.meshgrid(np.arange(max_order + 1), qs, indexing='ij'), axis=-1)
+
+    def side(line):                                                  # mathLibrary.py:1131-1137
+        p1, p2 = np.array(line)
+        rot = np.array([[0, 1], [-1, 0]]) @ (p2 - p1)
+        return (-1 * np.sum((grid - p1) * rot[None, None, :], axis=-1)) >= 0
+    if isinstance(line_specifier, tuple):
+        mask1, mask2 = side(line_specifier[0]), side(line_specifier[1])
+        if not invert:
+            q1_id, q2_id = np.argmax(mask1, axis=1), np.argmax(mask2, axis=1)
+            if not mask1.any():
+                q1_id = n_qs - 1
+            if not mask2.any():
+                q2_id = n_qs - 1
+        else:
+            mask1, mask2 = ~mask1, ~mask2
+            q1_id, q2_id = np.argmin(mask1, axis=1), np.argmin(mask2, axis=1)
+            if mask1.all():
+                q1_id = n_qs
+            if mask1.all():                                          # (sic, 392: the first mask decides for the second line too)
+                q2_id = n_qs
+        q_id_limits = np.stack(np.broadcast_arrays(q1_id, q2_id), axis=-1)
+        mask = mask1[:, :, None] * mask2[:, None, :]
+    else:
+        mask = side(line_specifier)
+        if not invert:
+            q_id = np.argmax(mask, axis=1)
+            if not mask.any():
+                q_id = n_qs - 1
+        else:
+            mask = ~mask
+            q_id = np.argmin(mask, axis=1)
+            if mask.all():
+                q_id = n_qs
+        mask = mask[:, :, None] * mask[:, None, :]
+        q_id_limits = np.stack(np.broadcast_arrays(q_id, q_id), axis=-1)
+    return mask, q_id_limits
+
+
+def calc_deg_2_invariant_masks(dopt, bl_shape, q_mask, radial_points, max_order):
+    """extract.py:332-364 for bl_q_limits types 'none' and 'line': returns (mask (orders, Nq, Nq), q_id_limits (orders, 2, 2))"""
+    lim = dopt['bl_q_limits']
+    min_type, max_type = lim['min']['type'], lim['max']['type']
+    for t in (min_type, max_type):
+        if t not in ('none', 'line'):
+            raise NotImplementedError("bl_q_limits type %r (extract.py:342-353 knows 'line'; anything else means none)" % (t,))
+    empty_mask = np.ones(bl_shape, dtype=bool)
+    q_id_limits = np.zeros((bl_shape[0],) + (2, 2), dtype=int)
+    q_id_limits[..., 1] = len(q_mask)
+    if min_type == 'line':
+        min_mask, q_id_mins = calc_deg_2_invariant_line_mask(radial_points, max_order, lim['min']['line'])
+        q_id_limits[:, :, 0] = q_id_mins
+    else:
+        min_mask = empty_mask.copy()
+    if max_type == 'line':
+        max_mask, q_id_maxs = calc_deg_2_invariant_line_mask(radial_points, max_order, lim['max']['line'], invert=True)
+        q_id_limits[:, :, 1] = q_id_maxs
+    else:
+        max_mask = empty_mask.copy()
+    q_id_min = np.argmax(q_mask)
+    q_id_max = len(q_mask) - np.argmax(q_mask[::-1])
+    mask = min_mask & max_mask
+    mask[:, ~q_mask] = False
+    q_id_limits[q_id_limits[:, :, 0] < q_id_min] = q_id_min
+    q_id_limits[q_id_limits[:, :, 1] > q_id_max] = q_id_max
+    return mask, q_id_limits
+
+
+def calc_projection_matrix_error_estimate(deg2_invariant, proj_matrices):
+    """fxs_invariant_tools.py:1259-1269: |B_l - V_l V_l^+| / |B_l| where B_l != 0, -1 elsewhere"""
+    errors = np.full_like(deg2_invariant, -1)
+    for b, pr, e in zip(deg2_invariant, proj_matrices, errors):
+        if pr.ndim == 1:
+            pr = pr[:, None]
+        nz = b != 0
+        e[nz] = np.abs(b[nz] - (pr @ pr.conj().T)[nz]) / np.abs(b[nz])
+    return errors
+
+
+def extract_from_cross_correlation(engine, ccd, settings):
+    """extract.py:95-168 + 496-532 for the dataset I1I1 in three dimensions: `ccd` as ``io.load_ccd`` returns it, `settings` the
+    extract settings as a plain dict (default_0.01.yaml: dimensions, max_order, bl_eig_sort_mode, optimize_projection_matrices,
+    low_resolution_intensity_approximation, cross_correlation.datasets.I1I1 ...).  Returns the `data` dict of the reconstruct worker
+    with the key names of ``io.load_invariants`` (what _database_.py:611-646 saves)."""
+    opt = settings
+    dim = int(opt.get('dimensions', 3))
+    if opt.get('extraction_mode', 'cross_correlation') != 'cross_correlation':
+        raise NotImplementedError("extraction_mode %r (extract.py:72-77): this is the route 'cross_correlation'" % (opt['extraction_mode'],))
+    if opt.get('optimize_projection_matrices', {}).get('use', False):
+        raise NotImplementedError('optimize_projection_matrices.use: True (extract.py:446-451, prephase_projection_matrices 479-493)')
+    if dim != 3:
+        raise NotImplementedError('extract_from_cross_correlation with dimensions = 2 (extract.py:129-130; the invariants themselves are '
+                                  'built: cross_correlation_to_deg2_invariant(engine, cc, 2, ...))')
+    cco = opt['cross_correlation']
+    to_process = cco.get('datasets_to_process', ['I1I1'])
+    cc_arrays = ccd['cross_correlation']
+    for name in cc_arrays:
+        if name != 'I1I1' and name in cco['datasets'] and (not isinstance(to_process, (list, tuple)) or name in to_process):
+            raise NotImplementedError('cross-correlation dataset %r (extract.py:122-159): only I1I1 is built' % (name,))
+    dopt = cco['datasets']['I1I1']
+    avg = ccd['average_intensity']
+    avg = np.array(getattr(avg, 'data', avg), dtype=float)
+    qs = np.asarray(ccd['radial_points'], dtype=float)
+    phis = np.asarray(ccd['angular_points'], dtype=float)
+    max_order = min(int(opt['max_order']), len(phis) // 2)                                               # 112-119
+    meta = {**{k: v for k, v in ccd.items() if k != 'cross_correlation'}, **dopt, 'orders': np.arange(max_order + 1),
+            'mode': dopt['bl_extraction_method'], 'average_intensity': avg}                              # 134
+    b_coeff, q_mask = cross_correlation_to_deg2_invariant(engine, cc_arrays['I1I1'], dim, **meta)
+    mask, q_id_limits = calc_deg_2_invariant_masks(dopt, b_coeff.shape, q_mask, qs, max_order)
+    b_coeff = apply_invariant_constraints(engine, b_coeff, q_id_limits, dopt.get('bl_enforce_psd', False))
+    if dopt.get('modify_cc', {}).get('subtract_average_intensity', False):                               # 160-167
+        b_coeff[0] = avg[:, None] * avg[None, :] * (4 * np.pi if dim == 3 else 1)
+    sort_mode = 1 if opt.get('bl_eig_sort_mode', 'eigenvalues') == 'median_of_scaled_eigenvector' else 0  # 436-439
+    pms, _ = deg2_invariant_to_projection_matrices(engine, b_coeff, q_id_limits=q_id_limits, sort_mode=sort_mode)
+    errors = calc_projection_matrix_error_estimate(b_coeff, pms)
+    trapz = getattr(np, 'trapezoid', None) or np.trapz
+    integrated = trapz(avg * qs ** 2, x=qs, axis=0) * 4 * np.pi                                          # 518
+    low_order = int(opt.get('low_resolution_intensity_approximation', {}).get('max_order', 20))
+    matrices = np.empty(len(pms), object)
+    for i, m in enumerate(pms):
+        matrices[i] = m
+    low = np.empty(len(pms[:low_order + 1]), object)                                                     # 476
+    for i, m in enumerate(pms[:low_order + 1]):
+        low[i] = m
+    return {'dimensions': dim, 'xray_wavelength': ccd['xray_wavelength'], 'average_intensity': avg, 'data_radial_points': qs,
+            'data_angular_points': phis, 'data_min_q': float(qs.min()), 'max_order': max_order, 'data_projection_matrices': matrices,
+            'data_low_resolution_intensity_coefficients': low, 'data_projection_matrices_q_id_limits': {'I1I1': q_id_limits[:, 0]},
+            'data_projection_matrices_masks': {'I1I1': mask.sum(axis=2)}, 'data_projection_matrix_error_estimates': {'I1I1': errors},
+            'integrated_intensity': integrated, 'deg_2_invariant': {'I1I1': b_coeff}, 'deg_2_invariant_masks': {'I1I1': mask},
+            'deg_2_invariant_q_id_limits': {'I1I1': q_id_limits}, 'b_coeff': {'I1I1': b_coeff}}

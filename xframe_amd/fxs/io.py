@@ -9,6 +9,9 @@
   * ``load_invariants``       what ProjectDB.load_invariants (xframe/projects/fxs/_database_.py:566-609) makes of the tree of an
                               invariants file -- the `data` dict the reconstruct worker starts from.
 
+  * ``load_ccd``              what ProjectDB.load_ccd (_database_.py:482-564) makes of the tree of a cross-correlation file -- the
+                              `ccd` dict the extract worker starts from (``extract.extract_from_cross_correlation``).
+
 Writing the bytes needs an HDF5 library (absent from this image): ``write_hdf5`` / ``read_hdf5`` do it through h5py when it can
 be imported and raise otherwise.  The layouts are pinned by tests/golden/io_contract.npz (G16), recorded from the reference's own
 post_processing, plugin and loader running against a recording stand-in for h5py.File."""
@@ -153,6 +156,60 @@ def load_invariants(tree):
     elif data['dimensions'] == 2:
         data['data_projection_matrices'] = np.array(matrices)
     return data
+
+
+def load_ccd(tree, ccd_type='direct', dimensions=3):
+    """ProjectDB.load_ccd (_database_.py:482-564) on the tree of a cross-correlation file: the `ccd` dict of the extract worker
+    (extract.py:95-110).  ccd_type 'direct' (552-564): the file's keys as they are ('cross_correlation' {'I1I1': ...},
+    'radial_points', 'angular_points', 'average_intensity', 'xray_wavelength', ...); 'legacy' (496-550): 'ccf_q1q2_2p' (or
+    'intra'/'ccf_2p_q1q2'), 'q1', 'q2', 'phi', 'iaverage', the longer radial axis thinned to the shorter, optional 'ccf_q1q2_3p' /
+    '_4p' as I2I1 / I2I2, wavelength 1.23984 when absent.  Added in both: 'data_grid' {qs, thetas, phis} and 'dimensions'.
+    'average_intensity' stays the sampled values (the reference wraps them into a SampledFunction and reads .data back).  thetas:
+    ewald_sphere_theta_pi (physicsLibrary.py:94-95); the legacy loader takes arccos(q lambda / 2) instead when the file says
+    pi_in_q = False (543-546) -- the back-substitution computes its own angles with ewald_sphere_theta_pi whatever pi_in_q says
+    (fxs_invariant_tools.py:602), so that flag changes data_grid['thetas'] and nothing of B_l."""
+    data = dict(tree)
+    if ccd_type == 'direct':
+        qs, phis = np.asarray(data['radial_points']), np.asarray(data['angular_points'])
+        data['cross_correlation'] = dict(data['cross_correlation'])
+        data['average_intensity'] = np.asarray(data['average_intensity'])
+        thetas = np.arccos(qs * data['xray_wavelength'] / (4 * np.pi))
+        data['data_grid'] = {'qs': qs, 'thetas': thetas, 'phis': phis}
+        data['dimensions'] = dimensions
+        return data
+    if ccd_type != 'legacy':
+        raise AssertionError('ccd loading type {} not specifierd or known!'.format(ccd_type))
+    out = {}
+    cc = (data['intra']['ccf_2p_q1q2'] if 'intra' in data else data['ccf_q1q2_2p']).real
+    if cc.shape[0] < cc.shape[1]:
+        qs = data['q2']
+        step = int(np.round(cc.shape[1] / cc.shape[0]))
+        cc = cc[:, ::step]
+        a_int = data['iaverage'][::step]
+    elif cc.shape[0] > cc.shape[1]:
+        qs = data['q1']
+        step = int(np.round(cc.shape[0] / cc.shape[1]))              # (a float upstream, 509: a slice step numpy refuses)
+        cc = cc[::step, :]
+        a_int = data['iaverage'][::step]
+    else:
+        qs = data['q1']
+        a_int = data['iaverage']
+    other = {name: data[key].real for key, name in zip(['ccf_q1q2_3p', 'ccf_q1q2_4p'], ['I2I1', 'I2I2']) if key in data}
+    out['cross_correlation'] = {**{'I1I1': cc}, **other}
+    qs, phis = np.asarray(qs), np.asarray(data['phi'])
+    out['radial_points'] = out['qs'] = qs
+    out['angular_points'] = out['phis'] = phis
+    out['pi_in_q'] = data.get('pi_in_q', True)
+    out['average_intensity'] = np.asarray(a_int)
+    out['xray_wavelength'] = data.get('xray_wavelength', 1.23984)
+    if out['pi_in_q']:
+        thetas = np.arccos(qs * out['xray_wavelength'] / (4 * np.pi))
+    else:
+        thetas = np.arccos(qs * out['xray_wavelength'] / 2)
+    out['thetas'] = thetas
+    out['data_grid'] = {'qs': qs, 'thetas': thetas, 'phis': phis}
+    out['dimensions'] = dimensions
+    return out
 
 
 def _h5py():
