@@ -11,10 +11,15 @@ PRTF variants, centred average), and this restatement reproduces it; so do fixtu
 built on THIS file (tests/golden/make_golden.py ``install_pysofft_double``), so their grid / sign / normalisation conventions
 are those restated below from the published definitions the plugin quotes (soft_plugin.py:64-99): ``C(R) = <f, g o R>`` on the
 (2 bw)^3 Euler grid (``alpha_j = 2 pi j / 2bw``, ``beta_k = pi (2k+1) / 4bw``, ``gamma_j`` like alpha, bw = L + 1) and
-``f_lm -> sum_n D^l_nm f_ln``, ZYZ convention ``D^l_mn(alpha, beta, gamma) = e^{-i m alpha} d^l_mn(beta) e^{-i n gamma}``, pinned
-by known answers only (a density rotated by a grid rotation is found again, Wigner matrices are unitary and compose).  What the
-reference's averaged density depends on is the *composition* find_rotation -> rotate, which is convention free: the rotation
-that maximises the overlap with the reference is applied.
+``f_lm -> sum_n D^l_mn f_ln``, ZYZ convention ``D^l_mn(alpha, beta, gamma) = e^{-i m alpha} d^l_mn(beta) e^{-i n gamma}``.
+**Pinned to those published definitions** (tests/test_so3_reference.py, references in tests/so3_reference.py that share no code
+with this file): ``wigner_d`` (and the product's ``hostsetup.wigner_d``, the same eigen-decomposition) against the explicit Wigner
+sum at 80 digits, <= 1.2e-14 absolute up to l = 63 (bound 1e-13); ``rotate_coeff`` against ``f(R^-1 x)``, R = Rz Ry Rz, evaluated
+with scipy's spherical harmonics, 1.1e-14 of max|f| at L = 32 (bound 1e-12; ``f(R x)`` misses by O(1)); ``correlation`` against
+``mean_r Re <ref_r, rotate_coeff(sig, R)_r>`` and a longdouble restatement, 2e-15 of max|C|; ``mean_C_layout`` + arg-max against
+the key formula written out.  **Not pinned**: that pysofft's own conventions equal these definitions -- that needs pysofft and
+stays the one-line check of INTEGRATION.md section 6.  What the reference's averaged density depends on is the *composition*
+find_rotation -> rotate, which is convention free: the rotation that maximises the overlap with the reference is applied.
 
 One behaviour of the reference is kept literally because its results depend on it: ``find_rotation`` edits the Euler-angle grid
 IN PLACE (average.py:938-940: the grid entry it reads is a view, ``alpha -> 2 pi - alpha``, ``gamma -> 2 pi - gamma``), so a grid
@@ -86,8 +91,8 @@ def correlation(ref, sig, L, r_limit_ids=None):
         S[:, L - l:L + l + 1, L - l:L + l + 1] += T[None] * d
     Ea = np.exp(-1j * al[:, None] * m_all[None, :])          # (alpha, m)
     Eg = np.exp(-1j * ga[:, None] * m_all[None, :])          # (gamma, n)
-    C = np.einsum('am,bmn,gn->abg', Ea, S, Eg)
-    return C.real
+    P = S @ Eg.T                                             # (beta, m, gamma): two matrix products, 70 x the einsum at L = 32
+    return np.ascontiguousarray((Ea[None] @ P).real.transpose(1, 0, 2))
 
 
 def find_rotation(ref, sig, L, r_limit_ids=None):
@@ -174,14 +179,19 @@ def normalize_density(d, d_min=False):
     return (d - d_min) / (np.max(d.real) - d_min)
 
 
-def PRTF(a1, a2, b1, b2):
-    """resolution_metrics.py:62-78"""
-    axes = tuple(range(1, a1.ndim))
+def prtf_points(a1, a2, b1, b2):
+    """resolution_metrics.py:62-76: the quantity whose shell mean is the PRTF, point by point"""
     nd = np.ones(a1.shape, dtype=complex)
     nz = (b1 != 0) & (b2 != 0)
     nd[nz] = (a1[nz] * a2[nz].conj()) / (b1[nz] * b2[nz].conj())
     nd[~nz & (a1 != 0) & (a2 != 0)] = 0
-    nd = np.sqrt(nd)
+    return np.sqrt(nd)
+
+
+def PRTF(a1, a2, b1, b2):
+    """resolution_metrics.py:62-78"""
+    axes = tuple(range(1, a1.ndim))
+    nd = prtf_points(a1, a2, b1, b2)
     return np.average(nd, axis=axes), np.std(nd, axis=axes)
 
 

@@ -1176,17 +1176,21 @@ def check_variant_golden(g, v, name, lib_path=None, use_oracle=False, n_restarts
 
 
 # ---- alignment + averaging of reconstructions ----------------------------------------------------
-def check_average_vs_oracle(lib_path=None, N=12, L=6, n_rec=5, seed=3):
+def check_average_vs_oracle(lib_path=None, N=12, L=6, n_rec=5, seed=3, n_batch=2, timings=None):
     """xframe/projects/fxs/average.py run_3d on synthetic reconstructions: one band-limited real density, rotated by
     different rotations of the Euler grid (one copy point-inverted, all with a little noise and different scales and
     centres), has to come back aligned.  The HIP path (transforms, SO(3) correlation and coefficient rotation on the
     device) against the oracle restatement: alignment errors, Euler angles, the inversion decisions, the averaged density
-    and the PRTF; and the size-independent property that the aligned copies agree with the reference."""
+    and the PRTF; and the size-independent property that the aligned copies agree with the reference.
+    n_batch: restarts of the engine, i.e. the chunk the signals are aligned in; timings: a dict that receives the wall time of the
+    oracle half ('oracle') and of everything else ('device'), in seconds."""
+    import time
     from oracle import alignment as OA
     from xframe_amd.fxs import average as AV
     from xframe_amd.fxs import hostsetup as hs
     max_q = float(np.max(S.midpoint_points(S.data_cutoff(N), N)))
-    e = Engine({'grid': {'n_radial_points': N, 'max_order': L}}, None, n_batch=2, lib_path=lib_path, max_q=max_q)
+    t_start = time.perf_counter()
+    e = Engine({'grid': {'n_radial_points': N, 'max_order': L}}, None, n_batch=n_batch, lib_path=lib_path, max_q=max_q)
     fp = FourierPair(SHT(L), N, max_q, 2.0)
     sht = fp.sht
     rng = np.random.default_rng(seed)
@@ -1210,12 +1214,16 @@ def check_average_vs_oracle(lib_path=None, N=12, L=6, n_rec=5, seed=3):
                 d = fp.ift(fp.ft(d).conj())                          # point inverse
             d = (1.0 + 0.3 * i) * d + 1e-5 * rng.normal(size=d.shape)
             recs.append((d, fp.ft(d)))
-            errs.append(0.01 * (1 + ((i + 2) % n_rec)))
+            errs.append(0.01 * (1 + ((i + n_rec - 3) % n_rec)))       # lowest at copy 3, whatever n_rec (n_rec = 5: (i + 2) % 5)
         return recs, errs
 
     recs, errs = make(False)
     opt = {'alignment_error_limit': 0.5, 'find_rotation': {'r_limit_ids': [0, N]}}
+    t_oracle = time.perf_counter()
     ref = OA.average_reconstructions(fp, recs, errs, opt)
+    t_oracle = time.perf_counter() - t_oracle
+    if timings is not None:
+        timings['oracle'] = t_oracle
     got = AV.average_reconstructions(e, recs, errs, opt)
     assert got['reference_arg'] == ref['reference_arg']
     assert np.allclose(got['alignment_errors'], ref['alignment_errors'], rtol=1e-6, atol=1e-12)
@@ -1240,6 +1248,8 @@ def check_average_vs_oracle(lib_path=None, N=12, L=6, n_rec=5, seed=3):
     assert got['inverted'] == inv_expected
     assert got['n_averaged'] == n_rec - 1                           # the reference's selection quirk drops the last valid alignment
     e.close()
+    if timings is not None:
+        timings['device'] = time.perf_counter() - t_start - t_oracle
     return got
 
 

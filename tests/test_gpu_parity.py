@@ -225,6 +225,20 @@ def test_average_vs_oracle(N, L):
     PC.check_average_vs_oracle(None, N=N, L=L)
 
 
+@pytest.mark.parametrize('n_batch', [8, 3])
+def test_average_vs_oracle_reported_size(n_batch):
+    """the same check at the size the README reports a time for (8 reconstructions at 128 x L32, scripts/bench_average.py): Euler
+    grid 66^3, grids of 1 048 576 points; n_batch = 8 is what the script times, n_batch = 3 aligns the signals in chunks of 3 with a
+    padded last chunk (_batched, apply_to, rotate).  Budget in the style of the shadow tests: twice the oracle half plus the rest,
+    as measured on the test machine (one MI355X, 16 CPU threads): oracle half 6.3 s, the rest 4.0 s (n_batch = 8) and 3.4 s
+    (n_batch = 3) -- 2 x 6.3 + 4.0 = 17 s.  (The rest is mostly host work too: building the second set of copies with the oracle's
+    transforms.)"""
+    t = {}
+    PC.check_average_vs_oracle(None, N=128, L=32, n_rec=8, n_batch=n_batch, timings=t)
+    print('average flow 128 x L32, 8 reconstructions, n_batch = %d: oracle half %.1f s, the rest %.1f s' % (n_batch, t['oracle'], t['device']))
+    assert t['oracle'] + t['device'] < 17
+
+
 def test_average_flow_golden(golden_flow):
     """the product's averaging against what the reference's own ProjectWorker.run_3d / Alignment did with two seeded sets of
     reconstructions (fixture G17, tests/golden/average_flow.npz): decisions, aligned pairs, averages, PRTF variants"""

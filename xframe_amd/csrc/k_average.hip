@@ -16,6 +16,9 @@
 // ---- moments, integrals and extrema of n grids (partials per workgroup, then a fixed-order reduction: reproducible) ----------
 // per grid: [0] sum w Re, [1..3] sum w Re {x, y, z}, [4] sum w Re^2, [5] sum w (Re - Re ref)^2, [6] max Re, [7] min Re,
 // [8], [9] sum of the entries "> 0" in numpy's lexicographic order on complex numbers (Re > 0, or Re == 0 and Im > 0), [10] their count
+// The extrema are numpy's max / min (average.py:432, 721-727): a NaN in the grid is returned, where fmax / fmin would drop it.
+__device__ __forceinline__ double av_max(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
+__device__ __forceinline__ double av_min(double a, double b) { return (a != a || b != b) ? a + b : fmin(a, b); }
 __global__ void __launch_bounds__(AV_THREADS) k_av_stats(const double2* __restrict__ g, const double2* __restrict__ ref,
                                                          const double* __restrict__ wr, const double* __restrict__ wt,
                                                          const double* __restrict__ rs, const double* __restrict__ cost,
@@ -47,8 +50,8 @@ __global__ void __launch_bounds__(AV_THREADS) k_av_stats(const double2* __restri
             const double d = ref[i].x - v.x;
             s[5] = fma(w * d, d, s[5]);
         }
-        s[6] = fmax(s[6], v.x);
-        s[7] = fmin(s[7], v.x);
+        s[6] = av_max(s[6], v.x);
+        s[7] = av_min(s[7], v.x);
         if (v.x > 0.0 || (v.x == 0.0 && v.y > 0.0)) {
             s[8] += v.x;
             s[9] += v.y;
@@ -62,7 +65,7 @@ __global__ void __launch_bounds__(AV_THREADS) k_av_stats(const double2* __restri
         for (int o = AV_THREADS / 2; o > 0; o >>= 1) {
             if ((int)threadIdx.x < o) {
                 const double a = red[threadIdx.x], c2 = red[threadIdx.x + o];
-                red[threadIdx.x] = k == 6 ? fmax(a, c2) : (k == 7 ? fmin(a, c2) : a + c2);
+                red[threadIdx.x] = k == 6 ? av_max(a, c2) : (k == 7 ? av_min(a, c2) : a + c2);
             }
             __syncthreads();
         }
@@ -77,7 +80,7 @@ __global__ void k_av_stats_finish(const double* __restrict__ part, int nblk, dou
     double a = part[(size_t)b * nblk * AV_NSTAT + k];
     for (int i = 1; i < nblk; ++i) {
         const double v = part[((size_t)b * nblk + i) * AV_NSTAT + k];
-        a = k == 6 ? fmax(a, v) : (k == 7 ? fmin(a, v) : a + v);
+        a = k == 6 ? av_max(a, v) : (k == 7 ? av_min(a, v) : a + v);
     }
     out[(size_t)b * AV_NSTAT + k] = a;
 }
@@ -147,7 +150,9 @@ __device__ __forceinline__ double2 prtf_point(double2 a1, double2 a2, double i1,
     if (nz) {
         const double den = b1 * b2;
         const double2 num = cmulc(a1, a2);
-        nd = make_double2(num.x / den, num.y / den);
+        // (numpy divides by b1 conj(b2) as the complex number den + 0i: a zero imaginary part of the quotient comes out as +0,
+        //  so a negative real ratio has the root +i whatever the sign of the zero was)
+        nd = make_double2(num.x / den, num.y == 0.0 ? 0.0 : num.y / den);
     } else if ((a1.x != 0.0 || a1.y != 0.0) && (a2.x != 0.0 || a2.y != 0.0)) {
         nd = make_double2(0.0, 0.0);
     }
