@@ -90,3 +90,24 @@ __device__ __forceinline__ void group_sum4(double& v0, double& v1, double& v2, d
     v3 = dpp_mov<0xFF>(w);
 }
 
+// The same for THREE values, with the two lane predicates handed in (p: lane & 1, p2: lane & 2): v0, v1, v2 come out bit for
+// bit as from group_sum4<16> with a fourth value of zero.  The fourth slot only ever reaches quad lane 3's partial sum, which
+// nobody reads, so the odd lanes need no zero there and form u1 like the even lanes (four selects fewer).  A caller inside a hot
+// loop derives the predicates where it wants them to live (k_projr.hip: once per sweep; as values of the whole kernel they were
+// spilled to lanes and read back in every round).
+__device__ __forceinline__ void group_sum3_sel(double& v0, double& v1, double& v2, bool p, bool p2) {
+    // xor 1: odd lanes keep v2, even lanes keep (v0, v1)
+    const double s0 = p ? v0 : v2;
+    double u0 = p ? v2 : v0;
+    u0 += dpp_mov<0xB1>(s0);
+    const double u1 = v1 + dpp_mov<0xB1>(v1);              // even lanes: as in group_sum4; odd lanes: not used
+    // xor 2, then across the quads: as in group_sum4
+    const double s = p2 ? u0 : u1;
+    double w = p2 ? u1 : u0;
+    w += dpp_mov<0x4E>(s);
+    w += dpp_mov<0x128>(w);
+    w += dpp_mov<0x124>(w);
+    v0 = dpp_mov<0x00>(w);
+    v1 = dpp_mov<0xAA>(w);
+    v2 = dpp_mov<0x55>(w);
+}

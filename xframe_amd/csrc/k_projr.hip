@@ -203,8 +203,9 @@ __device__ __forceinline__ void rp_sweep(double* Xs, double* Vs, int ns, int ks,
 //     access of a round is `ds_read / ds_write base + immediate`, base = column offset from the table + lane;
 //   * rows beyond the matrix are zero and stay zero under rotations: no predicate on the last row slot;
 //   * column 16 NR - 1 is all zero: the groups without a pair in a round "rotate" it with itself (identity, zeros written back);
-//   * the pairing table is translated once per sweep into {resident offset << 2 | write-back << 1 | load, mover offset} (through
-//     the compaction of the deflated columns), flags made self-contained: a resident is written back before an idle round;
+//   * the pairing table is translated once per sweep into {resident offset | load << 31, mover offset | write-back << 31}
+//     (offsets in doubles, through the compaction of the deflated columns; an address is one shift-and-add, which drops the
+//     flag), flags made self-contained: a resident is written back before an idle round;
 //   * a pair that is orthogonal already takes the identity rotation through the same instructions.
 // nc = blocks of 16 columns (= row slots of 16 rows: 2l+2 <= 16 nc); TG = lanes per column pair (16; a 32-lane variant -- twice
 // the waves per round with shorter chains each -- measured 3520 against 2440 ticks per round and was removed in round 4)
@@ -245,21 +246,69 @@ __host__ __device__ __forceinline__ RpLayout rp_layout(int k, int n2, int tg, in
 }
 #define RP_LAYOUT_ERROR 0x7fffffff     // sweeps_out marker: the kernel's layout did not fit the launch's LDS (order skipped)
 
-template <int TG>
-__device__ __forceinline__ void rp_sum3(double& a, double& b, double& g) {
-    static_assert(TG == 16, "16 lanes per column pair (the 32-lane variant measured slower and was removed)");
-    double z = 0.0;
-    group_sum4<16>(a, b, g, z);
+// fast_rsqrt (k_jacobi.h: the same operations in the same order) with the 1.5 of its Newton steps handed in
+__device__ __forceinline__ double rp_rsqrt(double x, double c15) {
+    double y = __builtin_amdgcn_rsq(x);
+    y = y * (c15 - 0.5 * x * y * y);
+    y = y * (c15 - 0.5 * x * y * y);
+    return y;
 }
+
 template <int TG>
 __device__ __forceinline__ double rp_sum1(double v) {
     v = group_sum<16>(v);
     return v;
 }
 
+// LDS addresses of the padded sweep as plain integers (bytes): the device build forms them in 32 bits and dereferences them in
+// the LDS address space, so every access is a ds_read / ds_write whatever the compiler can or cannot infer about the pointer
+// (the host passes -- and the CPU emulation of the test-suite -- use ordinary pointers of the machine's width)
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef unsigned rp_addr_t;
+typedef __attribute__((address_space(3))) double rp_lds_double;
+typedef __attribute__((address_space(3))) const int2 rp_lds_int2;
+__device__ __forceinline__ rp_addr_t rp_lds_addr(const void* p) {
+    return (rp_addr_t)(size_t)(__attribute__((address_space(3))) const void*)p;
+}
+// (the empty statement makes the value one the compiler has to hold in a vector register from here on)
+#define RP_IN_VGPR(x) asm volatile("" : "+v"(x))
+// (... and this one makes `x`, from here on, a value that exists only once `after` does)
+#define RP_THEN(x, after) asm volatile("" : "+v"(x) : "v"(after))
+#else
+typedef uintptr_t rp_addr_t;
+typedef double rp_lds_double;
+typedef const int2 rp_lds_int2;
+__device__ __forceinline__ rp_addr_t rp_lds_addr(const void* p) { return (rp_addr_t)p; }
+#define RP_IN_VGPR(x)
+#define RP_THEN(x, after)
+#endif
+// address of a column: base + 8 * (table entry, a column offset in doubles); flags in the top three bits leave with the shift
+__device__ __forceinline__ rp_addr_t rp_col_addr(rp_addr_t base, int entry) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    rp_addr_t a;
+    asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(a) : "v"(entry), "v"(base));      // (the compiler emits a shift and an add)
+    return a;
+#else
+    return base + ((unsigned)entry << 3);
+#endif
+}
+__device__ __forceinline__ rp_lds_double* rp_lds(rp_addr_t a) { return (rp_lds_double*)a; }
+
+// entry of the per-sweep table: column offsets in doubles; the flags sit in the top bits, which the shift to a byte offset drops
+#define RP_TAB_LOAD (1u << 31)         // .x: a new resident for this group
+#define RP_TAB_WB (1u << 31)           // .y: someone else takes the resident next round
+
+// The round is written for its instruction count (scripts/isa_census.py, profiles/rproj_round_census.txt):
+//   * every predicate is an integer product of comparisons (no short-circuit: `&&` compiled to nested exec-mask regions);
+//   * the constants of a sweep (tabs2, S, early2, JAC_TOL^2, 1.5 of the Newton steps) and the lane predicates of the lane sums
+//     are made vector-register values at the head of the sweep: left to the compiler they are scalars that live across the
+//     whole kernel, and were spilled to lanes and read back (v_readlane) in every round;
+//   * an address is one shift-and-add of a table entry.
+// The arithmetic -- order and association of every floating-point operation -- is that of rp_sweep / rp_params.
 template <int NC, int TG, bool TIMED = false>
-__device__ __forceinline__ void rp_sweep_pad(double* xt /* X~ + lane of the group */, const int2* tab, int n_rounds, int ngroups,
+__device__ __forceinline__ void rp_sweep_pad(double* xt_ /* X~ + lane of the group */, const int2* tab_, int n_rounds, int ngroups,
                                              int group, double tabs2, double S, double early2, bool& big, long long* tacc = nullptr) {
+    static_assert(TG == 16, "16 lanes per column pair");
     constexpr int NR = rp_pad_nrt(NC, TG);
     constexpr int VOFF = rp_pad_voff(NC, TG);
     long long tq = 0;
@@ -269,26 +318,42 @@ __device__ __forceinline__ void rp_sweep_pad(double* xt /* X~ + lane of the grou
         tacc[I] += tn_ - tq;                 \
         tq = tn_;                            \
     }
+    const rp_addr_t xt = rp_lds_addr(xt_);
+    rp_addr_t tp = rp_lds_addr(tab_) + (rp_addr_t)group * sizeof(int2);
+    const rp_addr_t tstep = (rp_addr_t)ngroups * sizeof(int2);
+    double tol2 = JAC_TOL * JAC_TOL, c15 = 1.5;
+    int lane = threadIdx.x;
+    RP_IN_VGPR(tabs2);
+    RP_IN_VGPR(S);
+    RP_IN_VGPR(early2);
+    RP_IN_VGPR(tol2);
+    RP_IN_VGPR(c15);
+    RP_IN_VGPR(lane);
+    const bool p1 = (lane & 1) != 0, p2 = (lane & 2) != 0;
+    bool bigb = false;
     double rx[NR], rv[NR];
 #pragma unroll
     for (int u = 0; u < NR; ++u) {
         rx[u] = 0.0;
         rv[u] = 0.0;
     }
-    int2 e_next = tab[group];
+    int2 e_next = *(rp_lds_int2*)tp;
     if (TIMED) tq = clock64();
     for (int r = 0; r < n_rounds; ++r) {
         const int2 e = e_next;
-        if (r + 1 < n_rounds) e_next = tab[(r + 1) * ngroups + group];     // in flight during the round
-        double* xr = xt + (e.x >> 2);
-        double* xm = xt + e.y;
+        tp += tstep;
+        if (r + 1 < n_rounds) e_next = *(rp_lds_int2*)tp;     // in flight during the round
+        const rp_addr_t ar = rp_col_addr(xt, e.x);
+        const rp_addr_t am = rp_col_addr(xt, e.y);
+        rp_lds_double* xr = rp_lds(ar);
+        rp_lds_double* xm = rp_lds(am);
         double mx[NR], mv[NR];
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
             mx[u] = xm[u * TG];
             mv[u] = xm[VOFF + u * TG];
         }
-        if (e.x & 1) {                                           // a new resident for this group
+        if (e.x < 0) {                                           // a new resident for this group
 #pragma unroll
             for (int u = 0; u < NR; ++u) {
                 rx[u] = xr[u * TG];
@@ -306,35 +371,48 @@ __device__ __forceinline__ void rp_sweep_pad(double* xt /* X~ + lane of the grou
         }
         if (TIMED) asm volatile("" : "+v"(alpha), "+v"(beta), "+v"(g));
         RP_SEG(1)
-        rp_sum3<TG>(alpha, beta, g);
+        group_sum3_sel(alpha, beta, g, p1, p2);
         if (TIMED) asm volatile("" : "+v"(alpha), "+v"(beta), "+v"(g));
         RP_SEG(2)
         // rotation [a b] <- [a b] [[c, w], [-w, c]] (see rp_params), the identity for a pair that is orthogonal already
         const double g2 = g * g, ab = alpha * beta;
-        const bool rot = g2 > (JAC_TOL * JAC_TOL) * ab && g2 > tabs2 * fmax(alpha, beta) * S && g2 > 0.0;
-        big = big || (rot && g2 > early2 * ab);
+        const bool rot = bool(int(g2 > tol2 * ab) & int(g2 > tabs2 * fmax(alpha, beta) * S) & int(g2 > 0.0));
+        bigb = bool(int(bigb) | (int(rot) & int(g2 > early2 * ab)));
         const double d = 0.5 * (beta - alpha);
         const double h2 = fma(d, d, g2);
-        const double ih = fast_rsqrt(rot ? h2 : 1.0);
+        const double ih = rp_rsqrt(rot ? h2 : 1.0, c15);
         const double c2 = fma(0.5 * fabs(d), ih, 0.5);
-        const double rc = fast_rsqrt(c2);
+        const double rc = rp_rsqrt(c2, c15);
         const double cs = rot ? c2 * rc : 1.0;
         const double w = rot ? ((d >= 0.0 ? 0.5 : -0.5) * ih * rc) * g : 0.0;
         if (TIMED) asm volatile("" : "+v"(mx[0]) : "v"(cs), "v"(w));
         RP_SEG(3)
+        // (the mover's new value first, then the resident's in place of the old one: RP_THEN keeps the compiler from starting
+        // the second before the first is done, which cost a register copy per row slot and round)
+        double bn[NR];
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
-            const double a = rx[u], bq = mx[u];
-            rx[u] = fma(-w, bq, cs * a);
-            xm[u * TG] = fma(w, a, cs * bq);
+            bn[u] = fma(w, rx[u], cs * mx[u]);
+            xm[u * TG] = bn[u];
         }
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
-            const double a = rv[u], bq = mv[u];
-            rv[u] = fma(-w, bq, cs * a);
-            xm[VOFF + u * TG] = fma(w, a, cs * bq);
+            double a = rx[u];
+            RP_THEN(a, bn[u]);
+            rx[u] = fma(-w, mx[u], cs * a);
         }
-        if (e.x & 2) {                                           // someone else takes the resident next round
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            bn[u] = fma(w, rv[u], cs * mv[u]);
+            xm[VOFF + u * TG] = bn[u];
+        }
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            double a = rv[u];
+            RP_THEN(a, bn[u]);
+            rv[u] = fma(-w, mv[u], cs * a);
+        }
+        if (e.y < 0) {                                           // someone else takes the resident next round
 #pragma unroll
             for (int u = 0; u < NR; ++u) {
                 xr[u * TG] = rx[u];
@@ -349,6 +427,7 @@ __device__ __forceinline__ void rp_sweep_pad(double* xt /* X~ + lane of the grou
         __syncthreads();
         RP_SEG(6)
     }
+    big = big || bigb;
 #undef RP_SEG
 }
 
@@ -383,9 +462,13 @@ enum { RP_SOLVE = 0, RP_ZERO = 1, RP_L0 = 2 };
 // loads (a `cond ? load : 0` compiles to an exec-masked block with a full wait at its join): rows and columns outside the
 // matrices are clamped by the caller -- they only reach outputs that are never stored -- and the inner indices beyond K are
 // clamped to K - 1 and multiplied by zero.
-template <int T, int UNR>
-__device__ __forceinline__ void rp_tiles(v4f64 (&acc)[T], const double* const (&pa)[T], int sa, const double* const (&pb)[T], int sb,
-                                         int K, int lk, int nu) {
+// NU: the number of tiles this wave has, a compile-time constant here (rp_tiles below dispatches on the scalar count once per
+// product).  As a run-time bound it put a scalar branch around every tile of every request and every multiply -- about 125
+// branches and, from the values merged behind them, 128 register copies in an iteration of the chunk loop that holds 16 MFMAs.
+template <int T, int UNR, int NU>
+__device__ __forceinline__ void rp_tiles_n(v4f64 (&acc)[T], const double* const (&pa)[T], int sa, const double* const (&pb)[T], int sb,
+                                           int K, int lk) {
+    constexpr int nu = NU;
 #pragma unroll
     for (int u = 0; u < T; ++u) acc[u] = v4f64{0.0, 0.0, 0.0, 0.0};
     // two register sets: the operands of the next chunk are requested before the current chunk is multiplied (the two waves of a
@@ -444,6 +527,22 @@ __device__ __forceinline__ void rp_tiles(v4f64 (&acc)[T], const double* const (&
         multiply(a0, b0);
         if (ch + 2 < n_chunks) request(a0, b0);
         if (ch + 1 < n_chunks) multiply(a1, b1);
+    }
+}
+template <int T, int UNR>
+__device__ __forceinline__ void rp_tiles(v4f64 (&acc)[T], const double* const (&pa)[T], int sa, const double* const (&pb)[T], int sb,
+                                         int K, int lk, int nu /* the same for the whole wave */) {
+    static_assert(T <= RP_ACC_MAX && RP_ACC_MAX == 5, "one case per tile count");
+    switch (nu) {
+    case 1: rp_tiles_n<T, UNR, 1>(acc, pa, sa, pb, sb, K, lk); break;
+    case 2: rp_tiles_n<T, UNR, (T >= 2 ? 2 : T)>(acc, pa, sa, pb, sb, K, lk); break;
+    case 3: rp_tiles_n<T, UNR, (T >= 3 ? 3 : T)>(acc, pa, sa, pb, sb, K, lk); break;
+    case 4: rp_tiles_n<T, UNR, (T >= 4 ? 4 : T)>(acc, pa, sa, pb, sb, K, lk); break;
+    case 5: rp_tiles_n<T, UNR, (T >= 5 ? 5 : T)>(acc, pa, sa, pb, sb, K, lk); break;
+    default:
+#pragma unroll
+        for (int u = 0; u < T; ++u) acc[u] = v4f64{0.0, 0.0, 0.0, 0.0};
+        break;
     }
 }
 
@@ -653,17 +752,17 @@ __device__ __forceinline__ void rp_solve(const RProjArgs& A, int b, int l, RpSha
                     for (int e = tid; e < nrd * ngroups; e += nthreads) {
                         const int r = e / ngroups, gq = e - r * ngroups;
                         const int raw = gq < ps ? s_tab[r * ps + gq] : 0;
-                        int x = (dummy << 2) | 1, y = dummy;
+                        unsigned x = (unsigned)dummy | RP_TAB_LOAD, y = (unsigned)dummy;
                         if (raw & JS_ACTIVE) {
                             const int prev = r > 0 ? s_tab[(r - 1) * ps + gq] : 0;
                             const int next = r + 1 < nrd ? s_tab[(r + 1) * ps + gq] : 0;
                             // a resident stays in registers only from one active round to the next one with the same resident
-                            const int load = (!(prev & JS_ACTIVE) || (prev & JS_WB) || (prev & 255) != (raw & 255)) ? 1 : 0;
-                            const int wb = ((raw & JS_WB) || !(next & JS_ACTIVE)) ? 2 : 0;
-                            x = ((sh.perm[raw & 255] * ns) << 2) | wb | load;
-                            y = sh.perm[(raw >> 8) & 255] * ns;
+                            const unsigned load = (!(prev & JS_ACTIVE) || (prev & JS_WB) || (prev & 255) != (raw & 255)) ? RP_TAB_LOAD : 0u;
+                            const unsigned wb = ((raw & JS_WB) || !(next & JS_ACTIVE)) ? RP_TAB_WB : 0u;
+                            x = (unsigned)(sh.perm[raw & 255] * ns) | load;
+                            y = (unsigned)(sh.perm[(raw >> 8) & 255] * ns) | wb;
                         }
-                        s_tab2[e] = make_int2(x, y);
+                        s_tab2[e] = make_int2((int)x, (int)y);
                     }
                     __syncthreads();
                     double* xt = Xs + t;
