@@ -185,6 +185,18 @@ def test_invariant_metrics_vs_oracle(emul_lib, golden_mtip16, fused):
     PC.check_invariant_metrics_vs_oracle(golden_mtip16, emul_lib, fused)
 
 
+def test_invariant_metrics_vs_oracle_five_restarts(emul_lib):
+    """the same at 24 x L10 on seeded invariants with 5 restarts: the history row II (B) | ccd (B) | fqc (B, N) with more restarts
+    than one chunk of k_metric_fqc, and k_metric_rl2_shell in two trips over the 16 x 32 points of a shell"""
+    PC.check_invariant_metrics_vs_oracle(None, emul_lib, True, synthetic=(24, 10), n_restarts=5)
+
+
+def test_invariant_metrics_vs_oracle_ragged_angular_grid(emul_lib):
+    """12 x L6 on a 20 x 32 angular grid: 640 points, a ragged third trip of k_metric_rl2_shell, and no pairing of the blocks of 256
+    points by the Friedel symmetry of |F| (see the check)"""
+    PC.check_invariant_metrics_vs_oracle(None, emul_lib, True, synthetic=(12, 6), n_theta=20, n_phi=32)
+
+
 @pytest.mark.parametrize('cat,name', [('real', 'support_size'), ('reciprocal', 'no_such_metric')])
 def test_unknown_error_metrics_are_rejected(emul_lib, golden_mtip16, cat, name):
     """a metric this build does not record raises instead of being dropped silently: `support_size` (fxs_IO_methods.py:685-688 raises

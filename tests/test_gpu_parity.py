@@ -257,6 +257,23 @@ def test_invariant_metrics_vs_oracle(golden_mtip16, fused):
     PC.check_invariant_metrics_vs_oracle(golden_mtip16, None, fused)
 
 
+@pytest.mark.parametrize('fused', [True, False])
+@pytest.mark.parametrize('N,L,n_restarts', [(24, 10, 5), (64, 16, 2)])
+def test_invariant_metrics_vs_oracle_synthetic(N, L, n_restarts, fused):
+    """the same on seeded invariants beyond 16 x L4, with the reciprocal l2_projection_diff and deg2_invariant_l2_diff next to them:
+    24 x L10 with 5 restarts (the history row II (B) | ccd (B) | fqc (B, N) with more restarts than one chunk of k_metric_fqc) and
+    64 x L16 with 2 (the chained kernels' grid; k_metric_rl2_shell makes several trips over the 32 x 64 points of a shell).  The
+    loop's fqc_error is NaN by construction in 3-D and asserted to be; its values are pinned in tests/test_gpu_metrics.py"""
+    PC.check_invariant_metrics_vs_oracle(None, None, fused, synthetic=(N, L), n_restarts=n_restarts)
+
+
+@pytest.mark.parametrize('fused', [True, False])
+def test_invariant_metrics_vs_oracle_ragged_angular_grid(fused):
+    """12 x L6 on a 20 x 32 angular grid: 640 points, a ragged third trip of k_metric_rl2_shell, and no pairing of the blocks of 256
+    points by the Friedel symmetry of |F| (on the power-of-two grids above, a sum over every second block is exactly half the full one)"""
+    PC.check_invariant_metrics_vs_oracle(None, None, fused, synthetic=(12, 6), n_theta=20, n_phi=32)
+
+
 def test_polar2d_golden(golden_polar2d):
     """the 2-D (polar) operators -- circular harmonic transforms, polar Hankel pair, Fourier pair, reciprocal projection -- against
     the reference's own functions (fixture G18, tests/golden/polar2d_ops.npz)"""

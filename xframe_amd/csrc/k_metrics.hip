@@ -234,10 +234,15 @@ int launch_reciprocal_l2_metric(mtip_ctx* c, const double2* F, const double2* Fp
     return MTIP_OK;
 }
 
-void free_invariant_metrics(mtip_ctx* c) {
+static void free_reciprocal_l2_metric(mtip_ctx* c) {
     for (void* p : {(void*)c->d_rl2_wr, (void*)c->d_rl2_wt, (void*)c->d_rl2_part, (void*)c->d_rl2_hist})
         if (p) (void)hipFree(p);
     c->d_rl2_wr = nullptr; c->d_rl2_wt = nullptr; c->d_rl2_part = nullptr; c->d_rl2_hist = nullptr;
+}
+
+// the tables, scratch and history of II_error / ccd_diff / fqc_error alone (the reciprocal l2_projection_diff is armed on its own:
+// re-arming these must leave it on)
+static void free_invariant_tables(mtip_ctx* c) {
     if (c->d_im_part) (void)hipFree(c->d_im_part);
     if (c->d_im_fq) (void)hipFree(c->d_im_fq);
     c->d_im_part = nullptr;
@@ -248,6 +253,11 @@ void free_invariant_metrics(mtip_ctx* c) {
     c->d_im_zmask = nullptr; c->d_im_IIref = nullptr; c->d_im_qq = nullptr; c->d_im_ccdT = nullptr; c->d_im_ccdref = nullptr;
     c->d_im_P = nullptr; c->d_im_refavg = nullptr; c->d_im_refw = nullptr; c->d_im_hist = nullptr;
     c->im_which = 0;
+}
+
+void free_invariant_metrics(mtip_ctx* c) {                 // everything this file allocates (mtip_destroy)
+    free_reciprocal_l2_metric(c);
+    free_invariant_tables(c);
 }
 
 // per step: B_l of the current coefficients, then the enabled metrics into the step's row of the history
@@ -302,7 +312,7 @@ int mtip_set_invariant_metrics(mtip_ctx* c, uint32_t which, const uint8_t* zero_
     if (!c) return MTIP_EINVAL;
     (void)hipSetDevice(c->device);
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    free_invariant_metrics(c);
+    free_invariant_tables(c);
     if (which == 0) return MTIP_OK;
     if (which > 7 || !zero_mask || ((which & 1) && (!II_reference || !qq)) || ((which & 2) && (!ccd_weights || !ccd_reference || !(ccd_norm != 0.0))) ||
         ((which & 4) && (!fqc_P || !fqc_reference_average || !fqc_reference_weights))) {
@@ -362,9 +372,7 @@ int mtip_fetch_invariant_metrics(mtip_ctx* c, int64_t first, int64_t n, double* 
 int mtip_set_reciprocal_l2_metric(mtip_ctx* c, const double* radial_w, const double* theta_w) {
     if (!c) return MTIP_EINVAL;
     (void)hipSetDevice(c->device);
-    for (void* p : {(void*)c->d_rl2_wr, (void*)c->d_rl2_wt, (void*)c->d_rl2_part, (void*)c->d_rl2_hist})
-        if (p) (void)hipFree(p);
-    c->d_rl2_wr = nullptr; c->d_rl2_wt = nullptr; c->d_rl2_part = nullptr; c->d_rl2_hist = nullptr;
+    free_reciprocal_l2_metric(c);
     if (!radial_w || !theta_w) return MTIP_OK;
     MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_rl2_wr, c->N * sizeof(double)));
     MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_rl2_wt, c->nt * sizeof(double)));
