@@ -206,6 +206,12 @@ int mtip_op_sht_inverse(mtip_ctx* ctx, const mtip_cdouble* coeff, mtip_cdouble* 
  * transforms one after the other. */
 int mtip_op_sht_inverse_forward(mtip_ctx* ctx, const mtip_cdouble* coeff, mtip_cdouble* grid, mtip_cdouble* coeff_out, int prologue);
 int mtip_op_hankel(mtip_ctx* ctx, const mtip_cdouble* coeff_in, mtip_cdouble* coeff_out, int inverse);
+/* the difference variant of the Hankel step, through the launcher the one-pass ft_stab step uses (csrc/k_hankel.hip, SUB):
+ * coeff_out = H(coeff_in - coeff_sub) above output shell 0 and H(coeff_in) on shell 0, for the restarts whose byte of sub_mask
+ * (n_batch bytes) is non-zero; the others get H(coeff_in).  sub_mask NULL: every restart subtracts.  MTIP_ESTATE when the
+ * Hankel kernel in use has no difference variant. */
+int mtip_op_hankel_difference(mtip_ctx* ctx, const mtip_cdouble* coeff_in, const mtip_cdouble* coeff_sub, mtip_cdouble* coeff_out,
+                              int inverse, const uint8_t* sub_mask);
 int mtip_op_fourier_transform(mtip_ctx* ctx, const mtip_cdouble* grid_in, mtip_cdouble* grid_out, int inverse);
 /* approximate_unknowns + mtip_projection (fxs_Projections.py:752-767, 832-872) on 'direct' coefficients */
 int mtip_op_project_coefficients(mtip_ctx* ctx, const mtip_cdouble* Ilm, mtip_cdouble* Ilm_projected);
@@ -421,6 +427,10 @@ int mtip_debug_jacobi_sweeps(mtip_ctx* ctx, int32_t* out);
  * epilogue + forward phase 1 done, barrier, forward phase 2 done, barrier; [16] Legendre sums done, [17] end.  The first call
  * switches the stamps on (out may be null). */
 int mtip_debug_chain_timing(mtip_ctx* ctx, int64_t* out);
+/* diagnostic: the launch plan of the Hankel kernel (build_hankel_tiles, csrc/k_hankel.hip): ct = 16-column MFMA tiles per
+ * workgroup (1, 2, 3 or 5: the instantiation that runs), n_tiles = column tiles (grid x), n_row_blocks = blocks of 128 output
+ * shells (grid y).  Any of the three may be NULL. */
+int mtip_debug_hankel_tiles(mtip_ctx* ctx, int* ct, int* n_tiles, int* n_row_blocks);
 /* diagnostic: workgroups per restart of the real projection kernel (k_rproj: the host-packed slots of orders), 0 before the
  * first projection or when the general complex kernels are in use; negative = error code */
 int mtip_debug_projection_slots(mtip_ctx* ctx);

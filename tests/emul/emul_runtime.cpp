@@ -3,6 +3,7 @@
 // ucontext fibers scheduled round-robin, yielding at barriers and wave collectives.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <map>
 #include <string>
 #include <sys/mman.h>
 #include <ucontext.h>
@@ -254,6 +255,46 @@ void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& bod
         for (int i = 0; i < nw; ++i) ts.emplace_back(work, i);
         for (auto& t : ts) t.join();
     }
+}
+}  // namespace emul
+
+// MTIP_EMUL_GUARD=1 (read once per process): every "device" allocation ends at an inaccessible page, so a kernel that loads or
+// stores past the end of a buffer faults on the spot instead of touching its neighbour; such a load is invisible in the results
+// where the value only feeds rows that are never stored.  tests/test_emul_hankel.py runs cases this way in a child process.
+// Sizes are rounded up to 8 bytes only, so an array of doubles ends exactly at the page.  Off: plain calloc.
+namespace emul {
+static std::mutex guard_mutex;
+static std::map<void*, std::pair<void*, size_t>> guard_blocks;
+
+static bool guard_on() {
+    static const bool on = [] { const char* e = std::getenv("MTIP_EMUL_GUARD"); return e != nullptr && std::atoi(e) != 0; }();
+    return on;
+}
+
+void* device_alloc(size_t n) {
+    if (!guard_on()) return std::calloc(1, n ? n : 1);
+    const size_t page = 4096, len = (std::max<size_t>(n, 1) + 7) & ~size_t(7), body = (len + page - 1) / page * page;
+    char* base = (char*)mmap(nullptr, body + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+    if (base == MAP_FAILED) return nullptr;
+    if (mprotect(base + body, page, PROT_NONE) != 0) { munmap(base, body + page); return nullptr; }
+    void* p = base + body - len;
+    std::lock_guard<std::mutex> guard(guard_mutex);
+    guard_blocks[p] = {base, body + page};
+    return p;
+}
+
+void device_free(void* p) {
+    if (p == nullptr) return;
+    {
+        std::lock_guard<std::mutex> guard(guard_mutex);
+        auto it = guard_blocks.find(p);
+        if (it != guard_blocks.end()) {
+            munmap(it->second.first, it->second.second);
+            guard_blocks.erase(it);
+            return;
+        }
+    }
+    std::free(p);
 }
 }  // namespace emul
 

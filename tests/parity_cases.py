@@ -6,6 +6,7 @@ Tolerances (SURVEY section 8 d / BASELINE.md section 5, fp64 end to end):
   per operator rel-L2 <= 1e-12 (Hankel, elementwise, GEMMs), <= 1e-10 (SHT; polar factor via V_l U_l),
   one full step <= 1e-9, 20-step trajectory <= 1e-6.
 """
+import copy
 import ctypes
 import os
 
@@ -190,12 +191,14 @@ def check_operators_golden(golden_ops, lib_path):
     e.close()
 
 
-def check_steps_golden(golden_mtip16, lib_path, fused):
-    """G10: single HIO / ER (+ft_stab) steps and one SW update from a stored state, vs the reference's sketches."""
+def check_steps_golden(golden_mtip16, lib_path, fused, hankel_ct=None):
+    """G10: single HIO / ER (+ft_stab) steps and one SW update from a stored state, vs the reference's sketches.
+    hankel_ct: the Hankel tile width the caller forced (MTIP_HANKEL_CT), asserted to be the planned one."""
     g = golden_mtip16
     extra = {'main_loop': {'error': {'methods': {'reciprocal': {
         'calculate': ['deg2_invariant_l2_diff'], 'deg2_invariant_l2_diff': {'order': 2}}}}}}
     e, om, opt, data = _engine_and_oracle(g, lib_path, fused=fused, extra=extra)
+    assert hankel_ct is None or e.hankel_tiles()[0] == hankel_ct, e.hankel_tiles()
     for enforce in (True, False):
         for meth in ('HIO', 'ER', 'HIO_ft_stab', 'ER_ft_stab'):
             e.set_density(0, g['rho0'])
@@ -295,10 +298,14 @@ def check_short_trajectory_vs_oracle(g, lib_path, fused, n_hio=3, n_er=2, n_rest
     m.engine.close()
 
 
-def check_ft_stab_disagreement(g, lib_path=None):
-    """3-D loop, two restarts of ONE engine that disagree on `ft_stab: link_to_enforce_initial_support` (one has its initial support
-    enforced by the shrink-wrap, the other not -- the reference decides per reconstruction process, reconstruct.py:836-850): the
-    engine takes ft_stab per restart (mtip_set_ft_stab_mask) and each restart follows the oracle's own run of it"""
+_FT_STAB_DISAGREEMENT = {}
+
+
+def _ft_stab_disagreement_problem(g):
+    """settings, data, the two initial densities and the oracle's run of each (computed once per fixture: the oracle does not
+    depend on the device's kernel choice)"""
+    if id(g) in _FT_STAB_DISAGREEMENT:
+        return _FT_STAB_DISAGREEMENT[id(g)][1]
     N, L = int(g['N']), int(g['L'])
     data = data_from_golden(g, L)
     link = {'ft_stab': 'link_to_enforce_initial_support', 'link_to_enforce_initial_support': {'delay': 1}}
@@ -313,9 +320,21 @@ def check_ft_stab_disagreement(g, lib_path=None):
     eis = opt['projections']['real']['projections']['support']['enforce_initial_support']
     eis['apply'], eis['if_error_bigger_than'] = True, float(np.sqrt(e3[0] * e3[1]))
     refs = [OM.MTIP(opt, data).phasing_loop(rho0=r) for r in (rho_a, rho_b)]
+    _FT_STAB_DISAGREEMENT[id(g)] = (g, (opt, data, rho_a, rho_b, refs))          # (g kept alive: its id stays its own)
+    return _FT_STAB_DISAGREEMENT[id(g)][1]
+
+
+def check_ft_stab_disagreement(g, lib_path=None, hankel_ct=None):
+    """3-D loop, two restarts of ONE engine that disagree on `ft_stab: link_to_enforce_initial_support` (one has its initial support
+    enforced by the shrink-wrap, the other not -- the reference decides per reconstruction process, reconstruct.py:836-850): the
+    engine takes ft_stab per restart (mtip_set_ft_stab_mask) and each restart follows the oracle's own run of it.
+    hankel_ct: the Hankel tile width the caller forced (MTIP_HANKEL_CT), asserted to be the planned one."""
+    opt, data, rho_a, rho_b, refs = _ft_stab_disagreement_problem(g)
+    opt = copy.deepcopy(opt)
     R.MTIP.preinit(opt, data)
     m = R.MTIP(n_restarts=2, initial_densities=[rho_a, rho_b], lib_path=lib_path, fused=True)
     m.generate_phasing_loop()
+    assert hankel_ct is None or m.engine.hankel_tiles()[0] == hankel_ct, m.engine.hankel_tiles()
     seen = []
     orig = m.engine.run
 

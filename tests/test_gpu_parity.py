@@ -50,6 +50,13 @@ def test_single_steps_golden(golden_mtip16, fused):
     PC.check_steps_golden(golden_mtip16, None, fused)
 
 
+@pytest.mark.parametrize('ct', [1, 2, 3, 5])
+def test_single_steps_golden_hankel_width(golden_mtip16, monkeypatch, ct):
+    """the fused single steps (ft_stab: the difference variant of the Hankel kernel) with every tile width forced"""
+    monkeypatch.setenv('MTIP_HANKEL_CT', str(ct))
+    PC.check_steps_golden(golden_mtip16, None, True, hankel_ct=ct)
+
+
 @pytest.mark.parametrize('fused', [False, True])
 def test_short_trajectory_vs_oracle(golden_mtip16, fused):
     PC.check_short_trajectory_vs_oracle(golden_mtip16, None, fused)
@@ -180,6 +187,14 @@ def test_config3_short_trajectory_vs_oracle():
 def test_ft_stab_disagreement(golden_mtip16):
     """restarts of one engine that disagree on the ft_stab link: ft_stab per restart, each follows the oracle's run of it"""
     PC.check_ft_stab_disagreement(golden_mtip16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('ct', [1, 2, 3, 5])
+def test_ft_stab_disagreement_hankel_width(golden_mtip16, monkeypatch, ct):
+    """the same under every tile width of the Hankel kernel: the per-restart mask reaches its difference variant"""
+    monkeypatch.setenv('MTIP_HANKEL_CT', str(ct))
+    PC.check_ft_stab_disagreement(golden_mtip16, hankel_ct=ct)
 
 
 @pytest.mark.gpu

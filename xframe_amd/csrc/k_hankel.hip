@@ -40,8 +40,8 @@ void launch_coeff_diff(mtip_ctx* c, const double2* a, const double2* b, double2*
 // ---- workgroup-tiled variant ---------------------------------------------------------------------------------
 // (rounds 1-2 had one 16-column tile per WAVE, fragments straight from L2: the panel was re-read once per row group and W_l once per column tile, PMC 3.3 x the algorithmic
 // bytes), and what bounds these kernels is the rate at which a CU can pull bytes when every CU pulls (~11 B/clk,
-// L2 hits included).  Here a 512-thread workgroup owns 80 columns x all (<= 128) output shells of one order -- 218
-// workgroups at 8 restarts, L = 32: one per CU, all resident, W_l read once per 80 columns and the panel once.  Per
+// L2 hits included).  Here a 512-thread workgroup owns 80 columns x all (<= 128) output shells of one order -- 231
+// workgroups at 8 restarts, L = 32: about one per CU, all resident, W_l read once per 80 columns and the panel once.  Per
 // chunk of 16 input shells W_l[16][Nq] and the panel [16][80] are staged in LDS with coalesced loads (operands of the
 // next two chunks in flight in registers); wave w multiplies row tile w with the five column tiles (one A and five B
 // fragments from LDS per k-step).  LDS row strides = 16 doubles mod 32, so the two input shells a half-wave reads
@@ -197,9 +197,11 @@ __global__ void __launch_bounds__(HT_THREADS) k_hankel_tile(const double* __rest
 
 bool hankel_has_difference(const mtip_ctx* c) { return c->d_htiles32 != nullptr; }
 
+int hankel_row_blocks(const mtip_ctx* c) { return div_up(c->N, HT_ROWS); }
+
 // out = H(in - in_sub) above output shell 0, H(in) on it (in_sub == nullptr: plain transform)
 void launch_hankel_mfma_sub(mtip_ctx* c, const double2* in, const double2* in_sub, double2* out, int inverse, const uint8_t* sub_mask) {
-    const dim3 grid((unsigned)c->n_htiles32, (unsigned)div_up(c->N, HT_ROWS));
+    const dim3 grid((unsigned)c->n_htiles32, (unsigned)hankel_row_blocks(c));
 #define HT_LAUNCH(CT, SUBF)                                                                                                  \
     hipLaunchKernelGGL((k_hankel_tile<CT, SUBF>), grid, dim3(HT_THREADS), 0, c->stream, reinterpret_cast<const double*>(in), \
                        reinterpret_cast<double*>(out), (const double*)c->d_W, (const HankelTile32*)c->d_htiles32, c->N,      \
@@ -238,7 +240,7 @@ int build_hankel_tiles(mtip_ctx* c) {
             const int ncols = c->B * (4 * l + 2);
             for (int c0 = 0; c0 < ncols; c0 += 16 * cts[ci]) t32.push_back(HankelTile32{l, c0});
         }
-        if (c->htile_force > 0 ? cts[ci] == c->htile_force : (int)t32.size() * div_up(c->N, HT_ROWS) * 5 >= c->n_cu * 4) break;
+        if (c->htile_force > 0 ? cts[ci] == c->htile_force : (int)t32.size() * hankel_row_blocks(c) * 5 >= c->n_cu * 4) break;
     }
     {
         // XCD-aware order: consecutive workgroup ids go round-robin to the 8 XCDs (one L2 each), so the tiles of one order

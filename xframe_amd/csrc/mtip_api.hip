@@ -1141,6 +1141,35 @@ int mtip_op_hankel(mtip_ctx* c, const mtip_cdouble* in, mtip_cdouble* out, int i
     return post_launch(c, "mtip_op_hankel");
 }
 
+int mtip_op_hankel_difference(mtip_ctx* c, const mtip_cdouble* in, const mtip_cdouble* sub, mtip_cdouble* out, int inverse,
+                              const uint8_t* sub_mask) {
+    CTX_CHECK(c);
+    if (!c->have_weights) FAIL(c, MTIP_ESTATE, "mtip_set_hankel_weights has not been called");
+    if (!hankel_has_difference(c)) FAIL(c, MTIP_ESTATE, "the Hankel kernel in use has no difference variant");
+    if (!in || !sub || !out) FAIL(c, MTIP_EINVAL, "null buffer");
+    (void)hipSetDevice(c->device);
+    SYNC();
+    H2D(c->d_c[0], in, (size_t)c->B * c->C * sizeof(double2));
+    H2D(c->d_c[1], sub, (size_t)c->B * c->C * sizeof(double2));
+    uint8_t* d_mask = nullptr;                                  // a buffer of its own: d_ftmask belongs to the loop's next runs
+    if (sub_mask) {
+        if (hipMalloc((void**)&d_mask, (size_t)c->B) != hipSuccess) FAIL(c, MTIP_ENOMEM, "hipMalloc failed");
+        if (mtip_copy(c, d_mask, sub_mask, (size_t)c->B, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d_mask);
+            FAIL(c, MTIP_EHIP, "copy of the subtraction mask failed");
+        }
+    }
+    {
+        ProfScope ps(c, "hankel");
+        launch_hankel_mfma_sub(c, c->d_c[0], c->d_c[1], c->d_c[2], inverse ? 1 : 0, d_mask);
+    }
+    const hipError_t sync = hipStreamSynchronize(c->stream);
+    if (d_mask) (void)hipFree(d_mask);
+    MTIP_HIP_CHECK(c, sync);
+    D2H(out, c->d_c[2], (size_t)c->B * c->C * sizeof(double2));
+    return post_launch(c, "mtip_op_hankel_difference");
+}
+
 int mtip_op_fourier_transform(mtip_ctx* c, const mtip_cdouble* in, mtip_cdouble* out, int inverse) {
     CTX_CHECK(c);
     int r = require_transforms(c);
@@ -1295,6 +1324,14 @@ int mtip_debug_jacobi_sweeps(mtip_ctx* c, int32_t* out) {
     MTIP_HIP_CHECK(c, mtip_copy(c, out, c->d_sweeps, (size_t)c->B * (c->L + 1) * sizeof(int), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < (size_t)c->B * (c->L + 1); ++i)
         if (out[i] == 0x7fffffff) FAIL(c, MTIP_ESTATE, "k_rproj: an order's LDS layout exceeded the launch's allocation and was skipped");
+    return MTIP_OK;
+}
+
+int mtip_debug_hankel_tiles(mtip_ctx* c, int* ct, int* n_tiles, int* n_row_blocks) {
+    CTX_CHECK(c);
+    if (ct) *ct = c->htile_ct;
+    if (n_tiles) *n_tiles = c->n_htiles32;
+    if (n_row_blocks) *n_row_blocks = hankel_row_blocks(c);
     return MTIP_OK;
 }
 

@@ -366,6 +366,7 @@ void launch_hankel_mfma_sub(mtip_ctx* c, const double2* in, const double2* in_su
 int build_jacobi_schedule(mtip_ctx* c, int kmax);    // k_proj.hip: resident-column pairing schedule, verified on the host
 int jacobi_groups(int k);                            // pair-groups a round of that schedule keeps busy for k columns (<= jsched_ps: the table's row length)
 int build_hankel_tiles(mtip_ctx* c);
+int hankel_row_blocks(const mtip_ctx* c);            // row blocks (128 output shells each) of k_hankel_tile: the grid's y extent
 int launch_invariant_metrics(mtip_ctx* c, const double2* Ilm, long long step);
 void free_invariant_metrics(mtip_ctx* c);
 int launch_reciprocal_l2_metric(mtip_ctx* c, const double2* F, const double2* Fp, long long step);

@@ -77,6 +77,7 @@ _SIGNATURES = {
     'mtip_op_sht_inverse': (C.c_int, [c_void, c_void, c_void]),
     'mtip_op_sht_inverse_forward': (C.c_int, [c_void, c_void, c_void, c_void, C.c_int]),
     'mtip_op_hankel': (C.c_int, [c_void, c_void, c_void, C.c_int]),
+    'mtip_op_hankel_difference': (C.c_int, [c_void, c_void, c_void, c_void, C.c_int, c_void]),
     'mtip_op_fourier_transform': (C.c_int, [c_void, c_void, c_void, C.c_int]),
     'mtip_op_project_coefficients': (C.c_int, [c_void, c_void, c_void]),
     'mtip_op_project_real_intensity': (C.c_int, [c_void, c_void, c_void]),
@@ -142,6 +143,7 @@ _SIGNATURES = {
     'mtip_profile_reset': (C.c_int, [c_void]),
     'mtip_debug_jacobi_sweeps': (C.c_int, [c_void, c_void]),
     'mtip_debug_projection_slots': (C.c_int, [c_void]),
+    'mtip_debug_hankel_tiles': (C.c_int, [c_void, c_void, c_void, c_void]),
     'mtip_debug_chain_timing': (C.c_int, [c_void, c_void]),
     'mtip_debug_check_jacobi_schedule': (C.c_int, [c_void, C.c_int]),
     'mtip_debug_polar_timing': (C.c_int, [c_void, c_void]),

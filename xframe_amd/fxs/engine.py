@@ -232,6 +232,15 @@ class Engine:
         self._ck(self.lib.mtip_op_hankel(self.ctx, _lib.ptr(c), _lib.ptr(out), int(inverse)))
         return out
 
+    def hankel_difference(self, coeff, coeff_sub, inverse=False, sub_mask=None):
+        """H(coeff - coeff_sub) above output shell 0 and H(coeff) on it, for the restarts sub_mask (B flags, None: all) selects;
+        H(coeff) for the others: the launch of the one-pass ft_stab step"""
+        c, s = self._bcoef(coeff), self._bcoef(coeff_sub)
+        out = np.empty_like(c)
+        m = None if sub_mask is None else _lib.as_u8(np.asarray(sub_mask).reshape(self.B) != 0)
+        self._ck(self.lib.mtip_op_hankel_difference(self.ctx, _lib.ptr(c), _lib.ptr(s), _lib.ptr(out), int(inverse), _lib.ptr(m)))
+        return out
+
     def fourier_transform(self, grid, inverse=False):
         g = self._bgrid(grid)
         out = np.empty_like(g)
@@ -707,6 +716,12 @@ class Engine:
         out = np.zeros((self.B, self.L + 1), np.int32)
         self._ck(self.lib.mtip_debug_jacobi_sweeps(self.ctx, _lib.ptr(out)))
         return (out >> 8) & 0xffff
+
+    def hankel_tiles(self):
+        """(ct, n_tiles, n_row_blocks) of the Hankel kernel's launch plan: 16-column tiles per workgroup, grid x, grid y"""
+        ct, nt, nr = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._ck(self.lib.mtip_debug_hankel_tiles(self.ctx, C.byref(ct), C.byref(nt), C.byref(nr)))
+        return ct.value, nt.value, nr.value
 
     def projection_slots(self):
         """workgroups per restart of the real projection kernel in the last call (0: general complex kernels)"""
