@@ -309,6 +309,45 @@ int mtip_op_cc_to_deg2(mtip_ctx* ctx, int n_q, int n_delta, int max_order, int o
                        const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
                        mtip_cdouble* b_out);
 
+/* ---- correlate: polar patterns -> averaged two-point cross-correlation C(q1, q2, Delta) (csrc/k_correlate.h) ----------------
+ * The first stage of the fxs chain (xframe/projects/fxs/correlate.py:401-452, 347-355, 249-270 and all of
+ * projectLibrary/cross_correlation.py) from the polar resampling on: images (n_patterns, n_q, n_phi) float64 and masks
+ * (n_patterns, n_q, n_phi) uint8 with values 0 / 1 are what process_image holds at line 398.  A handle owns the accumulators
+ * sum (n_q1, n_q2, n_phi) float64 and count (same shape) int32 on the context's device; its size is checked against the free
+ * device memory at create (a null return; the message in mtip_last_error names the size).
+ * cfg: filter_kind 1 = intensity_radial_pixel_filter 'average_sigma' with filter_k sigmas (0: none); the ROI mean runs over the
+ * rings [roi_lo, roi_hi) where mask == 1: roi_filter rejects a pattern whose mean is outside [roi_min, roi_max], roi_normalize
+ * divides the image by it; factor (n_q, n_phi) or NULL: polarisation x solid-angle table (565-591) multiplied in afterwards.
+ * shared_mask: the mask is the same for every pattern (ignored with a filter, which makes it per pattern): masks is then
+ * (n_q, n_phi), the mask of the first batch is the handle's, and its pair counts M are computed once.
+ * q1_pos (n_q1), q2_pos (n_q2): the selected rings.  n_phi: 16, 32, .. 1024 (a power of two).
+ * Per good pattern  sum += D / M, count += 1  where |M| >= 0.5, with D = irfft(conj F[q1] F[q2]), M = irfft(conj G[q1] G[q2]),
+ * F = rfft(image), G = rfft(mask).  (The reference tests M != 0 on a rounded integer: the one deliberate deviation.)
+ * Every buffer of add / get_partial / merge / finalize may be host memory or memory of the context's device. */
+typedef struct mtip_correlate mtip_correlate;
+typedef struct {
+    int32_t n_q, n_phi, n_q1, n_q2;
+    int32_t filter_kind, roi_lo, roi_hi, roi_filter, roi_normalize, shared_mask;
+    double filter_k, roi_min, roi_max;
+} mtip_correlate_cfg;
+mtip_correlate* mtip_correlate_create(mtip_ctx* ctx, const mtip_correlate_cfg* cfg, const int32_t* q1_pos, const int32_t* q2_pos,
+                                      const double* factor);
+void mtip_correlate_destroy(mtip_correlate* h);
+/* one batch: flags and waxs rows are decided on the device and kept by the handle; patterns are accumulated in pattern order, so
+ * the same patterns give bit-identical sum and count however they are split into batches */
+int mtip_correlate_add(mtip_correlate* h, int n_patterns, const double* images, const uint8_t* masks);
+/* patterns added or merged so far (a negative error code for a null handle) */
+int mtip_correlate_num_patterns(mtip_correlate* h);
+/* the additive partial result: sum, count (n_q1, n_q2, n_phi), is_good (n_patterns) int32, waxs (n_patterns, n_q); NULL: skipped */
+int mtip_correlate_get_partial(mtip_correlate* h, double* sum, int32_t* count, int32_t* is_good, double* waxs);
+/* add another handle's partial result (its patterns are appended) */
+int mtip_correlate_merge(mtip_correlate* h, const double* sum, const int32_t* count, int n_patterns, const int32_t* is_good,
+                         const double* waxs);
+/* ccf = sum / count, NaN where count = 0; symmetrize != 0: symmetrize_ccf with the three positions; ccf (n_q1, n_q2, n_phi) and / or
+ * fc = fft(ccf)[..., :fc_n_max] (n_q1, n_q2, fc_n_max); a NULL output is skipped */
+int mtip_correlate_finalize(mtip_correlate* h, int symmetrize, int pos_pi2, int pos_pi, int pos_3pi2, int fc_n_max, double* ccf,
+                            mtip_cdouble* fc);
+
 /* ---- the 2-D (polar) variant, operator level --------------------------------------
  * Grids (n_batch, Nq, n_phi) complex128 with n_phi = 2 M + 1 (harmonic_transforms.py:44-47); harmonic coefficients in numpy's
  * FFT order (orders 0..M, -M..-1); coefficients of the real transform (n_batch, Nq, M + 1).  Buffers: host or device memory. */

@@ -1,0 +1,132 @@
+"""GPU: patterns -> C(q1, q2, Delta) (fxs.correlate.Correlator, csrc/k_correlate.h) at the reference's tutorial shape (256 rings,
+n_phi = 1024, every pair of rings) and at a small one (64 rings, n_phi = 256), with a shared mask and with per-pattern masks.
+Per shape and mask mode, batch sizes 1, 8 and 32: ms per pattern of Correlator.add on device tensors (host clock around calls that end
+in a synchronise; five windows after a warm-up: median, min .. max), and inside the same windows the event brackets of the kernel
+families corr_ring (k_corr_stats + k_corr_ring) and corr_pair (k_corr_pair).  Derived, with the counts stated where they are printed:
+the achieved FFT rate of k_corr_pair against the fp64 vector peak, and the accumulator bytes per pattern against HBM.
+The numpy restatement of the route (tests/correlate_cases.r_correlate) on this host with 1 and with 8 processes, as context.
+usage: python scripts/bench_correlate.py [--small]          (--small: the small shape only)"""
+import multiprocessing as mp
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+np.seterr(all='ignore')
+
+HBM_PEAK = 8e12
+FP64_VECTOR_PEAK = 78e12
+BATCHES = (1, 8, 32)
+
+
+def settings_for(n_q, n_phi):
+    import correlate_cases as CO
+    return CO.make_settings(n_q, n_phi, q_step=2.0 ** -10, q_min=2.0 ** -10)
+
+
+def patterns(n_q, n_phi, P, seed=0):
+    rng = np.random.default_rng(seed)
+    masks = (rng.random((P, n_q, n_phi)) < 0.85).astype(np.uint8)
+    images = (200.0 * (1.0 + 0.4 * rng.random((P, n_q, n_phi)))) * masks
+    return images, masks
+
+
+def pair_flops(n_q1, n_q2, n_phi, shared):
+    """per pattern: (2 or 1) inverse real transforms per pair, each one complex FFT of m = n_phi / 2 points (5 m log2 m) plus the
+    spectrum product and the even / odd fold (24 m)"""
+    m = n_phi // 2
+    return n_q1 * n_q2 * (1 if shared else 2) * (5.0 * m * np.log2(m) + 24.0 * m)
+
+
+def stats(v):
+    v = np.sort(np.asarray(v))
+    return '%8.3f ms (min %.3f .. max %.3f)' % (np.median(v), v[0], v[-1])
+
+
+def _cpu_worker(args):
+    n_q, n_phi, P, seed = args
+    import correlate_cases as CO
+    prm = CO.params(settings_for(n_q, n_phi))
+    images, masks = patterns(n_q, n_phi, P, seed)
+    t0 = time.perf_counter()
+    CO.r_correlate(images, masks, prm)
+    return time.perf_counter() - t0
+
+
+def cpu_context(n_q, n_phi, P):
+    t1 = _cpu_worker((n_q, n_phi, P, 1))
+    t0 = time.perf_counter()
+    with mp.get_context('spawn').Pool(8) as pool:
+        pool.map(_cpu_worker, [(n_q, n_phi, P, 10 + i) for i in range(8)])
+    t8 = time.perf_counter() - t0
+    print('  numpy restatement on this host: 1 process %.1f ms per pattern; 8 processes (%d patterns each, pool start included) '
+          '%.1f ms per pattern' % (1e3 * t1 / P, P, 1e3 * t8 / (8 * P)))
+
+
+def main():
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_correlate needs a GPU: a timing without one measures nothing')
+    from xframe_amd.fxs import correlate as CR
+    from xframe_amd.fxs.engine import Engine
+    e = Engine({'grid': {'n_radial_points': 8, 'max_order': 2}}, None, n_batch=1, max_q=1.0)
+    shapes = ((64, 256),) if '--small' in sys.argv else ((256, 1024), (64, 256))
+    for n_q, n_phi in shapes:
+        settings = settings_for(n_q, n_phi)
+        images, masks = patterns(n_q, n_phi, max(BATCHES))
+        d_img = torch.from_numpy(images).cuda()
+        d_mask = torch.from_numpy(masks).cuda()
+        n_acc = n_q * n_q * n_phi
+        print('%d rings x %d angles, %d x %d pairs: accumulator %.1f MB (sum f64 + count int32), shared-mask table %.1f MB' %
+              (n_q, n_phi, n_q, n_q, 12e-6 * n_acc, 8e-6 * n_acc))
+        for shared in (True, False):
+            per_pattern = {}
+            for B in BATCHES:
+                c = CR.Correlator(e, settings, shared_mask=shared)
+                m = d_mask[0] if shared else d_mask[:B]
+                t0 = time.perf_counter()
+                c.add(d_img[:B], m)                                    # warm-up (code objects, the shared mask's table)
+                c.add(d_img[:B], m)
+                torch.cuda.synchronize()
+                one = (time.perf_counter() - t0) / 2
+                reps = int(min(64, max(2, round(0.4 / max(one, 1e-4)))))
+                wall, ring, pair = [], [], []
+                for _ in range(5):
+                    e.profile(True)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(reps):
+                        c.add(d_img[:B], m)
+                    torch.cuda.synchronize()
+                    wall.append(1e3 * (time.perf_counter() - t0) / (reps * B))
+                    r_ms, _ = e.profile_get('corr_ring')
+                    p_ms, n = e.profile_get('corr_pair')
+                    assert n == reps, (n, reps)
+                    ring.append(r_ms / (reps * B))
+                    pair.append(p_ms / (reps * B))
+                    e.profile(False)
+                c.close()
+                per_pattern[B] = float(np.median(wall))
+                k = 1e-3 * float(np.median(pair))
+                fl = pair_flops(n_q, n_q, n_phi, shared)
+                acc_bytes = (24.0 + (8.0 if shared else 0.0)) * n_acc / B
+                print('  %s mask, batch %2d (%2d calls per window): add %s per pattern' % ('shared     ' if shared else 'per-pattern', B, reps,
+                                                                                         stats(wall)))
+                print('      k_corr_pair %s | k_corr_stats + k_corr_ring %s per pattern' % (stats(pair), stats(ring)))
+                print('      k_corr_pair: %.2f GFLOP of FFT per pattern -> %.2f TFLOP/s = %.1f %% of the fp64 vector peak (78 TFLOP/s); '
+                      'accumulator traffic %.1f MB per pattern = %.3f ms at 8 TB/s (%.1f %% of the kernel time)' %
+                      (1e-9 * fl, 1e-12 * fl / k, 100 * fl / k / FP64_VECTOR_PEAK, 1e-6 * acc_bytes, 1e3 * acc_bytes / HBM_PEAK,
+                       100 * acc_bytes / HBM_PEAK / k))
+            print('  %s mask: ms per pattern at batch 1 / 8 / 32 = %.3f / %.3f / %.3f  (batch 32 below batch 1: %s)' %
+                  ('shared' if shared else 'per-pattern', per_pattern[1], per_pattern[8], per_pattern[32], per_pattern[32] < per_pattern[1]))
+        del d_img, d_mask
+        cpu_context(n_q, n_phi, 1 if n_q >= 256 else 8)
+    e.close()
+
+
+if __name__ == '__main__':
+    main()

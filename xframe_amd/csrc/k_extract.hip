@@ -875,3 +875,6 @@ extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_ord
     }
     return MTIP_OK;
 }
+
+// ---- patterns -> cross-correlation (the stage in front of the one above) -----------------------------------------------
+#include "k_correlate.h"

@@ -26,6 +26,12 @@ class MtipCfg(C.Structure):
                 ('n_batch', C.c_int32), ('hankel_trapz', C.c_int32), ('fused', C.c_int32), ('reserved', C.c_int32)]
 
 
+class MtipCorrelateCfg(C.Structure):
+    _fields_ = [('n_q', C.c_int32), ('n_phi', C.c_int32), ('n_q1', C.c_int32), ('n_q2', C.c_int32), ('filter_kind', C.c_int32),
+                ('roi_lo', C.c_int32), ('roi_hi', C.c_int32), ('roi_filter', C.c_int32), ('roi_normalize', C.c_int32),
+                ('shared_mask', C.c_int32), ('filter_k', C.c_double), ('roi_min', C.c_double), ('roi_max', C.c_double)]
+
+
 class MtipError(RuntimeError):
     pass
 
@@ -138,6 +144,13 @@ _SIGNATURES = {
     'mtip_op_hermitian_eig': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
     'mtip_op_symmetric_eig': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
     'mtip_op_cc_to_deg2': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, c_void, c_void, c_void, c_void, c_void]),
+    'mtip_correlate_create': (c_void, [c_void, C.POINTER(MtipCorrelateCfg), c_void, c_void, c_void]),
+    'mtip_correlate_destroy': (None, [c_void]),
+    'mtip_correlate_add': (C.c_int, [c_void, C.c_int, c_void, c_void]),
+    'mtip_correlate_num_patterns': (C.c_int, [c_void]),
+    'mtip_correlate_get_partial': (C.c_int, [c_void, c_void, c_void, c_void, c_void]),
+    'mtip_correlate_merge': (C.c_int, [c_void, c_void, c_void, C.c_int, c_void, c_void]),
+    'mtip_correlate_finalize': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void]),
     'mtip_profile': (C.c_int, [c_void, C.c_int]),
     'mtip_profile_get': (C.c_int, [c_void, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'mtip_profile_reset': (C.c_int, [c_void]),

@@ -1,0 +1,303 @@
+"""``fxs correlate`` from the polar resampling on: patterns -> averaged two-point cross-correlation C(q1, q2, Delta).
+
+Reference: ``xframe/projects/fxs/correlate.py`` (``process_image`` 401-452, accumulation 347-355, normalisation and result dict
+249-295, ``_analyse_dependencies`` 478-484, ``_prepare_polar_representation`` 489-559, correction tables 565-591) and
+``projectLibrary/cross_correlation.py`` (``ccf_analysis``).  The arithmetic runs in the kernels of ``csrc/k_correlate.h``; this file is
+settings bookkeeping, the host-side tables and the result dict.
+
+The boundary is AFTER the Cartesian -> polar resampling: the caller reads detector files, applies ``intensity_pixel_threshold``, the
+binary mask and the background, and resamples with ``scipy.ndimage.map_coordinates`` on the ``cart_x`` / ``cart_y`` of
+:func:`polar_geometry`; ``Correlator.add`` takes what ``process_image`` holds at line 398: images (P, n_q, n_phi) float and masks
+(P, n_q, n_phi) -- or one shared (n_q, n_phi) -- with values 0 / 1.
+
+Deviations from the reference, both deliberate: a (q1, q2, Delta) element of a pattern counts where the mask's pair count
+|M| >= 0.5 (the reference tests the rounded value M != 0; the two agree wherever the reference is deterministic), and a pattern's own
+``is_good`` flag decides whether it is accumulated (the reference indexes the flag array with the position inside a sub-batch, 347).
+"""
+import ctypes as C
+import math
+import warnings
+
+import numpy as np
+
+from . import _lib
+from .settings import resolve_correlate
+
+SUPPORTED_N_PHI = (16, 32, 64, 128, 256, 512, 1024)
+
+
+def analyse_dependencies(compute):
+    """``_analyse_dependencies`` (correlate.py:478-484)"""
+    compute = list(compute)
+    if 'ccf_q1q2' in compute and 'xcca' not in compute:
+        compute.append('xcca')
+    if 'waxs_aver' in compute and 'waxs' not in compute:
+        compute.append('waxs')
+    return compute
+
+
+def polar_geometry(settings):
+    """``_prepare_polar_representation`` (correlate.py:489-559) and the default q ranges of ``ProjectWorker.__init__`` (77-90) on the
+    host: everything the caller's resampling and the result dict need.  Returns a dict with qvals, theta, phi, n_q, n_phi, maxpix,
+    cart_x, cart_y (n_q, n_phi), q1vals_pos, q2vals_pos, q1vals, q2vals."""
+    opt = resolve_correlate(settings)
+    wavelng, det_sam, pixelsize = float(opt['wavelength']), float(opt['sample_distance']), float(opt['pixel_size'])
+    qrange, qrange_xcca = opt['qrange'], opt['qrange_xcca']
+    if isinstance(qrange, bool) or isinstance(qrange_xcca, bool):                        # 77-90
+        detector_edge = opt['image_dimensions'][0] / 2 * (pixelsize / 1000)
+        scattering_angle = np.arctan(detector_edge / det_sam)
+        q_max = 4 * np.pi * np.sin(scattering_angle / 2) / wavelng
+        if isinstance(qrange, bool):
+            qrange = [0, q_max, q_max / (opt['image_dimensions'][0] / 2 - 1)]
+        if isinstance(qrange_xcca, bool):
+            qrange_xcca = [[0, q_max, 1], [0, q_max, 1]]
+    phirange = opt['phi_range']
+    q_min, q_max, q_step = qrange[0], qrange[1], qrange[2]
+    pixsz = pixelsize * 0.001
+    n_q = int((q_max - q_min) / q_step + 1)                                              # 495
+    phi_min, phi_max, n_phi = phirange[0], phirange[1], phirange[2]
+    qvals = np.arange(n_q) * q_step + q_min
+    theta = 2.0 * np.arcsin(qvals * wavelng / (4.0 * math.pi))
+    max_circ_rad_pix = int(round(det_sam * math.tan(theta[-1]) / pixsz))
+    maxpix = round(2 * math.pi * max_circ_rad_pix)
+    if (maxpix % 2) != 0:
+        maxpix += 1
+    maxpix = int(maxpix)
+    if phirange[3] == 'max':                                                             # 517-522
+        n_phi = min(maxpix, n_phi)
+    elif phirange[3] == 'min':
+        n_phi = max(maxpix, n_phi)
+    n_phi = int(n_phi)
+    phi = np.arange(n_phi) * (phi_max - phi_min) / float(n_phi) + phi_min
+    pol_q = np.outer(np.tan(theta) * det_sam / pixsz, np.ones(n_phi))
+    pol_phi = np.outer(np.ones(n_q), phi)
+    origin = opt['detector_origin']
+    cart_x = pol_q * np.cos(pol_phi) + origin[0]
+    cart_y = pol_q * np.sin(pol_phi) + origin[1]
+    pos = []
+    for sel in qrange_xcca:                                                              # 547-558
+        p1 = np.abs(qvals - sel[0]).argmin()
+        p2 = np.abs(qvals - sel[1]).argmin()
+        pos.append(np.arange(p1, p2 + 1, sel[2]))
+    return {'qvals': qvals, 'theta': theta, 'phi': phi, 'n_q': n_q, 'n_phi': n_phi, 'maxpix': maxpix, 'cart_x': cart_x, 'cart_y': cart_y,
+            'q1vals_pos': pos[0], 'q2vals_pos': pos[1], 'q1vals': qvals[pos[0]], 'q2vals': qvals[pos[1]]}
+
+
+def polarization_factor(theta, phi, kind):
+    """``_determine_polarization_correction`` (565-582); any other kind leaves ones, as upstream"""
+    out = np.ones((len(theta), len(phi)))
+    if kind in ('v', 'h'):
+        f = np.sin if kind == 'v' else np.cos
+        for i, th in enumerate(theta):
+            for j, fi in enumerate(phi):
+                out[i, j] = 1.0 / (math.cos(th) ** 2 + (math.sin(th) ** 2) * (f(fi) ** 2))
+    return out
+
+
+def solid_angle_factor(theta, n_phi):
+    """``_determine_solid_angle_correction`` (587-591)"""
+    out = np.empty((len(theta), n_phi))
+    for i, th in enumerate(theta):
+        out[i] = 1.0 / (math.cos(th) ** 3)
+    return out
+
+
+class Correlator:
+    """Accumulates patterns on the engine's device: ``add(images, masks)`` any number of times, ``result()`` for the reference's result
+    dict (it goes through ``io.load_ccd(..., 'direct')`` into ``extract_from_cross_correlation`` unchanged).  ``partial()`` /
+    ``merge(partials)`` make the accumulation additive over ranks or GPUs that each take a share of the patterns.
+
+    shared_mask=True: one mask for every pattern; its pair counts are computed once per handle.  An active radial pixel filter makes
+    masks per pattern, so the flag is ignored then."""
+
+    def __init__(self, engine, settings=None, shared_mask=False):
+        self.engine = engine
+        self.lib = engine.lib
+        self.opt = opt = resolve_correlate(settings)
+        self.compute = analyse_dependencies(opt['compute'])
+        self.geometry = g = polar_geometry(opt)
+        self.n_q, self.n_phi = g['n_q'], g['n_phi']
+        if self.n_phi not in SUPPORTED_N_PHI:
+            raise NotImplementedError(f'correlate: n_phi = {self.n_phi} is not built; supported lengths: {SUPPORTED_N_PHI}')
+        filt = opt['intensity_radial_pixel_filter']
+        self.filter = bool(filt[0])
+        if self.filter and filt[1][0] == 'median_mad':
+            raise NotImplementedError("correlate: intensity_radial_pixel_filter 'median_mad' (correlate.py:405-406, i_median_and_mad "
+                                      '471-474) is not built; average_sigma is')
+        if self.filter and filt[1][0] != 'average_sigma':
+            raise ValueError(f'correlate: unknown intensity_radial_pixel_filter {filt[1][0]!r} (correlate.py:408)')
+        roi_n, roi_f = opt['ROI_normalization'], opt['ROI_mean_filter']
+        qvals = g['qvals']
+        roi_lo = roi_hi = 0
+        if roi_n[0] or roi_f[0]:                                                         # 186-188: both read ROI_normalization's range
+            roi_lo = int(np.abs(qvals - roi_n[1]).argmin())
+            roi_hi = int(np.abs(qvals - roi_n[2]).argmin())
+        factor = None
+        pol = opt['polarization_correction']
+        if pol[0]:
+            factor = polarization_factor(g['theta'], g['phi'], pol[1])
+        if opt['solid_angle_correction'] is True:
+            sa = solid_angle_factor(g['theta'], self.n_phi)
+            factor = sa if factor is None else factor * sa
+        self.factor = None if factor is None else _lib.as_f64(factor)
+        self.q1 = np.ascontiguousarray(g['q1vals_pos'], dtype=np.int32)
+        self.q2 = np.ascontiguousarray(g['q2vals_pos'], dtype=np.int32)
+        self.n_q1, self.n_q2 = len(self.q1), len(self.q2)
+        self.shared_mask = bool(shared_mask) and not self.filter
+        self._mask0 = None
+        cfg = _lib.MtipCorrelateCfg(self.n_q, self.n_phi, self.n_q1, self.n_q2, 1 if self.filter else 0, roi_lo, roi_hi,
+                                    1 if roi_f[0] else 0, 1 if roi_n[0] else 0, 1 if self.shared_mask else 0,
+                                    float(filt[1][1]) if self.filter else 0.0, float(roi_f[1]), float(roi_f[2]))
+        self.handle = self.lib.mtip_correlate_create(engine.ctx, C.byref(cfg), _lib.ptr(self.q1), _lib.ptr(self.q2), _lib.ptr(self.factor))
+        if not self.handle:
+            msg = self.lib.mtip_last_error(engine.ctx).decode()
+            if 'GB' in msg:
+                raise MemoryError(msg)
+            raise _lib.MtipError(msg)
+
+    # ------------------------------------------------------------------ bookkeeping
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.mtip_correlate_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        self.engine._ck(rc)
+
+    @property
+    def acc_shape(self):
+        return (self.n_q1, self.n_q2, self.n_phi)
+
+    @property
+    def num_patterns(self):
+        return int(self.lib.mtip_correlate_num_patterns(self.handle))
+
+    # ------------------------------------------------------------------ accumulation
+    def add(self, images, masks):
+        """images (P, n_q, n_phi) float32 / float64, masks (P, n_q, n_phi) or one (n_q, n_phi) of 0 / 1 (any integer or bool type):
+        numpy arrays, or torch tensors on the engine's device.  A single mask for P patterns is expanded unless the handle was made
+        with shared_mask."""
+        on_device = not isinstance(images, np.ndarray) and hasattr(images, 'data_ptr')
+        ring = (self.n_q, self.n_phi)
+        if on_device:
+            import torch
+            if images.dtype not in (torch.float32, torch.float64):
+                raise TypeError('correlate: images must be float32 or float64')
+            if images.ndim == 2:
+                images = images[None]
+            images = images.to(torch.float64).contiguous()
+            masks = torch.as_tensor(masks, device=images.device)
+            if bool(((masks != 0) & (masks != 1)).any()):
+                raise ValueError('correlate: mask values other than 0 / 1')
+            masks = masks.to(torch.uint8)
+            shape, mshape = tuple(images.shape), tuple(masks.shape)
+        else:
+            images = np.asarray(images)
+            if images.dtype not in (np.float32, np.float64):
+                raise TypeError('correlate: images must be float32 or float64')
+            if images.ndim == 2:
+                images = images[None]
+            images = _lib.as_f64(images)
+            masks = np.asarray(masks)
+            if ((masks != 0) & (masks != 1)).any():
+                raise ValueError('correlate: mask values other than 0 / 1')
+            masks = masks.astype(np.uint8)
+            shape, mshape = images.shape, masks.shape
+        if len(shape) != 3 or tuple(shape[1:]) != ring:
+            raise ValueError(f'correlate: images must have shape (P, {self.n_q}, {self.n_phi}), got {tuple(shape)}')
+        P = int(shape[0])
+        if tuple(mshape) not in (ring, (1,) + ring, (P,) + ring):
+            raise ValueError(f'correlate: masks must have shape (P, n_q, n_phi) or (n_q, n_phi), got {tuple(mshape)}')
+        one = tuple(mshape) == ring or (tuple(mshape) == (1,) + ring and P != 1)
+        masks = masks.reshape((-1,) + ring)
+        if self.shared_mask:
+            if masks.shape[0] != 1:
+                raise ValueError('correlate: a handle made with shared_mask takes one (n_q, n_phi) mask')
+            host = masks.cpu().numpy() if on_device else masks
+            if self._mask0 is None:
+                self._mask0 = host.copy()
+            elif not np.array_equal(self._mask0, host):
+                raise ValueError('correlate: shared_mask: the mask differs from the one of the first batch')
+        elif one or masks.shape[0] != P:
+            masks = masks.expand(P, -1, -1) if on_device else np.broadcast_to(masks, (P,) + ring)
+        if on_device:
+            masks = masks.contiguous()
+            p_img, p_mask = self.engine._tp(images), self.engine._tp(masks)
+            if images.is_cuda:                                                           # torch's conversions above run on torch's stream,
+                torch.cuda.current_stream(images.device).synchronize()                   # the kernels on the context's own
+        else:
+            masks = np.ascontiguousarray(masks)
+            p_img, p_mask = _lib.ptr(images), _lib.ptr(masks)
+        self._ck(self.lib.mtip_correlate_add(self.handle, P, p_img, p_mask))
+        return self
+
+    def partial(self):
+        """the additive state: {'sum', 'count' (n_q1, n_q2, n_phi), 'is_good' (M) int32, 'waxs' (M, n_q)} as numpy arrays"""
+        n = self.num_patterns
+        out = {'sum': np.empty(self.acc_shape), 'count': np.empty(self.acc_shape, np.int32), 'is_good': np.empty(n, np.int32),
+               'waxs': np.empty((n, self.n_q))}
+        self._ck(self.lib.mtip_correlate_get_partial(self.handle, _lib.ptr(out['sum']), _lib.ptr(out['count']), _lib.ptr(out['is_good']),
+                                                     _lib.ptr(out['waxs'])))
+        return out
+
+    def merge(self, partials):
+        """add the partial results of other correlators (a dict of ``partial()`` or a list of them); their patterns are appended"""
+        if isinstance(partials, dict):
+            partials = [partials]
+        for p in partials:
+            s, c = _lib.as_f64(p['sum']), np.ascontiguousarray(p['count'], dtype=np.int32)
+            g, w = np.ascontiguousarray(p['is_good'], dtype=np.int32), _lib.as_f64(p['waxs'])
+            if s.shape != self.acc_shape or c.shape != self.acc_shape or w.shape != (len(g), self.n_q):
+                raise ValueError('correlate: a partial result of another shape')
+            self._ck(self.lib.mtip_correlate_merge(self.handle, _lib.ptr(s), _lib.ptr(c), len(g), _lib.ptr(g), _lib.ptr(w)))
+        return self
+
+    # ------------------------------------------------------------------ result (correlate.py:249-295)
+    def symmetrize_positions(self):
+        phi = self.geometry['phi']
+        return (int(np.abs(phi - math.pi / 2.0).argmin()), int(np.abs(phi - math.pi).argmin()), int(np.abs(phi - 3 * math.pi / 2.0).argmin()))
+
+    def finalize(self, want_ccf=True, want_fc=False):
+        """(ccf (n_q1, n_q2, n_phi) or None, fc (n_q1, n_q2, fc_n_max) or None) from the device"""
+        sym = self.opt['ccf_2p_symmetrize'] is True
+        pos = self.symmetrize_positions() if sym else (0, 0, 0)
+        fc_n = min(int(self.opt['fc_n_max']), self.n_phi)
+        ccf = np.empty(self.acc_shape) if want_ccf else None
+        fc = np.empty((self.n_q1, self.n_q2, fc_n), complex) if want_fc else None
+        self._ck(self.lib.mtip_correlate_finalize(self.handle, int(sym), pos[0], pos[1], pos[2], fc_n, _lib.ptr(ccf), _lib.ptr(fc)))
+        return ccf, fc
+
+    def result(self):
+        compute, g = self.compute, self.geometry
+        want_fc = 'ccf_q1q2_fc' in compute
+        want_ccf = 'ccf_q1q2' in compute
+        part_n = self.num_patterns
+        is_good = np.empty(part_n, np.int32)
+        waxs = np.empty((part_n, self.n_q))
+        self._ck(self.lib.mtip_correlate_get_partial(self.handle, None, None, _lib.ptr(is_good), _lib.ptr(waxs)))
+        mgood = int(np.sum(is_good))                                                     # 249
+        result = {}
+        if 'waxs_aver' in compute:                                                       # 252-253, 276-278
+            aver = np.zeros(self.n_q)
+            with np.errstate(invalid='ignore', divide='ignore'), warnings.catch_warnings():
+                warnings.simplefilter('ignore', RuntimeWarning)                          # (no good pattern: NaN, as upstream)
+                np.mean(waxs, axis=0, where=(is_good[:, None] == 1), out=aver)
+            result['average_intensity'] = aver
+        if 'xcca' in compute and (want_ccf or want_fc):
+            ccf, fc = self.finalize(want_ccf, want_fc)
+            if want_ccf:
+                result['cross_correlation'] = {'I1I1': ccf}                              # 280-282
+            if want_fc:
+                result['cross_correlation'] = {'I1I1_fc': fc}                            # 287-288
+        result['radial_points'] = g['qvals']
+        result['angular_points'] = g['phi']
+        result['num_images_processed'] = part_n
+        result['num_images_good'] = mgood
+        result['xray_wavelength'] = self.opt['wavelength']
+        return result

@@ -113,6 +113,37 @@ def default_settings():
     }
 
 
+def correlate_default_settings():
+    """the keys of the ``fxs correlate`` worker that the device route reads, with the reference's defaults
+    (``xframe/projects/fxs/settings/correlate/default_0.01.yaml``).  What belongs to the Cartesian stage (file lists,
+    intensity_pixel_threshold, binary mask, background, interpolation order) stays with the caller."""
+    return {
+        'compute': ['is_good', 'waxs_aver', 'ccf_q1q2'],
+        'intensity_radial_pixel_filter': [False, ['average_sigma', 3]],
+        'ROI_normalization': [False, 0.3, 0.9],
+        'ROI_mean_filter': [False, 1e2, 1e4],
+        'polarization_correction': [False, 'h'],
+        'solid_angle_correction': False,
+        'qrange': False,
+        'qrange_xcca': False,
+        'phi_range': (0.0, 2 * np.pi, 1536, 'exact'),
+        'fc_n_max': 15,
+        'ccf_2p_symmetrize': False,
+        'image_dimensions': [512, 512],
+        'pixel_size': 200.0,
+        'sample_distance': 620.0,
+        'wavelength': 1.23984,
+        'detector_origin': [255.2, 255.5],
+    }
+
+
+def resolve_correlate(overrides=None):
+    o = correlate_default_settings()
+    if overrides:
+        o = deep_update(o, to_plain(overrides))
+    return o
+
+
 def resolve(overrides=None):
     o = default_settings()
     if overrides:
