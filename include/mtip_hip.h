@@ -348,6 +348,35 @@ int mtip_correlate_merge(mtip_correlate* h, const double* sum, const int32_t* co
 int mtip_correlate_finalize(mtip_correlate* h, int symmetrize, int pos_pi2, int pos_pi, int pos_3pi2, int fc_n_max, double* ccf,
                             mtip_cdouble* fc);
 
+/* ---- correlate, the Cartesian stage: detector frames -> polar patterns (csrc/k_resample.h) ------------------------------------
+ * process_image 377-398 of xframe/projects/fxs/correlate.py per pattern: mask = 0 where image < threshold_lo or image >
+ * threshold_hi (threshold_on; tested on the raw image), mask *= (binary_mask != 0), image -= background, image *= mask, then
+ * scipy.ndimage.map_coordinates(., [cart_x, cart_y], order, mode='constant', cval=0, prefilter=True) of the image (float64 out)
+ * and of the mask (an integer array: rounded half away from zero, uint8 out).  cart_x indexes axis 0 (H), cart_y axis 1 (W); the
+ * n_points points need not form a grid.  Orders 0 .. 5; 2 <= H, W <= 4096 (beyond: a null return from create with a message).
+ * binary_mask (H, W) uint8, background (H, W) float64, each NULL unless its has_ flag is set; they and the coordinates are copied.
+ * run: images (n_patterns, H, W) float32 (is_float32 != 0) or float64; masks (n_patterns, H, W) uint8 0 / 1: the initial masks, or
+ * NULL for ones.  With the threshold off and masks NULL the Cartesian mask is the same for every pattern: it is resampled once per
+ * handle by the same kernels.  images_out (n_patterns, n_points) float64 and masks_out (n_patterns, n_points) uint8 are what
+ * mtip_correlate_add takes; *n_bad_mask (host memory, may be NULL) counts rounded mask values other than 0 / 1 (they are stored
+ * as their low byte).  Every other buffer may be host memory or memory of the context's device; work runs on the context's stream. */
+typedef struct mtip_resample mtip_resample;
+typedef struct {
+    int32_t H, W, order, threshold_on, has_binary_mask, has_background;
+    int64_t n_points;
+    double threshold_lo, threshold_hi;
+} mtip_resample_cfg;
+mtip_resample* mtip_resample_create(mtip_ctx* ctx, const mtip_resample_cfg* cfg, const double* cart_x, const double* cart_y,
+                                    const uint8_t* binary_mask, const double* background);
+void mtip_resample_destroy(mtip_resample* h);
+int mtip_resample_run(mtip_resample* h, int n_patterns, const void* images, int is_float32, const uint8_t* masks, double* images_out,
+                      uint8_t* masks_out, int64_t* n_bad_mask);
+/* run into buffers on the device, then mtip_correlate_add of them: bit-identical to the two calls.  The resample handle's points are
+ * the correlate handle's (n_q, n_phi) grid.  A rounded mask value other than 0 / 1 is MTIP_EINVAL and nothing is accumulated; so is
+ * a shared_mask correlate handle where the mask is not static (threshold on, or masks given). */
+int mtip_correlate_add_detector(mtip_correlate* h, mtip_resample* resample, int n_patterns, const void* images, int is_float32,
+                                const uint8_t* masks, int64_t* n_bad_mask);
+
 /* ---- the 2-D (polar) variant, operator level --------------------------------------
  * Grids (n_batch, Nq, n_phi) complex128 with n_phi = 2 M + 1 (harmonic_transforms.py:44-47); harmonic coefficients in numpy's
  * FFT order (orders 0..M, -M..-1); coefficients of the real transform (n_batch, Nq, M + 1).  Buffers: host or device memory. */

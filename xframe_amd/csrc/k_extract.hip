@@ -878,3 +878,5 @@ extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_ord
 
 // ---- patterns -> cross-correlation (the stage in front of the one above) -----------------------------------------------
 #include "k_correlate.h"
+// ---- detector frames -> patterns (the stage in front of that one) ------------------------------------------------------
+#include "k_resample.h"

@@ -32,6 +32,11 @@ class MtipCorrelateCfg(C.Structure):
                 ('shared_mask', C.c_int32), ('filter_k', C.c_double), ('roi_min', C.c_double), ('roi_max', C.c_double)]
 
 
+class MtipResampleCfg(C.Structure):
+    _fields_ = [('H', C.c_int32), ('W', C.c_int32), ('order', C.c_int32), ('threshold_on', C.c_int32), ('has_binary_mask', C.c_int32),
+                ('has_background', C.c_int32), ('n_points', C.c_int64), ('threshold_lo', C.c_double), ('threshold_hi', C.c_double)]
+
+
 class MtipError(RuntimeError):
     pass
 
@@ -151,6 +156,10 @@ _SIGNATURES = {
     'mtip_correlate_get_partial': (C.c_int, [c_void, c_void, c_void, c_void, c_void]),
     'mtip_correlate_merge': (C.c_int, [c_void, c_void, c_void, C.c_int, c_void, c_void]),
     'mtip_correlate_finalize': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void]),
+    'mtip_resample_create': (c_void, [c_void, C.POINTER(MtipResampleCfg), c_void, c_void, c_void, c_void]),
+    'mtip_resample_destroy': (None, [c_void]),
+    'mtip_resample_run': (C.c_int, [c_void, C.c_int, c_void, C.c_int, c_void, c_void, c_void, C.POINTER(C.c_int64)]),
+    'mtip_correlate_add_detector': (C.c_int, [c_void, c_void, C.c_int, c_void, C.c_int, c_void, C.POINTER(C.c_int64)]),
     'mtip_profile': (C.c_int, [c_void, C.c_int]),
     'mtip_profile_get': (C.c_int, [c_void, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'mtip_profile_reset': (C.c_int, [c_void]),

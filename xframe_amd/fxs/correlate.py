@@ -1,18 +1,21 @@
-"""``fxs correlate`` from the polar resampling on: patterns -> averaged two-point cross-correlation C(q1, q2, Delta).
+"""``fxs correlate`` from detector frames on: frames -> polar patterns -> averaged two-point cross-correlation C(q1, q2, Delta).
 
-Reference: ``xframe/projects/fxs/correlate.py`` (``process_image`` 401-452, accumulation 347-355, normalisation and result dict
-249-295, ``_analyse_dependencies`` 478-484, ``_prepare_polar_representation`` 489-559, correction tables 565-591) and
-``projectLibrary/cross_correlation.py`` (``ccf_analysis``).  The arithmetic runs in the kernels of ``csrc/k_correlate.h``; this file is
-settings bookkeeping, the host-side tables and the result dict.
+Reference: ``xframe/projects/fxs/correlate.py`` (``process_image`` 377-452, accumulation 347-355, normalisation and result dict
+249-295, ``_analyse_dependencies`` 478-484, ``_prepare_polar_representation`` 489-559, correction tables 565-591,
+``_read_binary_2D_arr`` 606-620) and ``projectLibrary/cross_correlation.py`` (``ccf_analysis``).  The arithmetic runs in the kernels
+of ``csrc/k_resample.h`` and ``csrc/k_correlate.h``; this file is settings bookkeeping, the host-side tables and the result dict.
 
-The boundary is AFTER the Cartesian -> polar resampling: the caller reads detector files, applies ``intensity_pixel_threshold``, the
-binary mask and the background, and resamples with ``scipy.ndimage.map_coordinates`` on the ``cart_x`` / ``cart_y`` of
-:func:`polar_geometry`; ``Correlator.add`` takes what ``process_image`` holds at line 398: images (P, n_q, n_phi) float and masks
-(P, n_q, n_phi) -- or one shared (n_q, n_phi) -- with values 0 / 1.
+The boundary is the detector frame: ``read_raw_images`` reads the files, ``Correlator.add_detector`` takes frames (P, H, W) and
+optional initial masks through ``Resampler`` (``intensity_pixel_threshold``, binary mask, background, ``image *= mask`` and the
+two ``map_coordinates`` calls of lines 382-398 on the ``cart_x`` / ``cart_y`` of :func:`polar_geometry`) into the accumulation
+without the polar arrays leaving the device.  ``Correlator.add`` still takes what ``process_image`` holds at line 398: images
+(P, n_q, n_phi) float and masks (P, n_q, n_phi) -- or one shared (n_q, n_phi) -- with values 0 / 1.
 
-Deviations from the reference, both deliberate: a (q1, q2, Delta) element of a pattern counts where the mask's pair count
-|M| >= 0.5 (the reference tests the rounded value M != 0; the two agree wherever the reference is deterministic), and a pattern's own
-``is_good`` flag decides whether it is accumulated (the reference indexes the flag array with the position inside a sub-batch, 347).
+Deviations from the reference, all deliberate: a (q1, q2, Delta) element of a pattern counts where the mask's pair count
+|M| >= 0.5 (the reference tests the rounded value M != 0; the two agree wherever the reference is deterministic), a pattern's own
+``is_good`` flag decides whether it is accumulated (the reference indexes the flag array with the position inside a sub-batch, 347),
+and ``use_binary_mask`` multiplies the mask by ``binary_mask != 0`` (line 385 multiplies an integer mask in place by a float array,
+which numpy refuses: the option raises upstream).
 """
 import ctypes as C
 import math
@@ -24,6 +27,9 @@ from . import _lib
 from .settings import resolve_correlate
 
 SUPPORTED_N_PHI = (16, 32, 64, 128, 256, 512, 1024)
+SUPPORTED_ORDERS = (0, 1, 2, 3, 4, 5)
+FRAME_DIM_MIN, FRAME_DIM_MAX = 2, 4096
+BAD_MASK = 'correlate: mask values other than 0 / 1'
 
 
 def analyse_dependencies(compute):
@@ -102,16 +108,169 @@ def solid_angle_factor(theta, n_phi):
     return out
 
 
+def read_raw_images(paths, shape):
+    """``_read_binary_2D_arr`` (606-620) for a list of files: little-endian float32 frames of the given (H, W), NaN -> 0; returns
+    (P, H, W) float32.  A file of another length raises (upstream's struct.unpack does)."""
+    if isinstance(paths, (str, bytes)) or hasattr(paths, '__fspath__'):
+        paths = [paths]
+    H, W = int(shape[0]), int(shape[1])
+    out = np.empty((len(paths), H, W), np.float32)
+    for i, path in enumerate(paths):
+        data = np.fromfile(path, dtype='<f4')
+        if data.size != H * W:
+            raise ValueError(f'read_raw_images: {path} holds {data.size} values, a {H} x {W} frame has {H * W}')
+        out[i] = data.reshape(H, W)
+    out[np.isnan(out)] = 0
+    return out
+
+
+def _frames(a, H, W, what, on_device):
+    """(P, H, W) from (P, H, W) or (H, W)"""
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or tuple(a.shape[1:]) != (H, W):
+        raise ValueError(f'correlate: {what} must have shape (P, {H}, {W}), got {tuple(a.shape)}')
+    return a.contiguous() if on_device else np.ascontiguousarray(a)
+
+
+class Resampler:
+    """The Cartesian stage of ``process_image`` (382-398) on the engine's device: ``run(images, masks=None)`` takes detector frames
+    (P, H, W) float32 / float64 and optional initial masks (P, H, W) or (H, W) of 0 / 1 (default: ones) to
+    (images_polar (P, n_q, n_phi) float64, masks_polar (P, n_q, n_phi) uint8), what ``Correlator.add`` takes.  numpy arrays in, numpy
+    arrays out; torch tensors on the engine's device in, such tensors out.  binary_mask / background (H, W) are read where the
+    settings switch them on (use_binary_mask, subtract_background); the binary mask counts where it is non-zero.
+
+    The mask is static where intensity_pixel_threshold is off and no masks are given: it is then resampled once per handle."""
+
+    def __init__(self, engine, settings=None, binary_mask=None, background=None):
+        self.engine = engine
+        self.lib = engine.lib
+        self.opt = opt = resolve_correlate(settings)
+        self.geometry = g = polar_geometry(opt)
+        self.n_q, self.n_phi = g['n_q'], g['n_phi']
+        self.H, self.W = int(opt['image_dimensions'][0]), int(opt['image_dimensions'][1])
+        self.order = opt['interpolation_order']
+        if self.order not in SUPPORTED_ORDERS:
+            raise NotImplementedError(f'correlate: interpolation_order = {self.order!r} is not built; supported orders: {SUPPORTED_ORDERS}')
+        if not (FRAME_DIM_MIN <= self.H <= FRAME_DIM_MAX and FRAME_DIM_MIN <= self.W <= FRAME_DIM_MAX):
+            raise NotImplementedError(f'correlate: frames of {self.H} x {self.W} are not built; supported: {FRAME_DIM_MIN} .. '
+                                      f'{FRAME_DIM_MAX} along either axis')
+        thr = opt['intensity_pixel_threshold']
+        self.threshold = bool(thr[0])
+        frame = (self.H, self.W)
+        self.binary_mask = self.background = None
+        if opt['use_binary_mask']:
+            if binary_mask is None or np.shape(binary_mask) != frame:
+                raise ValueError(f'correlate: use_binary_mask needs a binary_mask of shape {frame}')
+            self.binary_mask = _lib.as_u8(np.asarray(binary_mask) != 0)                  # 385: the evident intent
+        if opt['subtract_background']:
+            if background is None or np.shape(background) != frame:
+                raise ValueError(f'correlate: subtract_background needs a background of shape {frame}')
+            self.background = _lib.as_f64(background)
+        self.cart_x, self.cart_y = _lib.as_f64(g['cart_x']), _lib.as_f64(g['cart_y'])
+        cfg = _lib.MtipResampleCfg(self.H, self.W, int(self.order), int(self.threshold), int(self.binary_mask is not None),
+                                   int(self.background is not None), self.n_q * self.n_phi, float(thr[1]), float(thr[2]))
+        self.handle = self.lib.mtip_resample_create(engine.ctx, C.byref(cfg), _lib.ptr(self.cart_x), _lib.ptr(self.cart_y),
+                                                    _lib.ptr(self.binary_mask), _lib.ptr(self.background))
+        if not self.handle:
+            msg = self.lib.mtip_last_error(engine.ctx).decode()
+            if 'GB' in msg:
+                raise MemoryError(msg)
+            raise _lib.MtipError(msg)
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.mtip_resample_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def is_static(self, masks):
+        """the Cartesian mask does not depend on the pattern"""
+        return not self.threshold and masks is None
+
+    def prepare(self, images, masks):
+        """checked, contiguous inputs and their pointers: (images, masks or None, P, is_float32, on_device, p_img, p_mask)"""
+        on_device = not isinstance(images, np.ndarray) and hasattr(images, 'data_ptr')
+        if on_device:
+            import torch
+            if images.dtype not in (torch.float32, torch.float64):
+                raise TypeError('correlate: images must be float32 or float64')
+            images = _frames(images, self.H, self.W, 'images', True)
+            f32 = images.dtype == torch.float32
+            if masks is not None:
+                masks = torch.as_tensor(masks, device=images.device)
+                if bool(((masks != 0) & (masks != 1)).any()):
+                    raise ValueError(BAD_MASK)
+                masks = _frames(masks.to(torch.uint8), self.H, self.W, 'masks', True)
+        else:
+            images = np.asarray(images)
+            if images.dtype not in (np.float32, np.float64):
+                raise TypeError('correlate: images must be float32 or float64')
+            images = _frames(images, self.H, self.W, 'images', False)
+            f32 = images.dtype == np.float32
+            if masks is not None:
+                masks = np.asarray(masks)
+                if ((masks != 0) & (masks != 1)).any():
+                    raise ValueError(BAD_MASK)
+                masks = _frames(masks.astype(np.uint8), self.H, self.W, 'masks', False)
+        P = int(images.shape[0])
+        if masks is not None:
+            if masks.shape[0] not in (1, P):
+                raise ValueError(f'correlate: masks must have shape (P, H, W) or (H, W), got {tuple(masks.shape)}')
+            if masks.shape[0] != P:
+                masks = masks.expand(P, -1, -1).contiguous() if on_device else np.ascontiguousarray(np.broadcast_to(masks, images.shape))
+        if on_device:
+            p_img, p_mask = self.engine._tp(images), (None if masks is None else self.engine._tp(masks))
+            if images.is_cuda:                                                           # (torch's stream, see Correlator.add)
+                torch.cuda.current_stream(images.device).synchronize()
+        else:
+            p_img, p_mask = _lib.ptr(images), _lib.ptr(masks)
+        return images, masks, P, f32, on_device, p_img, p_mask
+
+    def run(self, images, masks=None):
+        images, masks, P, f32, on_device, p_img, p_mask = self.prepare(images, masks)
+        shape = (P, self.n_q, self.n_phi)
+        if on_device:
+            import torch
+            out_i = torch.empty(shape, dtype=torch.float64, device=images.device)
+            out_m = torch.empty(shape, dtype=torch.uint8, device=images.device)
+            p_oi, p_om = self.engine._tp(out_i), self.engine._tp(out_m)
+        else:
+            out_i, out_m = np.empty(shape), np.empty(shape, np.uint8)
+            p_oi, p_om = _lib.ptr(out_i), _lib.ptr(out_m)
+        bad = C.c_int64(0)
+        self.engine._ck(self.lib.mtip_resample_run(self.handle, P, p_img, int(f32), p_mask, p_oi, p_om, C.byref(bad)))
+        if bad.value:
+            raise ValueError(BAD_MASK + f' after the resampling ({bad.value} points)')
+        return out_i, out_m
+
+    def static_mask(self):
+        """the polar mask (n_q, n_phi) uint8 of the static case, as a numpy array"""
+        if getattr(self, '_static', None) is None:
+            if self.threshold:
+                raise ValueError('correlate: with intensity_pixel_threshold on the mask is not static')
+            self._static = self.run(np.zeros((1, self.H, self.W), np.float32))[1][0]
+        return self._static
+
+
 class Correlator:
     """Accumulates patterns on the engine's device: ``add(images, masks)`` any number of times, ``result()`` for the reference's result
-    dict (it goes through ``io.load_ccd(..., 'direct')`` into ``extract_from_cross_correlation`` unchanged).  ``partial()`` /
+    dict (it goes through ``io.load_ccd(..., 'direct')`` into ``extract_from_cross_correlation`` unchanged);
+    ``add_detector(images, masks=None)`` takes detector frames through a ``Resampler`` (binary_mask / background are its).  ``partial()`` /
     ``merge(partials)`` make the accumulation additive over ranks or GPUs that each take a share of the patterns.
 
     shared_mask=True: one mask for every pattern; its pair counts are computed once per handle.  An active radial pixel filter makes
     masks per pattern, so the flag is ignored then."""
 
-    def __init__(self, engine, settings=None, shared_mask=False):
+    def __init__(self, engine, settings=None, shared_mask=False, binary_mask=None, background=None):
         self.engine = engine
+        self._frame_arrays = (binary_mask, background)
+        self.resampler = None
         self.lib = engine.lib
         self.opt = opt = resolve_correlate(settings)
         self.compute = analyse_dependencies(opt['compute'])
@@ -157,6 +316,9 @@ class Correlator:
 
     # ------------------------------------------------------------------ bookkeeping
     def close(self):
+        if getattr(self, 'resampler', None) is not None:
+            self.resampler.close()
+            self.resampler = None
         if getattr(self, 'handle', None):
             self.lib.mtip_correlate_destroy(self.handle)
             self.handle = None
@@ -194,7 +356,7 @@ class Correlator:
             images = images.to(torch.float64).contiguous()
             masks = torch.as_tensor(masks, device=images.device)
             if bool(((masks != 0) & (masks != 1)).any()):
-                raise ValueError('correlate: mask values other than 0 / 1')
+                raise ValueError(BAD_MASK)
             masks = masks.to(torch.uint8)
             shape, mshape = tuple(images.shape), tuple(masks.shape)
         else:
@@ -206,7 +368,7 @@ class Correlator:
             images = _lib.as_f64(images)
             masks = np.asarray(masks)
             if ((masks != 0) & (masks != 1)).any():
-                raise ValueError('correlate: mask values other than 0 / 1')
+                raise ValueError(BAD_MASK)
             masks = masks.astype(np.uint8)
             shape, mshape = images.shape, masks.shape
         if len(shape) != 3 or tuple(shape[1:]) != ring:
@@ -235,6 +397,30 @@ class Correlator:
             masks = np.ascontiguousarray(masks)
             p_img, p_mask = _lib.ptr(images), _lib.ptr(masks)
         self._ck(self.lib.mtip_correlate_add(self.handle, P, p_img, p_mask))
+        return self
+
+    def add_detector(self, images, masks=None):
+        """detector frames (P, H, W) float32 / float64 and optional initial masks (P, H, W) or (H, W) of 0 / 1 (default: ones): the
+        same as ``add(*resampler.run(images, masks))``, bit for bit, without the polar arrays leaving the device.  A handle made
+        with shared_mask takes frames only where the mask is static (intensity_pixel_threshold off, no masks)."""
+        if self.resampler is None:
+            self.resampler = Resampler(self.engine, self.opt, *self._frame_arrays)
+        rs = self.resampler
+        if self.shared_mask and not rs.is_static(masks):
+            raise ValueError('correlate: shared_mask: detector frames are taken only where the mask is static; it is not with '
+                             'intensity_pixel_threshold on or with masks given')
+        images, masks, P, f32, _, p_img, p_mask = rs.prepare(images, masks)
+        if self.shared_mask:
+            host = rs.static_mask()[None]
+            if self._mask0 is None:
+                self._mask0 = host.copy()
+            elif not np.array_equal(self._mask0, host):
+                raise ValueError('correlate: shared_mask: the mask differs from the one of the first batch')
+        bad = C.c_int64(0)
+        rc = self.lib.mtip_correlate_add_detector(self.handle, rs.handle, P, p_img, int(f32), p_mask, C.byref(bad))
+        if bad.value:
+            raise ValueError(BAD_MASK + f' after the resampling ({bad.value} points)')
+        self._ck(rc)
         return self
 
     def partial(self):

@@ -115,9 +115,15 @@ def default_settings():
 
 def correlate_default_settings():
     """the keys of the ``fxs correlate`` worker that the device route reads, with the reference's defaults
-    (``xframe/projects/fxs/settings/correlate/default_0.01.yaml``).  What belongs to the Cartesian stage (file lists,
-    intensity_pixel_threshold, binary mask, background, interpolation order) stays with the caller."""
+    (``xframe/projects/fxs/settings/correlate/default_0.01.yaml``).  The Cartesian stage is part of it: intensity_pixel_threshold
+    [on, lo, hi] masks pixels of the raw frame outside lo .. hi, use_binary_mask / subtract_background switch on the arrays handed to
+    ``Resampler``, interpolation_order (0 .. 5) is the spline order of the polar resampling.  File lists and process splitting stay
+    with the caller (``read_raw_images`` reads the frames)."""
     return {
+        'intensity_pixel_threshold': [False, 4.0, 1e4],
+        'use_binary_mask': False,
+        'subtract_background': False,
+        'interpolation_order': 2,
         'compute': ['is_good', 'waxs_aver', 'ccf_q1q2'],
         'intensity_radial_pixel_filter': [False, ['average_sigma', 3]],
         'ROI_normalization': [False, 0.3, 0.9],
