@@ -3,6 +3,7 @@
 // ucontext fibers scheduled round-robin, yielding at barriers and wave collectives.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <string>
 #include <sys/mman.h>
@@ -265,6 +266,8 @@ void launch(dim3 grid, dim3 block, size_t smem, const std::function<void()>& bod
 namespace emul {
 static std::mutex guard_mutex;
 static std::map<void*, std::pair<void*, size_t>> guard_blocks;
+static std::atomic<long long> live_blocks{0};          // device_alloc blocks not yet freed (tests/test_emul_ownership.py)
+static std::atomic<long long> made_blocks{0};          // device_alloc blocks ever made
 
 static bool guard_on() {
     static const bool on = [] { const char* e = std::getenv("MTIP_EMUL_GUARD"); return e != nullptr && std::atoi(e) != 0; }();
@@ -272,7 +275,11 @@ static bool guard_on() {
 }
 
 void* device_alloc(size_t n) {
-    if (!guard_on()) return std::calloc(1, n ? n : 1);
+    if (!guard_on()) {
+        void* p = std::calloc(1, n ? n : 1);
+        if (p) ++live_blocks, ++made_blocks;
+        return p;
+    }
     const size_t page = 4096, len = (std::max<size_t>(n, 1) + 7) & ~size_t(7), body = (len + page - 1) / page * page;
     char* base = (char*)mmap(nullptr, body + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
     if (base == MAP_FAILED) return nullptr;
@@ -280,11 +287,13 @@ void* device_alloc(size_t n) {
     void* p = base + body - len;
     std::lock_guard<std::mutex> guard(guard_mutex);
     guard_blocks[p] = {base, body + page};
+    ++live_blocks, ++made_blocks;
     return p;
 }
 
 void device_free(void* p) {
     if (p == nullptr) return;
+    --live_blocks;
     {
         std::lock_guard<std::mutex> guard(guard_mutex);
         auto it = guard_blocks.find(p);
@@ -300,6 +309,11 @@ void device_free(void* p) {
 
 // tells the Python side that "device" pointers of this library are host pointers (torch CPU tensors, not cuda ones)
 extern "C" int mtip_emulated(void) { return 1; }
+
+// "device" allocations alive right now: a handle that is destroyed must bring it back to where it was before its creation
+extern "C" long long mtip_emul_live_allocations(void) { return emul::live_blocks.load(); }
+// ... and every one made so far: tells a buffer that was replaced from one that was left alone
+extern "C" long long mtip_emul_total_allocations(void) { return emul::made_blocks.load(); }
 
 // launch log (kernel choice tests): copies up to cap - 1 bytes of it into buf (NUL terminated), returns its full length
 extern "C" int mtip_emul_launch_log(char* buf, int cap) {

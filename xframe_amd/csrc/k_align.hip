@@ -201,16 +201,20 @@ int mtip_set_so3_tables(mtip_ctx* c, int bw, const double* d_table) {
     (void)hipSetDevice(c->device);
     const int nb = 2 * bw, ntab = so3_ntab(c->L), M = 2 * c->L + 1;
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    for (void* p : {(void*)c->d_so3_d, (void*)c->d_so3_tw, (void*)c->d_so3_T, (void*)c->d_so3_S, (void*)c->d_so3_P, (void*)c->d_so3_C, (void*)c->d_so3_D})
-        if (p) (void)hipFree(p);
-    c->d_so3_d = nullptr; c->d_so3_tw = nullptr; c->d_so3_T = nullptr; c->d_so3_S = nullptr; c->d_so3_P = nullptr; c->d_so3_C = nullptr; c->d_so3_D = nullptr;
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_so3_d, (size_t)nb * ntab * sizeof(double)));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_so3_tw, (size_t)nb * sizeof(double2)));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_so3_T, (size_t)c->B * ntab * sizeof(double2)));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_so3_D, (size_t)c->B * ntab * sizeof(double2)));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_so3_S, (size_t)c->B * nb * M * M * sizeof(double2)));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_so3_P, (size_t)c->B * nb * M * nb * sizeof(double2)));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_so3_C, (size_t)c->B * nb * nb * nb * sizeof(double)));
+    c->d_so3_d.reset();                                  // all of the old tables go before the first new one comes
+    c->d_so3_tw.reset();
+    c->d_so3_T.reset();
+    c->d_so3_D.reset();
+    c->d_so3_S.reset();
+    c->d_so3_P.reset();
+    c->d_so3_C.reset();
+    MTIP_HIP_CHECK(c, c->d_so3_d.alloc((size_t)nb * ntab));
+    MTIP_HIP_CHECK(c, c->d_so3_tw.alloc((size_t)nb));
+    MTIP_HIP_CHECK(c, c->d_so3_T.alloc((size_t)c->B * ntab));
+    MTIP_HIP_CHECK(c, c->d_so3_D.alloc((size_t)c->B * ntab));
+    MTIP_HIP_CHECK(c, c->d_so3_S.alloc((size_t)c->B * nb * M * M));
+    MTIP_HIP_CHECK(c, c->d_so3_P.alloc((size_t)c->B * nb * M * nb));
+    MTIP_HIP_CHECK(c, c->d_so3_C.alloc((size_t)c->B * nb * nb * nb));
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_so3_d, d_table, (size_t)nb * ntab * sizeof(double), hipMemcpyHostToDevice));
     std::vector<double2> tw(nb);
     const double pi = 3.14159265358979323846;
@@ -257,8 +261,8 @@ int mtip_op_so3_find_rotation(mtip_ctx* c, const mtip_cdouble* ref, const mtip_c
     const int rc = so3_correlate(c, ref, sig, r_lo, r_hi);
     if (rc != MTIP_OK) return rc;
     // (d_so3_P is free again: the first words of it take the B results)
-    long long* d_arg = reinterpret_cast<long long*>(c->d_so3_P);
-    double* d_max = reinterpret_cast<double*>(c->d_so3_P) + c->B;
+    long long* d_arg = reinterpret_cast<long long*>((double2*)c->d_so3_P);
+    double* d_max = reinterpret_cast<double*>((double2*)c->d_so3_P) + c->B;
     hipLaunchKernelGGL(k_so3_argmax, dim3((unsigned)c->B), dim3(1024), 0, c->stream, (const double*)c->d_so3_C, nb, d_arg, d_max);
     MTIP_HIP_CHECK(c, mtip_copy(c, arg, d_arg, (size_t)c->B * sizeof(long long), hipMemcpyDeviceToHost));
     MTIP_HIP_CHECK(c, mtip_copy(c, vmax, d_max, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost));
@@ -289,7 +293,7 @@ int mtip_op_rotate_coefficients_grid(mtip_ctx* c, const mtip_cdouble* coeff, con
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_c[0], coeff, (size_t)c->B * c->C * sizeof(double2), hipMemcpyHostToDevice));
     // (angles and indices are host arrays of B entries: staged in the head of d_so3_S)
-    double* d_al = reinterpret_cast<double*>(c->d_so3_S);
+    double* d_al = reinterpret_cast<double*>((double2*)c->d_so3_S);
     double* d_ga = d_al + c->B;
     int* d_bi = reinterpret_cast<int*>(d_ga + c->B);
     MTIP_HIP_CHECK(c, mtip_copy(c, d_al, alpha, (size_t)c->B * sizeof(double), hipMemcpyHostToDevice));

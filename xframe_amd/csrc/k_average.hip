@@ -231,12 +231,12 @@ int mtip_op_grid_stats(mtip_ctx* c, const mtip_cdouble* grids, int n, const mtip
     DevView vr(c, ref, c->G * sizeof(double2), true, false);
     DevView vw(c, radial_w, c->N * sizeof(double), true, false);
     DevView vt(c, theta_w, c->nt * sizeof(double), true, false);
-    double* d_part = nullptr;
+    DevBuf<double> d_part;
     AV_HIP(c, vg.err);
     AV_HIP(c, vr.err);
     AV_HIP(c, vw.err);
     AV_HIP(c, vt.err);
-    AV_HIP(c, hipMalloc((void**)&d_part, ((size_t)n * nblk + n) * AV_NSTAT * sizeof(double)));
+    AV_HIP(c, d_part.alloc(((size_t)n * nblk + n) * AV_NSTAT));
     double* d_out = d_part + (size_t)n * nblk * AV_NSTAT;
     hipLaunchKernelGGL(k_av_stats, dim3((unsigned)nblk, (unsigned)n), dim3(AV_THREADS), 0, c->stream, (const double2*)vg.dev,
                        (const double2*)vr.dev, (const double*)vw.dev, (const double*)vt.dev, (const double*)c->d_r,
@@ -244,7 +244,6 @@ int mtip_op_grid_stats(mtip_ctx* c, const mtip_cdouble* grids, int n, const mtip
     hipLaunchKernelGGL(k_av_stats_finish, dim3((unsigned)n), dim3(64), 0, c->stream, (const double*)d_part, nblk, d_out);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = mtip_copy(c, out, d_out, (size_t)n * AV_NSTAT * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d_part);
     AV_HIP(c, e);
     AV_HIP(c, hipGetLastError());
     return MTIP_OK;
@@ -303,14 +302,14 @@ int mtip_op_prtf(mtip_ctx* c, const mtip_cdouble* a1, const mtip_cdouble* a2, co
     AV_HIP(c, v2.err);
     AV_HIP(c, v3.err);
     AV_HIP(c, v4.err);
-    double* d_out = nullptr;
-    AV_HIP(c, hipMalloc((void**)&d_out, (size_t)c->N * 3 * sizeof(double)));
+    DevBuf<double> out_buf;
+    AV_HIP(c, out_buf.alloc((size_t)c->N * 3));
+    double* d_out = out_buf;
     hipLaunchKernelGGL(k_av_prtf, dim3((unsigned)c->N), dim3(AV_THREADS), 0, c->stream, (const double2*)v1.dev, (const double2*)v2.dev,
                        (const double2*)v3.dev, (const double2*)v4.dev, c->nt * c->np, reinterpret_cast<double2*>(d_out), d_out + 2 * (size_t)c->N);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = mtip_copy(c, mean, d_out, (size_t)c->N * sizeof(double2), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = mtip_copy(c, std_dev, d_out + 2 * (size_t)c->N, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
     AV_HIP(c, e);
     AV_HIP(c, hipGetLastError());
     return MTIP_OK;

@@ -36,16 +36,16 @@ struct mtip_correlate {
     mtip_correlate_cfg cfg{};
     int m = 0, log2n = 0;              // n_phi / 2
     size_t n_acc = 0;                  // n_q1 n_q2 n_phi
-    double* d_sum = nullptr;
-    int* d_cnt = nullptr;
-    double* d_M = nullptr;             // shared mask: M(q1, q2, Delta), filled by the first batch
+    DevBuf<double> d_sum;
+    DevBuf<int> d_cnt;
+    DevBuf<double> d_M;                // shared mask: M(q1, q2, Delta), filled by the first batch
     bool have_M = false;
-    int *d_q1 = nullptr, *d_q2 = nullptr;
-    double* d_factor = nullptr;        // (n_q, n_phi) polarisation x solid angle
-    double2* d_tw = nullptr;           // exp(-2 pi i k / n_phi), k < n_phi / 2
-    double2 *d_F = nullptr, *d_G = nullptr;   // (COR_CHUNK, n_q, m + 1)
-    uint8_t* d_mw = nullptr;           // (COR_CHUNK, n_q, n_phi) filtered masks
-    double *d_rc = nullptr, *d_rs = nullptr;  // (COR_CHUNK, n_q) ring mask counts / masked ring sums
+    DevBuf<int> d_q1, d_q2;
+    DevBuf<double> d_factor;           // (n_q, n_phi) polarisation x solid angle
+    DevBuf<double2> d_tw;              // exp(-2 pi i k / n_phi), k < n_phi / 2
+    DevBuf<double2> d_F, d_G;          // (COR_CHUNK, n_q, m + 1)
+    DevBuf<uint8_t> d_mw;              // (COR_CHUNK, n_q, n_phi) filtered masks
+    DevBuf<double> d_rc, d_rs;         // (COR_CHUNK, n_q) ring mask counts / masked ring sums
     std::vector<int32_t> good;         // every pattern added or merged so far
     std::vector<double> waxs;
 };
@@ -370,33 +370,15 @@ __global__ void __launch_bounds__(COR_RT) k_corr_final(CorFinalArgs a) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
-static inline void cor_free(mtip_correlate* h) {
-    for (void* p : {(void*)h->d_sum, (void*)h->d_cnt, (void*)h->d_M, (void*)h->d_q1, (void*)h->d_q2, (void*)h->d_factor, (void*)h->d_tw,
-                    (void*)h->d_F, (void*)h->d_G, (void*)h->d_mw, (void*)h->d_rc, (void*)h->d_rs})
-        if (p) (void)hipFree(p);
-    delete h;
-}
-
 // a copy between the caller's buffer (host or device memory) and a host vector of the handle
 static inline hipError_t cor_host_copy(mtip_ctx* c, void* dst, const void* src, size_t n, const void* callers) {
-    hipPointerAttribute_t at;
-    const bool is_dev = hipPointerGetAttributes(&at, callers) == hipSuccess && at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
 #ifdef __HIPCC__
-    if (is_dev) return mtip_copy(c, dst, src, n, hipMemcpyDefault);
+    if (mtip_is_device_pointer(callers)) return mtip_copy(c, dst, src, n, hipMemcpyDefault);
 #endif
-    (void)is_dev;
     (void)c;
+    (void)callers;
     std::memcpy(dst, src, n);
     return hipSuccess;
-}
-
-static inline size_t cor_free_memory() {
-#ifdef __HIPCC__
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess) return fr;
-#endif
-    return (size_t)8 << 30;            // (the CPU build of the tests: a fixed budget)
 }
 
 extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correlate_cfg* cfg, const int32_t* q1_pos, const int32_t* q2_pos,
@@ -434,10 +416,10 @@ extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correla
     h->n_acc = (size_t)cfg->n_q1 * cfg->n_q2 * n;
     const bool shared = cfg->shared_mask && !cfg->filter_kind;
     h->cfg.shared_mask = shared ? 1 : 0;
-    const size_t rows = (size_t)COR_CHUNK * cfg->n_q, spec = rows * (h->m + 1) * sizeof(double2);
+    const size_t rows = (size_t)COR_CHUNK * cfg->n_q, n_spec = rows * (h->m + 1), spec = n_spec * sizeof(double2);
     const size_t acc = h->n_acc * 12, tab = shared ? h->n_acc * 8 : 0;
     const size_t work = spec * (shared ? 1 : 2) + spec / COR_CHUNK + rows * n + rows * 16 + (factor ? (size_t)cfg->n_q * n * 8 : 0);
-    const size_t fr = cor_free_memory();
+    const size_t fr = mtip_free_memory();
     if (acc + tab + work > fr) {
         snprintf(msg, sizeof msg,
                  "correlate_create: the accumulator of %d x %d pairs x %d angles needs %.3f GB (sum f64 + count int32%s) and the work "
@@ -445,7 +427,7 @@ extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correla
                  cfg->n_q1, cfg->n_q2, n, (double)(acc + tab) * 1e-9, shared ? " + shared-mask table f64" : "", (double)work * 1e-9,
                  (double)fr * 1e-9);
         c->err = msg;
-        cor_free(h);
+        delete h;
         return nullptr;
     }
     std::vector<double2> tw((size_t)h->m);
@@ -453,18 +435,18 @@ extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correla
         const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
         tw[k] = make_double2((double)cosl(ang), (double)sinl(ang));
     }
-    hipError_t e = hipMalloc(&h->d_sum, h->n_acc * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&h->d_cnt, h->n_acc * sizeof(int));
-    if (e == hipSuccess && shared) e = hipMalloc(&h->d_M, h->n_acc * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&h->d_q1, (size_t)cfg->n_q1 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&h->d_q2, (size_t)cfg->n_q2 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&h->d_tw, tw.size() * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc(&h->d_F, spec);
-    if (e == hipSuccess) e = hipMalloc(&h->d_G, shared ? spec / COR_CHUNK : spec);
-    if (e == hipSuccess && cfg->filter_kind) e = hipMalloc(&h->d_mw, rows * n);
-    if (e == hipSuccess) e = hipMalloc(&h->d_rc, rows * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&h->d_rs, rows * sizeof(double));
-    if (e == hipSuccess && factor) e = hipMalloc(&h->d_factor, (size_t)cfg->n_q * n * sizeof(double));
+    hipError_t e = h->d_sum.alloc(h->n_acc);
+    if (e == hipSuccess) e = h->d_cnt.alloc(h->n_acc);
+    if (e == hipSuccess && shared) e = h->d_M.alloc(h->n_acc);
+    if (e == hipSuccess) e = h->d_q1.alloc((size_t)cfg->n_q1);
+    if (e == hipSuccess) e = h->d_q2.alloc((size_t)cfg->n_q2);
+    if (e == hipSuccess) e = h->d_tw.alloc(tw.size());
+    if (e == hipSuccess) e = h->d_F.alloc(n_spec);
+    if (e == hipSuccess) e = h->d_G.alloc(shared ? n_spec / COR_CHUNK : n_spec);
+    if (e == hipSuccess && cfg->filter_kind) e = h->d_mw.alloc(rows * n);
+    if (e == hipSuccess) e = h->d_rc.alloc(rows);
+    if (e == hipSuccess) e = h->d_rs.alloc(rows);
+    if (e == hipSuccess && factor) e = h->d_factor.alloc((size_t)cfg->n_q * n);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_sum, 0, h->n_acc * sizeof(double), c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_cnt, 0, h->n_acc * sizeof(int), c->stream);
     if (e == hipSuccess) e = mtip_copy(c, h->d_q1, q1_pos, (size_t)cfg->n_q1 * sizeof(int), hipMemcpyHostToDevice);
@@ -474,7 +456,7 @@ extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correla
     if (e != hipSuccess) {
         snprintf(msg, sizeof msg, "correlate_create: %s (accumulator %.3f GB)", hipGetErrorString(e), (double)(acc + tab) * 1e-9);
         c->err = msg;
-        cor_free(h);
+        delete h;
         return nullptr;
     }
     return h;
@@ -484,7 +466,7 @@ extern "C" void mtip_correlate_destroy(mtip_correlate* h) {
     if (!h) return;
     (void)hipSetDevice(h->c->device);
     (void)hipStreamSynchronize(h->c->stream);
-    cor_free(h);
+    delete h;
 }
 
 static inline void cor_launch_pair(mtip_correlate* h, const CorPairArgs& a) {
@@ -511,11 +493,11 @@ extern "C" int mtip_correlate_add(mtip_correlate* h, int n_patterns, const doubl
     const bool shared = f.shared_mask != 0;
     DevView v_img(c, images, (size_t)n_patterns * ring * sizeof(double), true, false);
     DevView v_mask(c, masks, (shared ? 1 : (size_t)n_patterns) * ring, true, false);
-    int* d_good = nullptr;
-    double* d_waxs = nullptr;
+    DevBuf<int> d_good;
+    DevBuf<double> d_waxs;
     hipError_t e = v_img.err != hipSuccess ? v_img.err : v_mask.err;
-    if (e == hipSuccess) e = hipMalloc(&d_good, (size_t)n_patterns * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d_waxs, (size_t)n_patterns * f.n_q * sizeof(double));
+    if (e == hipSuccess) e = d_good.alloc((size_t)n_patterns);
+    if (e == hipSuccess) e = d_waxs.alloc((size_t)n_patterns * f.n_q);
     CorRingArgs r{};
     r.mw = h->d_mw;
     r.rc = h->d_rc;
@@ -596,8 +578,6 @@ extern "C" int mtip_correlate_add(mtip_correlate* h, int n_patterns, const doubl
         e = mtip_copy(c, h->good.data() + old, d_good, (size_t)n_patterns * sizeof(int), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = mtip_copy(c, h->waxs.data() + old * f.n_q, d_waxs, (size_t)n_patterns * f.n_q * sizeof(double), hipMemcpyDeviceToHost);
     }
-    if (d_good) (void)hipFree(d_good);
-    if (d_waxs) (void)hipFree(d_waxs);
     if (e != hipSuccess) {
         c->err = std::string("correlate_add: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? MTIP_ENOMEM : MTIP_EHIP;

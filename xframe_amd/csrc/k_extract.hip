@@ -154,51 +154,41 @@ extern "C" int mtip_op_hermitian_eig(mtip_ctx* c, int n, int n_mat, const mtip_c
         return MTIP_EINVAL;
     }
     (void)hipSetDevice(c->device);
-    double2 *dW = nullptr, *dV = nullptr;
-    double *dl = nullptr, *dshift = nullptr, *dres = nullptr;
+    DevBuf<double2> dW, dV;
+    DevBuf<double> dl, dshift, dres;
     const size_t nn = (size_t)n_mat * n * n, mat = (size_t)n * n;
-    int rc = MTIP_OK;
-    if (hipMalloc((void**)&dW, nn * sizeof(double2)) != hipSuccess || hipMalloc((void**)&dV, nn * sizeof(double2)) != hipSuccess ||
-        hipMalloc((void**)&dl, (size_t)n_mat * n * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&dshift, (size_t)n_mat * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&dres, (size_t)n_mat * sizeof(double)) != hipSuccess) {
+    if (dW.alloc(nn) != hipSuccess || dV.alloc(nn) != hipSuccess || dl.alloc((size_t)n_mat * n) != hipSuccess ||
+        dshift.alloc((size_t)n_mat) != hipSuccess || dres.alloc((size_t)n_mat) != hipSuccess) {
         c->err = "hermitian_eig: out of device memory";
-        rc = MTIP_ENOMEM;
+        return MTIP_ENOMEM;
     }
-    if (rc == MTIP_OK) {
-        std::vector<double> resid(n_mat, 0.0);
-        hipError_t e = herm_eig_pass(c, n, n_mat, A, nullptr, dW, dV, dl, dshift, dres, eigvals, eigvecs, resid.data());
-        std::vector<int> again;
-        for (int k = 0; k < n_mat && e == hipSuccess; ++k)
-            if (!(resid[k] <= HE_RESID_TOL * n)) again.push_back(k);
-        if (e == hipSuccess && !again.empty()) {                                       // +x / -x eigenvalue pairs: shifted repeat
-            const int m = (int)again.size();
-            std::vector<mtip_cdouble> sub((size_t)m * mat), vec((size_t)m * mat);
-            std::vector<double> shift(m), val((size_t)m * n), res2(m);
-            for (int i = 0; i < m; ++i) {
-                const mtip_cdouble* src = A + (size_t)again[i] * mat;
-                double f2 = 0.0;
-                for (size_t q = 0; q < mat; ++q) f2 += src[q].re * src[q].re + src[q].im * src[q].im;
-                shift[i] = sqrt(f2);
-                std::copy(src, src + mat, sub.begin() + (size_t)i * mat);
-            }
-            e = herm_eig_pass(c, n, m, sub.data(), shift.data(), dW, dV, dl, dshift, dres, val.data(), vec.data(), res2.data());
-            for (int i = 0; i < m && e == hipSuccess; ++i) {
-                std::copy(val.begin() + (size_t)i * n, val.begin() + (size_t)(i + 1) * n, eigvals + (size_t)again[i] * n);
-                std::copy(vec.begin() + (size_t)i * mat, vec.begin() + (size_t)(i + 1) * mat, eigvecs + (size_t)again[i] * mat);
-            }
+    std::vector<double> resid(n_mat, 0.0);
+    hipError_t e = herm_eig_pass(c, n, n_mat, A, nullptr, dW, dV, dl, dshift, dres, eigvals, eigvecs, resid.data());
+    std::vector<int> again;
+    for (int k = 0; k < n_mat && e == hipSuccess; ++k)
+        if (!(resid[k] <= HE_RESID_TOL * n)) again.push_back(k);
+    if (e == hipSuccess && !again.empty()) {                                           // +x / -x eigenvalue pairs: shifted repeat
+        const int m = (int)again.size();
+        std::vector<mtip_cdouble> sub((size_t)m * mat), vec((size_t)m * mat);
+        std::vector<double> shift(m), val((size_t)m * n), res2(m);
+        for (int i = 0; i < m; ++i) {
+            const mtip_cdouble* src = A + (size_t)again[i] * mat;
+            double f2 = 0.0;
+            for (size_t q = 0; q < mat; ++q) f2 += src[q].re * src[q].re + src[q].im * src[q].im;
+            shift[i] = sqrt(f2);
+            std::copy(src, src + mat, sub.begin() + (size_t)i * mat);
         }
-        if (e != hipSuccess) {
-            c->err = std::string("hermitian_eig: ") + hipGetErrorString(e);
-            rc = MTIP_EHIP;
+        e = herm_eig_pass(c, n, m, sub.data(), shift.data(), dW, dV, dl, dshift, dres, val.data(), vec.data(), res2.data());
+        for (int i = 0; i < m && e == hipSuccess; ++i) {
+            std::copy(val.begin() + (size_t)i * n, val.begin() + (size_t)(i + 1) * n, eigvals + (size_t)again[i] * n);
+            std::copy(vec.begin() + (size_t)i * mat, vec.begin() + (size_t)(i + 1) * mat, eigvecs + (size_t)again[i] * mat);
         }
     }
-    if (dW) (void)hipFree(dW);
-    if (dV) (void)hipFree(dV);
-    if (dl) (void)hipFree(dl);
-    if (dshift) (void)hipFree(dshift);
-    if (dres) (void)hipFree(dres);
-    return rc;
+    if (e != hipSuccess) {
+        c->err = std::string("hermitian_eig: ") + hipGetErrorString(e);
+        return MTIP_EHIP;
+    }
+    return MTIP_OK;
 }
 
 // ---- real symmetric matrices up to 128 x 128: LDS-resident one-sided Jacobi (round 3) ---------------------------------------
@@ -488,50 +478,43 @@ static int sym_eig_blocked(mtip_ctx* c, int n, int n_mat, const double* dA, doub
     }
     for (auto& pr : pairs)                                                        // the kept (first) block in .x must exist
         if (pr.x < 0) std::swap(pr.x, pr.y);
-    int2* d_pairs = nullptr;
-    int* d_flags = nullptr;
-    double *dW = nullptr, *d_shift = nullptr;
-    int rc = 0;
-    if (hipMalloc((void**)&d_pairs, pairs.size() * sizeof(int2)) != hipSuccess || hipMalloc((void**)&d_flags, (size_t)n_mat * sizeof(int)) != hipSuccess ||
-        hipMalloc((void**)&dW, (size_t)n_mat * n * n * sizeof(double)) != hipSuccess || hipMalloc((void**)&d_shift, (size_t)n_mat * sizeof(double)) != hipSuccess)
-        rc = -2;
-    if (rc == 0 && mtip_copy(c, d_pairs, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) rc = -3;
-    if (rc == 0) {
-        hipLaunchKernelGGL(k_sym_eig_shift, dim3((unsigned)n_mat), dim3(1024), 0, c->stream, dA, dW, d_shift, n);
-        const int nr = (n + 15) / 16;
-        std::vector<int> flags(n_mat);
-        int outer = 0;
-        for (; outer < SB_MAX_OUTER; ++outer) {
-            (void)hipMemsetAsync(d_flags, 0, (size_t)n_mat * sizeof(int), c->stream);
-            for (int r = 0; r < n_rounds; ++r) {
-                const int2* pp = d_pairs + (size_t)r * n_pairs;
-                if (nr <= 10) launch_sym_eig_block<10>(c, dW, n, pp, n_pairs, n_mat, d_flags);
-                else if (nr <= 12) launch_sym_eig_block<12>(c, dW, n, pp, n_pairs, n_mat, d_flags);
-                else if (nr <= 14) launch_sym_eig_block<14>(c, dW, n, pp, n_pairs, n_mat, d_flags);
-                else if (nr <= 16) launch_sym_eig_block<16>(c, dW, n, pp, n_pairs, n_mat, d_flags);
-                else launch_sym_eig_block<18>(c, dW, n, pp, n_pairs, n_mat, d_flags);
-            }
-            if (mtip_copy(c, flags.data(), d_flags, (size_t)n_mat * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = -3;
-                break;
-            }
-            bool any = false;
-            for (int f : flags) any = any || f != 0;
-            if (!any) {
-                ++outer;
-                break;
-            }
+    DevBuf<int2> d_pairs;
+    DevBuf<int> d_flags;
+    DevBuf<double> dW, d_shift;
+    if (d_pairs.alloc(pairs.size()) != hipSuccess || d_flags.alloc((size_t)n_mat) != hipSuccess ||
+        dW.alloc((size_t)n_mat * n * n) != hipSuccess || d_shift.alloc((size_t)n_mat) != hipSuccess)
+        return -2;
+    if (mtip_copy(c, d_pairs, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) return -3;
+    hipLaunchKernelGGL(k_sym_eig_shift, dim3((unsigned)n_mat), dim3(1024), 0, c->stream, dA, dW, d_shift, n);
+    const int nr = (n + 15) / 16;
+    std::vector<int> flags(n_mat);
+    int rc = 0, outer = 0;
+    for (; outer < SB_MAX_OUTER; ++outer) {
+        (void)hipMemsetAsync(d_flags, 0, (size_t)n_mat * sizeof(int), c->stream);
+        for (int r = 0; r < n_rounds; ++r) {
+            const int2* pp = d_pairs + (size_t)r * n_pairs;
+            if (nr <= 10) launch_sym_eig_block<10>(c, dW, n, pp, n_pairs, n_mat, d_flags);
+            else if (nr <= 12) launch_sym_eig_block<12>(c, dW, n, pp, n_pairs, n_mat, d_flags);
+            else if (nr <= 14) launch_sym_eig_block<14>(c, dW, n, pp, n_pairs, n_mat, d_flags);
+            else if (nr <= 16) launch_sym_eig_block<16>(c, dW, n, pp, n_pairs, n_mat, d_flags);
+            else launch_sym_eig_block<18>(c, dW, n, pp, n_pairs, n_mat, d_flags);
         }
-        if (rc == 0) {
-            hipLaunchKernelGGL(k_sym_eig_finish, dim3((unsigned)n_mat), dim3(1024), 0, c->stream, (const double*)dW, (const double*)d_shift, dU, dl, n);
-            rc = outer;
+        if (mtip_copy(c, flags.data(), d_flags, (size_t)n_mat * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
+            rc = -3;
+            break;
+        }
+        bool any = false;
+        for (int f : flags) any = any || f != 0;
+        if (!any) {
+            ++outer;
+            break;
         }
     }
-    (void)hipStreamSynchronize(c->stream);
-    if (d_pairs) (void)hipFree(d_pairs);
-    if (d_flags) (void)hipFree(d_flags);
-    if (dW) (void)hipFree(dW);
-    if (d_shift) (void)hipFree(d_shift);
+    if (rc == 0) {
+        hipLaunchKernelGGL(k_sym_eig_finish, dim3((unsigned)n_mat), dim3(1024), 0, c->stream, (const double*)dW, (const double*)d_shift, dU, dl, n);
+        rc = outer;
+    }
+    (void)hipStreamSynchronize(c->stream);                                        // the work arrays go when this returns
     return rc;
 }
 
@@ -547,46 +530,40 @@ extern "C" int mtip_op_symmetric_eig(mtip_ctx* c, int n, int n_mat, const double
         c->err = "symmetric_eig: pairing schedule";
         return MTIP_ENOMEM;
     }
-    double *dA = nullptr, *dU = nullptr, *dl = nullptr;
+    DevBuf<double> dA, dU, dl;
     const size_t nn = (size_t)n_mat * n * n;
-    int rc = MTIP_OK;
-    if (hipMalloc((void**)&dA, nn * sizeof(double)) != hipSuccess || hipMalloc((void**)&dU, nn * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&dl, (size_t)n_mat * n * sizeof(double)) != hipSuccess) {
+    if (dA.alloc(nn) != hipSuccess || dU.alloc(nn) != hipSuccess || dl.alloc((size_t)n_mat * n) != hipSuccess) {
         c->err = "symmetric_eig: out of device memory";
-        rc = MTIP_ENOMEM;
+        return MTIP_ENOMEM;
     }
-    if (rc == MTIP_OK) {
-        hipError_t e = mtip_copy(c, dA, A, nn * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess && n > SE_MAX_N) {
-            ProfScope ps(c, "sym_eig");
-            const int outer = sym_eig_blocked(c, n, n_mat, dA, dU, dl);
-            if (outer < 0) {
-                c->err = "symmetric_eig: blocked solve failed (device memory or block schedule)";
-                rc = MTIP_EHIP;
-            } else if (c->d_sweeps != nullptr) {
-                (void)mtip_copy(c, c->d_sweeps, &outer, sizeof(int), hipMemcpyHostToDevice);
-            }
-        } else if (e == hipSuccess) {
-            // all pairs of a round in one workgroup: floor(n / 2) groups of 16 lanes (the schedule's group count for n columns)
-            const int groups = std::max(n / 2, 1);
-            const int threads = std::min(1024, std::max(64, (groups * 16 + 63) / 64 * 64));
-            const size_t lds = ((size_t)n * (n | 1) + 128) * sizeof(double);
-            ProfScope ps(c, "sym_eig");
-            hipLaunchKernelGGL(k_sym_eig, dim3((unsigned)n_mat), dim3((unsigned)threads), lds, c->stream, (const double*)dA, dU, dl, n,
-                               (const int*)c->d_jsched, (const int*)c->d_jsched_off, (const int*)c->d_jsched_rounds, c->jsched_ps,
-                               n_mat <= c->B * (c->L + 1) ? c->d_sweeps : (int*)nullptr);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess && rc == MTIP_OK) e = mtip_copy(c, eigvals, dl, (size_t)n_mat * n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = mtip_copy(c, eigvecs, dU, nn * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            c->err = std::string("symmetric_eig: ") + hipGetErrorString(e);
+    int rc = MTIP_OK;
+    hipError_t e = mtip_copy(c, dA, A, nn * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && n > SE_MAX_N) {
+        ProfScope ps(c, "sym_eig");
+        const int outer = sym_eig_blocked(c, n, n_mat, dA, dU, dl);
+        if (outer < 0) {
+            c->err = "symmetric_eig: blocked solve failed (device memory or block schedule)";
             rc = MTIP_EHIP;
+        } else if (c->d_sweeps != nullptr) {
+            (void)mtip_copy(c, c->d_sweeps, &outer, sizeof(int), hipMemcpyHostToDevice);
         }
+    } else if (e == hipSuccess) {
+        // all pairs of a round in one workgroup: floor(n / 2) groups of 16 lanes (the schedule's group count for n columns)
+        const int groups = std::max(n / 2, 1);
+        const int threads = std::min(1024, std::max(64, (groups * 16 + 63) / 64 * 64));
+        const size_t lds = ((size_t)n * (n | 1) + 128) * sizeof(double);
+        ProfScope ps(c, "sym_eig");
+        hipLaunchKernelGGL(k_sym_eig, dim3((unsigned)n_mat), dim3((unsigned)threads), lds, c->stream, (const double*)dA, dU, dl, n,
+                           (const int*)c->d_jsched, (const int*)c->d_jsched_off, (const int*)c->d_jsched_rounds, c->jsched_ps,
+                           n_mat <= c->B * (c->L + 1) ? c->d_sweeps : (int*)nullptr);
     }
-    if (dA) (void)hipFree(dA);
-    if (dU) (void)hipFree(dU);
-    if (dl) (void)hipFree(dl);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && rc == MTIP_OK) e = mtip_copy(c, eigvals, dl, (size_t)n_mat * n * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = mtip_copy(c, eigvecs, dU, nn * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        c->err = std::string("symmetric_eig: ") + hipGetErrorString(e);
+        rc = MTIP_EHIP;
+    }
     return rc;
 }
 

@@ -272,7 +272,7 @@ int build_hankel_tiles(mtip_ctx* c) {
         t32.swap(order);
     }
     c->n_htiles32 = (int)t32.size();
-    if (hipMalloc((void**)&c->d_htiles32, t32.size() * sizeof(HankelTile32)) != hipSuccess) return MTIP_ENOMEM;
+    if (c->d_htiles32.alloc(t32.size()) != hipSuccess) return MTIP_ENOMEM;
     (void)mtip_copy(c, c->d_htiles32, t32.data(), t32.size() * sizeof(HankelTile32), hipMemcpyHostToDevice);
     return MTIP_OK;
 }

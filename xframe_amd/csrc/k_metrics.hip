@@ -235,29 +235,27 @@ int launch_reciprocal_l2_metric(mtip_ctx* c, const double2* F, const double2* Fp
 }
 
 static void free_reciprocal_l2_metric(mtip_ctx* c) {
-    for (void* p : {(void*)c->d_rl2_wr, (void*)c->d_rl2_wt, (void*)c->d_rl2_part, (void*)c->d_rl2_hist})
-        if (p) (void)hipFree(p);
-    c->d_rl2_wr = nullptr; c->d_rl2_wt = nullptr; c->d_rl2_part = nullptr; c->d_rl2_hist = nullptr;
+    c->d_rl2_wr.reset();
+    c->d_rl2_wt.reset();
+    c->d_rl2_part.reset();
+    c->d_rl2_hist.reset();
 }
 
 // the tables, scratch and history of II_error / ccd_diff / fqc_error alone (the reciprocal l2_projection_diff is armed on its own:
 // re-arming these must leave it on)
 static void free_invariant_tables(mtip_ctx* c) {
-    if (c->d_im_part) (void)hipFree(c->d_im_part);
-    if (c->d_im_fq) (void)hipFree(c->d_im_fq);
-    c->d_im_part = nullptr;
-    c->d_im_fq = nullptr;
-    for (void* p : {(void*)c->d_im_zmask, (void*)c->d_im_IIref, (void*)c->d_im_qq, (void*)c->d_im_ccdT, (void*)c->d_im_ccdref, (void*)c->d_im_P,
-                    (void*)c->d_im_refavg, (void*)c->d_im_refw, (void*)c->d_im_hist})
-        if (p) (void)hipFree(p);
-    c->d_im_zmask = nullptr; c->d_im_IIref = nullptr; c->d_im_qq = nullptr; c->d_im_ccdT = nullptr; c->d_im_ccdref = nullptr;
-    c->d_im_P = nullptr; c->d_im_refavg = nullptr; c->d_im_refw = nullptr; c->d_im_hist = nullptr;
+    c->d_im_part.reset();
+    c->d_im_zmask.reset();
+    c->d_im_IIref.reset();
+    c->d_im_ccdref.reset();
+    c->d_im_fq.reset();
+    c->d_im_qq.reset();
+    c->d_im_ccdT.reset();
+    c->d_im_P.reset();
+    c->d_im_refavg.reset();
+    c->d_im_refw.reset();
+    c->d_im_hist.reset();
     c->im_which = 0;
-}
-
-void free_invariant_metrics(mtip_ctx* c) {                 // everything this file allocates (mtip_destroy)
-    free_reciprocal_l2_metric(c);
-    free_invariant_tables(c);
 }
 
 // per step: B_l of the current coefficients, then the enabled metrics into the step's row of the history
@@ -271,12 +269,12 @@ int launch_invariant_metrics(mtip_ctx* c, const double2* Ilm, long long step) {
 
 static int launch_invariant_metrics_row(mtip_ctx* c, const double2* Ilm, double* row) {
     const size_t per = (size_t)(c->L + 1) * c->N * c->N;
-    if (!c->d_Bl && hipMalloc((void**)&c->d_Bl, (size_t)c->B * per * sizeof(double2)) != hipSuccess) {
+    if (!c->d_Bl && c->d_Bl.alloc((size_t)c->B * per) != hipSuccess) {
         c->err = "invariant metrics: out of device memory for B_l";
         return MTIP_ENOMEM;
     }
     launch_deg2(c, Ilm, c->d_Bl);
-    if ((c->im_which & 3) && !c->d_im_part && hipMalloc((void**)&c->d_im_part, (size_t)c->B * IM_BLOCKS * 4 * sizeof(double2)) != hipSuccess) {
+    if ((c->im_which & 3) && !c->d_im_part && c->d_im_part.alloc((size_t)c->B * IM_BLOCKS * 4) != hipSuccess) {
         c->err = "invariant metrics: out of device memory for the partial sums";
         return MTIP_ENOMEM;
     }
@@ -291,7 +289,7 @@ static int launch_invariant_metrics_row(mtip_ctx* c, const double2* Ilm, double*
                            (int)(c->im_which & 3), c->im_ccd_inv_norm, row, row + c->B, c->B);
     if (c->im_which & 4)
     {
-        if (!c->d_im_fq && hipMalloc((void**)&c->d_im_fq, (size_t)c->B * c->N * c->N * sizeof(double)) != hipSuccess) {
+        if (!c->d_im_fq && c->d_im_fq.alloc((size_t)c->B * c->N * c->N) != hipSuccess) {
             c->err = "invariant metrics: out of device memory for the fqc matrix";
             return MTIP_ENOMEM;
         }
@@ -320,28 +318,28 @@ int mtip_set_invariant_metrics(mtip_ctx* c, uint32_t which, const uint8_t* zero_
         return MTIP_EINVAL;
     }
     const size_t NN = (size_t)c->N * c->N, LNN = (size_t)(c->L + 1) * NN;
-#define IM_UP(dst, src, bytes)                                                        \
-    do {                                                                              \
-        MTIP_HIP_CHECK(c, hipMalloc((void**)&(dst), (bytes)));                        \
-        MTIP_HIP_CHECK(c, mtip_copy(c, (dst), (src), (bytes), hipMemcpyHostToDevice)); \
+#define IM_UP(dst, src, count)                                                                          \
+    do {                                                                                                \
+        MTIP_HIP_CHECK(c, (dst).alloc(count));                                                          \
+        MTIP_HIP_CHECK(c, mtip_copy(c, (dst), (src), (count) * sizeof(*(dst)), hipMemcpyHostToDevice)); \
     } while (0)
     IM_UP(c->d_im_zmask, zero_mask, LNN);
     if (which & 1) {
-        IM_UP(c->d_im_IIref, II_reference, NN * sizeof(double2));
-        IM_UP(c->d_im_qq, qq, NN * sizeof(double));
+        IM_UP(c->d_im_IIref, II_reference, NN);
+        IM_UP(c->d_im_qq, qq, NN);
     }
     if (which & 2) {
-        IM_UP(c->d_im_ccdT, ccd_weights, LNN * sizeof(double));
-        IM_UP(c->d_im_ccdref, ccd_reference, NN * sizeof(double2));
+        IM_UP(c->d_im_ccdT, ccd_weights, LNN);
+        IM_UP(c->d_im_ccdref, ccd_reference, NN);
         c->im_ccd_inv_norm = 1.0 / ccd_norm;
     }
     if (which & 4) {
-        IM_UP(c->d_im_P, fqc_P, LNN * (c->L + 1) * sizeof(double));
-        IM_UP(c->d_im_refavg, fqc_reference_average, NN * sizeof(double));
-        IM_UP(c->d_im_refw, fqc_reference_weights, LNN * sizeof(double));
+        IM_UP(c->d_im_P, fqc_P, LNN * (c->L + 1));
+        IM_UP(c->d_im_refavg, fqc_reference_average, NN);
+        IM_UP(c->d_im_refw, fqc_reference_weights, LNN);
     }
 #undef IM_UP
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_im_hist, (size_t)c->err_cap * c->B * (2 + c->N) * sizeof(double)));
+    MTIP_HIP_CHECK(c, c->d_im_hist.alloc((size_t)c->err_cap * c->B * (2 + c->N)));
     MTIP_HIP_CHECK(c, hipMemsetAsync(c->d_im_hist, 0, (size_t)c->err_cap * c->B * (2 + c->N) * sizeof(double), c->stream));
     c->im_which = which;
     return MTIP_OK;
@@ -374,12 +372,12 @@ int mtip_set_reciprocal_l2_metric(mtip_ctx* c, const double* radial_w, const dou
     (void)hipSetDevice(c->device);
     free_reciprocal_l2_metric(c);
     if (!radial_w || !theta_w) return MTIP_OK;
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_rl2_wr, c->N * sizeof(double)));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_rl2_wt, c->nt * sizeof(double)));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_rl2_part, (size_t)c->B * c->N * 2 * sizeof(double)));
+    MTIP_HIP_CHECK(c, c->d_rl2_wr.alloc(c->N));
+    MTIP_HIP_CHECK(c, c->d_rl2_wt.alloc(c->nt));
+    MTIP_HIP_CHECK(c, c->d_rl2_part.alloc((size_t)c->B * c->N * 2));
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_rl2_wr, radial_w, c->N * sizeof(double), hipMemcpyHostToDevice));
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_rl2_wt, theta_w, c->nt * sizeof(double), hipMemcpyHostToDevice));
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&c->d_rl2_hist, (size_t)c->err_cap * c->B * sizeof(double)));
+    MTIP_HIP_CHECK(c, c->d_rl2_hist.alloc((size_t)c->err_cap * c->B));
     MTIP_HIP_CHECK(c, hipMemsetAsync(c->d_rl2_hist, 0, (size_t)c->err_cap * c->B * sizeof(double), c->stream));
     return MTIP_OK;
 }
@@ -405,19 +403,17 @@ int mtip_op_invariant_metrics(mtip_ctx* c, const mtip_cdouble* Ilm, double* II, 
     }
     (void)hipSetDevice(c->device);
     const size_t rowlen = (size_t)c->B * (2 + c->N);
-    double* d_row = nullptr;
-    MTIP_HIP_CHECK(c, hipMalloc((void**)&d_row, rowlen * sizeof(double)));
+    DevBuf<double> d_row;
+    MTIP_HIP_CHECK(c, d_row.alloc(rowlen));
     hipError_t he = hipMemsetAsync(d_row, 0, rowlen * sizeof(double), c->stream);
     if (he == hipSuccess) he = mtip_copy(c, c->d_c[2], Ilm, (size_t)c->B * c->C * sizeof(double2), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {                                  // (the row buffer must not outlive a failed call)
-        (void)hipFree(d_row);
+    if (he != hipSuccess) {
         c->err = std::string("op_invariant_metrics: ") + hipGetErrorString(he);
         return MTIP_EHIP;
     }
     int rc = launch_invariant_metrics_row(c, c->d_c[2], d_row);
     std::vector<double> row(rowlen);
     if (rc == MTIP_OK && mtip_copy(c, row.data(), d_row, rowlen * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = MTIP_EHIP;
-    (void)hipFree(d_row);
     if (rc != MTIP_OK) return rc;
     if (II) std::copy(row.begin(), row.begin() + c->B, II);
     if (ccd) std::copy(row.begin() + c->B, row.begin() + 2 * c->B, ccd);

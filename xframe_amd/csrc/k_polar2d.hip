@@ -17,67 +17,51 @@
 struct mtip2d_ctx {
     int N = 0, n_phi = 0, M = 0, B = 0, device = 0;
     hipStream_t stream = nullptr;
-    double2 *d_tw = nullptr;                       // n_phi: exp(-2 pi i j / n_phi)
-    double2 *d_wf = nullptr, *d_wi = nullptr;      // (N, N, n_phi) forward / inverse Hankel weights (summed p, new k, order)
-    uint8_t* d_unused = nullptr;                   // n_phi: order zeroed by the Hankel pair
-    double2 *d_a = nullptr, *d_b = nullptr;        // (B, N, n_phi) work grids
+    DevBuf<double2> d_tw;                          // n_phi: exp(-2 pi i j / n_phi)
+    DevBuf<double2> d_wf, d_wi;                    // (N, N, n_phi) forward / inverse Hankel weights (summed p, new k, order)
+    DevBuf<uint8_t> d_unused;                      // n_phi: order zeroed by the Hankel pair
+    DevBuf<double2> d_a, d_b;                      // (B, N, n_phi) work grids
     // projection
     int n_used = 0, zero_pos = -1, zero_id = -1;
     int so_pos = -1;                  // SO_freedom: position (among the used orders) of the order whose unknown is set to 1, or -1
-    int* d_order_ids = nullptr;                    // n_used
-    double2* d_pm = nullptr;                       // (n_used, N)
-    uint8_t* d_rmask = nullptr;                    // (n_used, N): radial mask of the used orders
-    double* d_q = nullptr;                         // N
-    double2* d_unk = nullptr;                      // (B, n_used)
+    DevBuf<int> d_order_ids;                       // n_used
+    DevBuf<double2> d_pm;                          // (n_used, N)
+    DevBuf<uint8_t> d_rmask;                       // (n_used, N): radial mask of the used orders
+    DevBuf<double> d_q;                            // N
+    DevBuf<double2> d_unk;                         // (B, n_used)
     double n_particles = 1.0;
     bool have_weights = false;
     // loop operators (step, shrink-wrap)
     RealParams rp{};
-    double* d_errw = nullptr;                      // (N, n_phi) weights of the real error metric (integrator weights x metric mask)
-    double2 *d_c = nullptr, *d_d = nullptr, *d_e = nullptr;   // more (B, N, n_phi) work grids
-    uint8_t* d_sup = nullptr;                      // (B, N, n_phi)
-    double* d_red = nullptr;                       // (B, 4) reductions
+    DevBuf<double> d_errw;                         // (N, n_phi) weights of the real error metric (integrator weights x metric mask)
+    DevBuf<double2> d_c, d_d, d_e;                 // more (B, N, n_phi) work grids
+    DevBuf<uint8_t> d_sup;                         // (B, N, n_phi)
+    DevBuf<double> d_red;                          // (B, 4) reductions
     bool have_errw = false;
     // ---- resident loop (second half of this file): the state of a batch of restarts stays in HBM between the steps
     bool r_alloc = false, r_ready = false, r_fixed_valid = false, r_ft_mixed = false;
     int r_cur = 0;                                 // which of the two (F, rho) pairs is the latest; the other one is the stale pair
     int r_n_used = 0;                              // n_used the per-order buffers were sized for
     long long r_steps = 0, r_cap = 0;              // steps done, capacity of the histories (steps)
-    double2 *r_F[2] = {nullptr, nullptr}, *r_R[2] = {nullptr, nullptr};   // (B, N, n_phi) pairs
-    double2 *r_C = nullptr, *r_H = nullptr, *r_D = nullptr;   // harmonic coefficients of rho, of F (Hankel output), of F'
-    double2 *r_wf = nullptr, *r_wi = nullptr;      // the Hankel weights repacked shell-major (new k, summed p, order)
+    DevBuf<double2> r_F[2], r_R[2];                // (B, N, n_phi) pairs
+    DevBuf<double2> r_C, r_H, r_D;                 // harmonic coefficients of rho, of F (Hankel output), of F'
+    DevBuf<double2> r_wf, r_wi;                    // the Hankel weights repacked shell-major (new k, summed p, order)
     bool r_w_dirty = true;
-    double2* r_Ft = nullptr;                       // F = FT(rho) of the step in flight (the pair's own F is the F' that produced rho)
-    double2 *r_Im = nullptr, *r_sp = nullptr;      // (B, N, M + 1) I_m of |F|^2; (B, n_used, N) terms of the scalar products
-    double2 *r_bestF = nullptr, *r_bestR = nullptr, *r_guess = nullptr, *r_unk = nullptr;
-    double* r_fixed = nullptr;                     // (B, N, n_phi) intensity grid of the *_non_FXS methods
-    uint8_t *r_sup = nullptr, *r_bestsup = nullptr, *r_swnew = nullptr, *r_S0 = nullptr;   // effective / best / new (B, G); initial (G)
-    uint8_t *r_flag = nullptr, *r_ft = nullptr, *r_enf = nullptr, *r_sel = nullptr;       // (B) each
-    double *r_part = nullptr, *r_part2 = nullptr, *r_besterr = nullptr;                   // (B, N, 2) x 2, (B)
-    double *r_herr = nullptr, *r_hmain = nullptr, *r_hrl2 = nullptr, *r_hdeg2 = nullptr;   // histories (cap, B[, n_used])
+    DevBuf<double2> r_Ft;                          // F = FT(rho) of the step in flight (the pair's own F is the F' that produced rho)
+    DevBuf<double2> r_Im, r_sp;                    // (B, N, M + 1) I_m of |F|^2; (B, n_used, N) terms of the scalar products
+    DevBuf<double2> r_bestF, r_bestR, r_guess, r_unk;
+    DevBuf<double> r_fixed;                        // (B, N, n_phi) intensity grid of the *_non_FXS methods
+    DevBuf<uint8_t> r_sup, r_bestsup, r_swnew, r_S0;   // effective / best / new (B, G); initial (G)
+    DevBuf<uint8_t> r_flag, r_ft, r_enf, r_sel;    // (B) each
+    DevBuf<double> r_part, r_part2, r_besterr;     // (B, N, 2) x 2, (B)
+    DevBuf<double> r_herr, r_hmain, r_hrl2, r_hdeg2;   // histories (cap, B[, n_used])
     bool r_have_S0 = false;
     uint32_t r_metrics = 0;                        // 1: deg2_invariant_l2_diff, 2: l2_projection_diff (reciprocal)
-    double2* r_deg2ref = nullptr;                  // (n_used, N, N)
-    double *r_deg2norm = nullptr, *r_recw = nullptr;   // (n_used), (N, n_phi)
+    DevBuf<double2> r_deg2ref;                     // (n_used, N, N)
+    DevBuf<double> r_deg2norm, r_recw;             // (n_used), (N, n_phi)
     int r_main_type = 0, r_main_n = 1, r_main_items[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // 0 real, 1 deg2, 2 reciprocal l2
     std::string err;
 };
-
-#define C2_CHECK(c, expr)                                                          \
-    do {                                                                            \
-        hipError_t e_ = (expr);                                                     \
-        if (e_ != hipSuccess) {                                                     \
-            (c)->err = std::string(#expr) + ": " + hipGetErrorString(e_);           \
-            return MTIP_EHIP;                                                       \
-        }                                                                           \
-    } while (0)
-
-static hipError_t c2_copy(mtip2d_ctx* c, void* dst, const void* src, size_t n) {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return e;
-    e = hipMemcpy(dst, src, n, hipMemcpyDefault);
-    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
-}
 
 // out[m] = scale * sum_p in[p] exp(sign 2 pi i m p / n) for one (restart, shell) per workgroup; n_out outputs (n for the complex
 // transform, M + 1 for the real one); real_in: only Re(in) enters (circularHarmonicTransform_real_forward)
@@ -274,17 +258,6 @@ __global__ void __launch_bounds__(256) k2d_sw_mask(const double2* __restrict__ c
     for (size_t e = threadIdx.x; e < G; e += blockDim.x) mask[(size_t)b * G + e] = fmax(conv[(size_t)b * G + e].x, 0.0) >= cut ? 1 : 0;
 }
 
-static void rs_free(mtip2d_ctx* c);
-
-static void c2_free(mtip2d_ctx* c) {
-    for (void* p : {(void*)c->d_tw, (void*)c->d_wf, (void*)c->d_wi, (void*)c->d_unused, (void*)c->d_a, (void*)c->d_b, (void*)c->d_order_ids,
-                    (void*)c->d_pm, (void*)c->d_rmask, (void*)c->d_q, (void*)c->d_unk, (void*)c->d_errw, (void*)c->d_c, (void*)c->d_d,
-                    (void*)c->d_e, (void*)c->d_sup, (void*)c->d_red})
-        if (p) (void)hipFree(p);
-    rs_free(c);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-}
-
 static void c2_dft(mtip2d_ctx* c, const double2* in, double2* out, int inverse) {
     const size_t lds = (size_t)2 * c->n_phi * sizeof(double2);
     hipLaunchKernelGGL(k2d_dft, dim3((unsigned)(c->B * c->N)), dim3(256), lds, c->stream, in, out, (const double2*)c->d_tw, c->n_phi, c->n_phi,
@@ -307,20 +280,19 @@ mtip2d_ctx* mtip2d_create(int n_radial, int n_phi, int n_batch, int device) {
     (void)hipSetDevice(device);
     const size_t G = (size_t)n_batch * n_radial * n_phi;
     bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipMalloc((void**)&c->d_tw, n_phi * sizeof(double2)) == hipSuccess &&
-              hipMalloc((void**)&c->d_wf, (size_t)n_radial * n_radial * n_phi * sizeof(double2)) == hipSuccess &&
-              hipMalloc((void**)&c->d_wi, (size_t)n_radial * n_radial * n_phi * sizeof(double2)) == hipSuccess &&
-              hipMalloc((void**)&c->d_unused, n_phi) == hipSuccess && hipMalloc((void**)&c->d_a, G * sizeof(double2)) == hipSuccess &&
-              hipMalloc((void**)&c->d_b, G * sizeof(double2)) == hipSuccess;
+              c->d_tw.alloc(n_phi) == hipSuccess &&
+              c->d_wf.alloc((size_t)n_radial * n_radial * n_phi) == hipSuccess &&
+              c->d_wi.alloc((size_t)n_radial * n_radial * n_phi) == hipSuccess &&
+              c->d_unused.alloc(n_phi) == hipSuccess && c->d_a.alloc(G) == hipSuccess &&
+              c->d_b.alloc(G) == hipSuccess;
     if (ok) {
         std::vector<double2> tw(n_phi);
         const double pi = 3.14159265358979323846;
         for (int j = 0; j < n_phi; ++j) tw[j] = make_double2(std::cos(2 * pi * j / n_phi), -std::sin(2 * pi * j / n_phi));
-        ok = c2_copy(c, c->d_tw, tw.data(), n_phi * sizeof(double2)) == hipSuccess;
+        ok = mtip_copy(c->stream, c->d_tw, tw.data(), n_phi * sizeof(double2)) == hipSuccess;
     }
     if (!ok) {
-        c2_free(c);
-        delete c;
+        mtip2d_destroy(c);
         return nullptr;
     }
     return c;
@@ -329,9 +301,11 @@ mtip2d_ctx* mtip2d_create(int n_radial, int n_phi, int n_batch, int device) {
 void mtip2d_destroy(mtip2d_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    c2_free(c);
-    delete c;
+    if (c->stream) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamDestroy(c->stream);
+    }
+    delete c;                                            // the device buffers go with it
 }
 
 const char* mtip2d_last_error(const mtip2d_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -344,9 +318,9 @@ int mtip2d_set_hankel_weights(mtip2d_ctx* c, const mtip_cdouble* forward, const 
     }
     (void)hipSetDevice(c->device);
     const size_t n = (size_t)c->N * c->N * c->n_phi * sizeof(double2);
-    C2_CHECK(c, c2_copy(c, c->d_wf, forward, n));
-    C2_CHECK(c, c2_copy(c, c->d_wi, inverse, n));
-    C2_CHECK(c, c2_copy(c, c->d_unused, unused_orders, c->n_phi));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_wf, forward, n));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_wi, inverse, n));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_unused, unused_orders, c->n_phi));
     c->have_weights = true;
     c->r_w_dirty = true;                           // (the resident loop repacks them in mtip2d_init_state)
     return MTIP_OK;
@@ -378,18 +352,20 @@ int mtip2d_set_projection(mtip2d_ctx* c, int n_used, const int32_t* order_ids, c
     }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (void* p : {(void*)c->d_order_ids, (void*)c->d_pm, (void*)c->d_rmask, (void*)c->d_q, (void*)c->d_unk})
-        if (p) (void)hipFree(p);
-    c->d_order_ids = nullptr; c->d_pm = nullptr; c->d_rmask = nullptr; c->d_q = nullptr; c->d_unk = nullptr;
-    C2_CHECK(c, hipMalloc((void**)&c->d_order_ids, n_used * sizeof(int)));
-    C2_CHECK(c, hipMalloc((void**)&c->d_pm, (size_t)n_used * c->N * sizeof(double2)));
-    C2_CHECK(c, hipMalloc((void**)&c->d_rmask, (size_t)n_used * c->N));
-    C2_CHECK(c, hipMalloc((void**)&c->d_q, c->N * sizeof(double)));
-    C2_CHECK(c, hipMalloc((void**)&c->d_unk, (size_t)c->B * n_used * sizeof(double2)));
-    C2_CHECK(c, c2_copy(c, c->d_order_ids, order_ids, n_used * sizeof(int)));
-    C2_CHECK(c, c2_copy(c, c->d_pm, pm, (size_t)n_used * c->N * sizeof(double2)));
-    C2_CHECK(c, c2_copy(c, c->d_rmask, radial_mask, (size_t)n_used * c->N));
-    C2_CHECK(c, c2_copy(c, c->d_q, radial_points, c->N * sizeof(double)));
+    c->d_order_ids.reset();                              // all of the old tables go before the first new one comes
+    c->d_pm.reset();
+    c->d_rmask.reset();
+    c->d_q.reset();
+    c->d_unk.reset();
+    MTIP_HIP_CHECK(c, c->d_order_ids.alloc(n_used));
+    MTIP_HIP_CHECK(c, c->d_pm.alloc((size_t)n_used * c->N));
+    MTIP_HIP_CHECK(c, c->d_rmask.alloc((size_t)n_used * c->N));
+    MTIP_HIP_CHECK(c, c->d_q.alloc(c->N));
+    MTIP_HIP_CHECK(c, c->d_unk.alloc((size_t)c->B * n_used));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_order_ids, order_ids, n_used * sizeof(int)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_pm, pm, (size_t)n_used * c->N * sizeof(double2)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_rmask, radial_mask, (size_t)n_used * c->N));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_q, radial_points, c->N * sizeof(double)));
     c->n_used = n_used;
     c->n_particles = n_particles;
     c->so_pos = -1;
@@ -408,10 +384,10 @@ int mtip2d_op_harmonic(mtip2d_ctx* c, const mtip_cdouble* in, mtip_cdouble* out,
     }
     (void)hipSetDevice(c->device);
     const size_t n = (size_t)c->B * c->N * c->n_phi * sizeof(double2);
-    C2_CHECK(c, c2_copy(c, c->d_a, in, n));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_a, in, n));
     c2_dft(c, c->d_a, c->d_b, inverse);
-    C2_CHECK(c, c2_copy(c, out, c->d_b, n));
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, out, c->d_b, n));
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -422,11 +398,11 @@ int mtip2d_op_real_harmonic_forward(mtip2d_ctx* c, const mtip_cdouble* grid, mti
         return MTIP_EINVAL;
     }
     (void)hipSetDevice(c->device);
-    C2_CHECK(c, c2_copy(c, c->d_a, grid, (size_t)c->B * c->N * c->n_phi * sizeof(double2)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_a, grid, (size_t)c->B * c->N * c->n_phi * sizeof(double2)));
     hipLaunchKernelGGL(k2d_dft, dim3((unsigned)(c->B * c->N)), dim3(256), (size_t)2 * c->n_phi * sizeof(double2), c->stream, (const double2*)c->d_a,
                        c->d_b, (const double2*)c->d_tw, c->n_phi, c->M + 1, -1, 1.0 / c->n_phi, 1);
-    C2_CHECK(c, c2_copy(c, coef, c->d_b, (size_t)c->B * c->N * (c->M + 1) * sizeof(double2)));
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, coef, c->d_b, (size_t)c->B * c->N * (c->M + 1) * sizeof(double2)));
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -437,11 +413,11 @@ int mtip2d_op_real_harmonic_inverse(mtip2d_ctx* c, const mtip_cdouble* coef, dou
         return MTIP_EINVAL;
     }
     (void)hipSetDevice(c->device);
-    C2_CHECK(c, c2_copy(c, c->d_a, coef, (size_t)c->B * c->N * (c->M + 1) * sizeof(double2)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_a, coef, (size_t)c->B * c->N * (c->M + 1) * sizeof(double2)));
     hipLaunchKernelGGL(k2d_irdft, dim3((unsigned)(c->B * c->N)), dim3(256), (size_t)2 * c->n_phi * sizeof(double2), c->stream, (const double2*)c->d_a,
-                       reinterpret_cast<double*>(c->d_b), (const double2*)c->d_tw, c->n_phi, c->M);
-    C2_CHECK(c, c2_copy(c, grid, c->d_b, (size_t)c->B * c->N * c->n_phi * sizeof(double)));
-    C2_CHECK(c, hipGetLastError());
+                       reinterpret_cast<double*>((double2*)c->d_b), (const double2*)c->d_tw, c->n_phi, c->M);
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, grid, c->d_b, (size_t)c->B * c->N * c->n_phi * sizeof(double)));
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -457,10 +433,10 @@ int mtip2d_op_hankel(mtip2d_ctx* c, const mtip_cdouble* in, mtip_cdouble* out, i
     }
     (void)hipSetDevice(c->device);
     const size_t n = (size_t)c->B * c->N * c->n_phi * sizeof(double2);
-    C2_CHECK(c, c2_copy(c, c->d_a, in, n));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_a, in, n));
     c2_hankel(c, c->d_a, c->d_b, inverse);
-    C2_CHECK(c, c2_copy(c, out, c->d_b, n));
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, out, c->d_b, n));
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -477,12 +453,12 @@ int mtip2d_op_fourier_transform(mtip2d_ctx* c, const mtip_cdouble* in, mtip_cdou
     }
     (void)hipSetDevice(c->device);
     const size_t n = (size_t)c->B * c->N * c->n_phi * sizeof(double2);
-    C2_CHECK(c, c2_copy(c, c->d_a, in, n));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_a, in, n));
     c2_dft(c, c->d_a, c->d_b, 0);
     c2_hankel(c, c->d_b, c->d_a, inverse);
     c2_dft(c, c->d_a, c->d_b, 1);
-    C2_CHECK(c, c2_copy(c, out, c->d_b, n));
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, out, c->d_b, n));
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -509,13 +485,13 @@ int mtip2d_op_project(mtip2d_ctx* c, const mtip_cdouble* I, mtip_cdouble* out, m
     (void)hipSetDevice(c->device);
     const int n_coef = c->M + 1;
     const size_t n = (size_t)c->B * c->N * n_coef * sizeof(double2);
-    C2_CHECK(c, c2_copy(c, c->d_a, I, n));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_a, I, n));
     hipLaunchKernelGGL(k2d_project, dim3((unsigned)c->B), dim3(256), (size_t)c->n_used * sizeof(double2), c->stream, (const double2*)c->d_a, c->d_b,
                        c->d_unk, (const double2*)c->d_pm, (const uint8_t*)c->d_rmask, (const int*)c->d_order_ids, (const double*)c->d_q, c->N,
                        n_coef, c->n_used, c->zero_pos, c->zero_id, 1.0 / std::sqrt(c->n_particles), c->so_pos);
-    C2_CHECK(c, c2_copy(c, out, c->d_b, n));
-    if (unknowns) C2_CHECK(c, c2_copy(c, unknowns, c->d_unk, (size_t)c->B * c->n_used * sizeof(double2)));
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, out, c->d_b, n));
+    if (unknowns) MTIP_HIP_CHECK(c, mtip_copy(c->stream, unknowns, c->d_unk, (size_t)c->B * c->n_used * sizeof(double2)));
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -532,13 +508,13 @@ int mtip2d_set_error_weights(mtip2d_ctx* c, const double* weights) {
     (void)hipSetDevice(c->device);
     const size_t G = (size_t)c->N * c->n_phi, BG = (size_t)c->B * G;
     // (each buffer on its own: a call that failed half way is completed by the next one)
-    if (!c->d_errw) C2_CHECK(c, hipMalloc((void**)&c->d_errw, G * sizeof(double)));
-    if (!c->d_c) C2_CHECK(c, hipMalloc((void**)&c->d_c, BG * sizeof(double2)));
-    if (!c->d_d) C2_CHECK(c, hipMalloc((void**)&c->d_d, BG * sizeof(double2)));
-    if (!c->d_e) C2_CHECK(c, hipMalloc((void**)&c->d_e, BG * sizeof(double2)));
-    if (!c->d_sup) C2_CHECK(c, hipMalloc((void**)&c->d_sup, BG));
-    if (!c->d_red) C2_CHECK(c, hipMalloc((void**)&c->d_red, (size_t)c->B * 4 * sizeof(double)));
-    C2_CHECK(c, c2_copy(c, c->d_errw, weights, G * sizeof(double)));
+    if (!c->d_errw) MTIP_HIP_CHECK(c, c->d_errw.alloc(G));
+    if (!c->d_c) MTIP_HIP_CHECK(c, c->d_c.alloc(BG));
+    if (!c->d_d) MTIP_HIP_CHECK(c, c->d_d.alloc(BG));
+    if (!c->d_e) MTIP_HIP_CHECK(c, c->d_e.alloc(BG));
+    if (!c->d_sup) MTIP_HIP_CHECK(c, c->d_sup.alloc(BG));
+    if (!c->d_red) MTIP_HIP_CHECK(c, c->d_red.alloc((size_t)c->B * 4));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_errw, weights, G * sizeof(double)));
     c->have_errw = true;
     return MTIP_OK;
 }
@@ -576,35 +552,35 @@ int mtip2d_op_step_ex(mtip2d_ctx* c, int method, int ft_stab, double beta, const
     const long long total = (long long)BG;
     const size_t lds = (size_t)2 * n * sizeof(double2);
     const unsigned rows = (unsigned)(B * N);
-    C2_CHECK(c, c2_copy(c, c->d_e, rho, BG * sizeof(double2)));                      // rho_in
-    C2_CHECK(c, c2_copy(c, c->d_sup, support, BG));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_e, rho, BG * sizeof(double2)));                      // rho_in
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_sup, support, BG));
     // F = FT(rho) -> d_c
     c2_dft(c, c->d_e, c->d_a, 0);
     c2_hankel(c, c->d_a, c->d_b, 0);
     c2_dft(c, c->d_b, c->d_c, 1);
-    if (F_out) C2_CHECK(c, c2_copy(c, F_out, c->d_c, BG * sizeof(double2)));
+    if (F_out) MTIP_HIP_CHECK(c, mtip_copy(c->stream, F_out, c->d_c, BG * sizeof(double2)));
     if (!fxs) {
         // MTIP_start_non_FXS (reconstruct.py:530-535): F' = F sqrt(fixed / |F|^2), no harmonic transform and no unknowns
-        C2_CHECK(c, c2_copy(c, c->d_a, fixed_intensity, BG * sizeof(double)));
+        MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_a, fixed_intensity, BG * sizeof(double)));
         unknowns = nullptr;
     } else {
     // I_m of |F|^2 -> d_a (B, N, M + 1); projection -> d_b; I' (real grid) -> d_a (as doubles)
     hipLaunchKernelGGL(k2d_dft, dim3(rows), dim3(256), lds, c->stream, (const double2*)c->d_c, c->d_a, (const double2*)c->d_tw, n, M1, -1, 1.0 / n, 2);
-    if (I_out) C2_CHECK(c, c2_copy(c, I_out, c->d_a, (size_t)B * N * M1 * sizeof(double2)));
+    if (I_out) MTIP_HIP_CHECK(c, mtip_copy(c->stream, I_out, c->d_a, (size_t)B * N * M1 * sizeof(double2)));
     hipLaunchKernelGGL(k2d_project, dim3((unsigned)B), dim3(256), (size_t)c->n_used * sizeof(double2), c->stream, (const double2*)c->d_a, c->d_b,
                        c->d_unk, (const double2*)c->d_pm, (const uint8_t*)c->d_rmask, (const int*)c->d_order_ids, (const double*)c->d_q, N, M1,
                        c->n_used, c->zero_pos, c->zero_id, 1.0 / std::sqrt(c->n_particles), c->so_pos);
-    hipLaunchKernelGGL(k2d_irdft, dim3(rows), dim3(256), lds, c->stream, (const double2*)c->d_b, reinterpret_cast<double*>(c->d_a),
+    hipLaunchKernelGGL(k2d_irdft, dim3(rows), dim3(256), lds, c->stream, (const double2*)c->d_b, reinterpret_cast<double*>((double2*)c->d_a),
                        (const double2*)c->d_tw, n, c->M);
     }
     // F' -> d_d
     hipLaunchKernelGGL(k2d_modulus, dim3((unsigned)div_up(total, 256)), dim3(256), 0, c->stream, (const double2*)c->d_c,
-                       (const double*)reinterpret_cast<double*>(c->d_a), c->d_d, total);
+                       (const double*)reinterpret_cast<double*>((double2*)c->d_a), c->d_d, total);
     // rho' = IFT(F') -> d_a
     c2_dft(c, c->d_d, c->d_a, 0);
     c2_hankel(c, c->d_a, c->d_b, 1);
     c2_dft(c, c->d_b, c->d_a, 1);
-    C2_CHECK(c, c2_copy(c, F_new, c->d_d, BG * sizeof(double2)));                   // F' delivered: d_d is free for the outputs below
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, F_new, c->d_d, BG * sizeof(double2)));                   // F' delivered: d_d is free for the outputs below
     if (ft_stab) {                                                                  // IFT(F) -> d_b (through d_d)
         c2_dft(c, c->d_c, c->d_b, 0);
         c2_hankel(c, c->d_b, c->d_d, 1);
@@ -613,12 +589,12 @@ int mtip2d_op_step_ex(mtip2d_ctx* c, int method, int ft_stab, double beta, const
     hipLaunchKernelGGL(k2d_real_update, dim3((unsigned)B), dim3(256), 0, c->stream, (const double2*)c->d_a, (const double2*)c->d_e,
                        (const double2*)c->d_b, (const uint8_t*)c->d_sup, (const double*)c->d_errw, c->d_d, c->d_red, c->rp, method & 1, beta,
                        ft_stab ? 1 : 0, N, n);
-    C2_CHECK(c, c2_copy(c, rho_new, c->d_d, BG * sizeof(double2)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, rho_new, c->d_d, BG * sizeof(double2)));
     std::vector<double> red((size_t)B * 2);
-    C2_CHECK(c, c2_copy(c, red.data(), c->d_red, red.size() * sizeof(double)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, red.data(), c->d_red, red.size() * sizeof(double)));
     for (int b = 0; b < B; ++b) err[b] = red[2 * b + 1] != 0.0 ? red[2 * b] / red[2 * b + 1] : HUGE_VAL;   // fxs_IO_methods.py:121-126
-    if (unknowns) C2_CHECK(c, c2_copy(c, unknowns, c->d_unk, (size_t)B * c->n_used * sizeof(double2)));
-    C2_CHECK(c, hipGetLastError());
+    if (unknowns) MTIP_HIP_CHECK(c, mtip_copy(c->stream, unknowns, c->d_unk, (size_t)B * c->n_used * sizeof(double2)));
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -637,7 +613,7 @@ int mtip2d_op_shrinkwrap(mtip2d_ctx* c, const mtip_cdouble* rho, double sigma, d
     (void)hipSetDevice(c->device);
     const size_t BG = (size_t)c->B * c->N * c->n_phi;
     const long long total = (long long)BG;
-    C2_CHECK(c, c2_copy(c, c->d_e, rho, BG * sizeof(double2)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->d_e, rho, BG * sizeof(double2)));
     hipLaunchKernelGGL(k2d_abs, dim3((unsigned)div_up(total, 256)), dim3(256), 0, c->stream, (const double2*)c->d_e, c->d_c, total);
     c2_dft(c, c->d_c, c->d_a, 0);
     c2_hankel(c, c->d_a, c->d_b, 0);
@@ -647,8 +623,8 @@ int mtip2d_op_shrinkwrap(mtip2d_ctx* c, const mtip_cdouble* rho, double sigma, d
     c2_hankel(c, c->d_a, c->d_b, 1);
     c2_dft(c, c->d_b, c->d_c, 1);
     hipLaunchKernelGGL(k2d_sw_mask, dim3((unsigned)c->B), dim3(256), 0, c->stream, (const double2*)c->d_c, c->d_sup, threshold, c->N, c->n_phi);
-    C2_CHECK(c, c2_copy(c, mask, c->d_sup, BG));
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, mask, c->d_sup, BG));
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -1145,21 +1121,6 @@ static size_t rs_lds_bytes(const mtip2d_ctx* c) {
     return ((size_t)(1 + 2 * RS_BC + rs_slices(c) * RS_BC) * c->n_phi + (size_t)RS_BC * (c->M + 1)) * sizeof(double2);
 }
 
-template <typename T>
-static hipError_t rs_alloc(T** p, size_t count) {
-    if (*p) return hipSuccess;
-    return hipMalloc((void**)p, count * sizeof(T));
-}
-
-static void rs_free(mtip2d_ctx* c) {
-    for (void* p : {(void*)c->r_F[0], (void*)c->r_F[1], (void*)c->r_R[0], (void*)c->r_R[1], (void*)c->r_wf, (void*)c->r_wi, (void*)c->r_C, (void*)c->r_H, (void*)c->r_D, (void*)c->r_Ft, (void*)c->r_Im,
-                    (void*)c->r_sp, (void*)c->r_bestF, (void*)c->r_bestR, (void*)c->r_guess, (void*)c->r_unk, (void*)c->r_fixed, (void*)c->r_sup,
-                    (void*)c->r_bestsup, (void*)c->r_swnew, (void*)c->r_S0, (void*)c->r_flag, (void*)c->r_ft, (void*)c->r_enf, (void*)c->r_sel,
-                    (void*)c->r_part, (void*)c->r_part2, (void*)c->r_besterr, (void*)c->r_herr, (void*)c->r_hmain, (void*)c->r_hrl2,
-                    (void*)c->r_hdeg2, (void*)c->r_deg2ref, (void*)c->r_deg2norm, (void*)c->r_recw})
-        if (p) (void)hipFree(p);
-}
-
 // the buffers that do not depend on the projection; allocated by the first resident call
 static int rs_ensure(mtip2d_ctx* c) {
     if (c->r_alloc) return MTIP_OK;
@@ -1167,32 +1128,32 @@ static int rs_ensure(mtip2d_ctx* c) {
     (void)hipSetDevice(c->device);
     const size_t G = (size_t)c->N * c->n_phi, BG = (size_t)c->B * G, B = (size_t)c->B;
     for (int i = 0; i < 2; ++i) {
-        C2_CHECK(c, rs_alloc(&c->r_F[i], BG));
-        C2_CHECK(c, rs_alloc(&c->r_R[i], BG));
+        MTIP_HIP_CHECK(c, c->r_F[i].alloc(BG));
+        MTIP_HIP_CHECK(c, c->r_R[i].alloc(BG));
     }
-    C2_CHECK(c, rs_alloc(&c->r_C, BG));
-    C2_CHECK(c, rs_alloc(&c->r_H, BG));
-    C2_CHECK(c, rs_alloc(&c->r_D, BG));
-    C2_CHECK(c, rs_alloc(&c->r_Ft, BG));
-    C2_CHECK(c, rs_alloc(&c->r_wf, (size_t)c->N * c->N * c->n_phi));
-    C2_CHECK(c, rs_alloc(&c->r_wi, (size_t)c->N * c->N * c->n_phi));
-    C2_CHECK(c, rs_alloc(&c->r_Im, B * c->N * (c->M + 1)));
-    C2_CHECK(c, rs_alloc(&c->r_bestF, BG));
-    C2_CHECK(c, rs_alloc(&c->r_bestR, BG));
-    C2_CHECK(c, rs_alloc(&c->r_guess, BG));
-    C2_CHECK(c, rs_alloc(&c->r_fixed, BG));
-    C2_CHECK(c, rs_alloc(&c->r_sup, BG));
-    C2_CHECK(c, rs_alloc(&c->r_bestsup, BG));
-    C2_CHECK(c, rs_alloc(&c->r_swnew, BG));
-    C2_CHECK(c, rs_alloc(&c->r_S0, G));
-    C2_CHECK(c, rs_alloc(&c->r_flag, B));
-    C2_CHECK(c, rs_alloc(&c->r_ft, B));
-    C2_CHECK(c, rs_alloc(&c->r_enf, B));
-    C2_CHECK(c, rs_alloc(&c->r_sel, B));
-    C2_CHECK(c, rs_alloc(&c->r_part, B * c->N * 2));
-    C2_CHECK(c, rs_alloc(&c->r_part2, B * c->N * 2));
-    C2_CHECK(c, rs_alloc(&c->r_besterr, B));
-    C2_CHECK(c, rs_alloc(&c->r_recw, G));
+    MTIP_HIP_CHECK(c, c->r_C.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_H.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_D.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_Ft.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_wf.alloc((size_t)c->N * c->N * c->n_phi));
+    MTIP_HIP_CHECK(c, c->r_wi.alloc((size_t)c->N * c->N * c->n_phi));
+    MTIP_HIP_CHECK(c, c->r_Im.alloc(B * c->N * (c->M + 1)));
+    MTIP_HIP_CHECK(c, c->r_bestF.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_bestR.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_guess.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_fixed.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_sup.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_bestsup.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_swnew.alloc(BG));
+    MTIP_HIP_CHECK(c, c->r_S0.alloc(G));
+    MTIP_HIP_CHECK(c, c->r_flag.alloc(B));
+    MTIP_HIP_CHECK(c, c->r_ft.alloc(B));
+    MTIP_HIP_CHECK(c, c->r_enf.alloc(B));
+    MTIP_HIP_CHECK(c, c->r_sel.alloc(B));
+    MTIP_HIP_CHECK(c, c->r_part.alloc(B * c->N * 2));
+    MTIP_HIP_CHECK(c, c->r_part2.alloc(B * c->N * 2));
+    MTIP_HIP_CHECK(c, c->r_besterr.alloc(B));
+    MTIP_HIP_CHECK(c, c->r_recw.alloc(G));
     c->r_alloc = true;
     return MTIP_OK;
 }
@@ -1203,22 +1164,23 @@ static int rs_ensure_hist(mtip2d_ctx* c, long long need) {
     long long cap = c->r_cap > 0 ? c->r_cap : 256;
     while (cap < need) cap *= 2;
     const size_t B = (size_t)c->B, nu = (size_t)(c->r_n_used > 0 ? c->r_n_used : 1);
-    double *e = nullptr, *m = nullptr, *l = nullptr, *d = nullptr;
-    C2_CHECK(c, hipMalloc((void**)&e, cap * B * sizeof(double)));
-    C2_CHECK(c, hipMalloc((void**)&m, cap * B * sizeof(double)));
-    C2_CHECK(c, hipMalloc((void**)&l, cap * B * sizeof(double)));
-    C2_CHECK(c, hipMalloc((void**)&d, cap * B * nu * sizeof(double)));
-    C2_CHECK(c, hipStreamSynchronize(c->stream));
+    DevBuf<double> e, m, l, d;
+    MTIP_HIP_CHECK(c, e.alloc(cap * B));
+    MTIP_HIP_CHECK(c, m.alloc(cap * B));
+    MTIP_HIP_CHECK(c, l.alloc(cap * B));
+    MTIP_HIP_CHECK(c, d.alloc(cap * B * nu));
+    MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     if (c->r_steps > 0) {
-        C2_CHECK(c, hipMemcpy(e, c->r_herr, c->r_steps * B * sizeof(double), hipMemcpyDeviceToDevice));
-        C2_CHECK(c, hipMemcpy(m, c->r_hmain, c->r_steps * B * sizeof(double), hipMemcpyDeviceToDevice));
-        C2_CHECK(c, hipMemcpy(l, c->r_hrl2, c->r_steps * B * sizeof(double), hipMemcpyDeviceToDevice));
-        C2_CHECK(c, hipMemcpy(d, c->r_hdeg2, c->r_steps * B * nu * sizeof(double), hipMemcpyDeviceToDevice));
-        C2_CHECK(c, hipDeviceSynchronize());
+        MTIP_HIP_CHECK(c, hipMemcpy(e, c->r_herr, c->r_steps * B * sizeof(double), hipMemcpyDeviceToDevice));
+        MTIP_HIP_CHECK(c, hipMemcpy(m, c->r_hmain, c->r_steps * B * sizeof(double), hipMemcpyDeviceToDevice));
+        MTIP_HIP_CHECK(c, hipMemcpy(l, c->r_hrl2, c->r_steps * B * sizeof(double), hipMemcpyDeviceToDevice));
+        MTIP_HIP_CHECK(c, hipMemcpy(d, c->r_hdeg2, c->r_steps * B * nu * sizeof(double), hipMemcpyDeviceToDevice));
+        MTIP_HIP_CHECK(c, hipDeviceSynchronize());
     }
-    for (void* p : {(void*)c->r_herr, (void*)c->r_hmain, (void*)c->r_hrl2, (void*)c->r_hdeg2})
-        if (p) (void)hipFree(p);
-    c->r_herr = e; c->r_hmain = m; c->r_hrl2 = l; c->r_hdeg2 = d;
+    c->r_herr = std::move(e);
+    c->r_hmain = std::move(m);
+    c->r_hrl2 = std::move(l);
+    c->r_hdeg2 = std::move(d);
     c->r_cap = cap;
     return MTIP_OK;
 }
@@ -1242,7 +1204,7 @@ static void rs_refresh_coefficients(mtip2d_ctx* c) { c2_dft(c, c->r_R[c->r_cur],
 static dim3 rs_grid_points(const mtip2d_ctx* c) { return dim3((unsigned)div_up((long long)c->N * c->n_phi, 256), (unsigned)c->B); }
 
 static int rs_copy_d2d(mtip2d_ctx* c, void* dst, const void* src, size_t n) {
-    C2_CHECK(c, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream));
+    MTIP_HIP_CHECK(c, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream));
     return MTIP_OK;
 }
 
@@ -1300,7 +1262,7 @@ int mtip2d_set_density(mtip2d_ctx* c, int batch, const mtip_cdouble* rho) {
     int r = rs_ensure(c);
     if (r) return r;
     const size_t G = (size_t)c->N * c->n_phi;
-    C2_CHECK(c, c2_copy(c, c->r_guess + (size_t)batch * G, rho, G * sizeof(double2)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_guess + (size_t)batch * G, rho, G * sizeof(double2)));
     return MTIP_OK;
 }
 
@@ -1310,8 +1272,8 @@ int mtip2d_set_initial_support(mtip2d_ctx* c, const uint8_t* support) {
     int r = rs_ensure(c);
     if (r) return r;
     const size_t G = (size_t)c->N * c->n_phi;
-    C2_CHECK(c, c2_copy(c, c->r_S0, support, G));
-    for (int b = 0; b < c->B; ++b) C2_CHECK(c, c2_copy(c, c->r_sup + (size_t)b * G, support, G));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_S0, support, G));
+    for (int b = 0; b < c->B; ++b) MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_sup + (size_t)b * G, support, G));
     c->r_have_S0 = true;
     return MTIP_OK;
 }
@@ -1322,7 +1284,7 @@ int mtip2d_set_support(mtip2d_ctx* c, int batch, const uint8_t* support) {
     int r = rs_ensure(c);
     if (r) return r;
     const size_t G = (size_t)c->N * c->n_phi;
-    C2_CHECK(c, c2_copy(c, c->r_sup + (size_t)batch * G, support, G));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_sup + (size_t)batch * G, support, G));
     return MTIP_OK;
 }
 
@@ -1332,17 +1294,20 @@ int mtip2d_init_state(mtip2d_ctx* c) {
     if (!c->r_alloc || !c->r_have_S0) C2_FAIL(c, MTIP_ESTATE, "init_state: mtip2d_set_density (every restart) and mtip2d_set_initial_support come first");
     (void)hipSetDevice(c->device);
     const size_t BG = (size_t)c->B * c->N * c->n_phi;
-    C2_CHECK(c, hipStreamSynchronize(c->stream));
+    MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     // the per-order buffers follow the projection (none yet: the *_non_FXS methods alone can run)
     const int nu = c->n_used > 0 ? c->n_used : 1;
     if (nu != c->r_n_used) {
-        for (void* p : {(void*)c->r_sp, (void*)c->r_unk, (void*)c->r_herr, (void*)c->r_hmain, (void*)c->r_hrl2, (void*)c->r_hdeg2})
-            if (p) (void)hipFree(p);
-        c->r_sp = nullptr; c->r_unk = nullptr; c->r_herr = c->r_hmain = c->r_hrl2 = c->r_hdeg2 = nullptr;
+        c->r_sp.reset();
+        c->r_unk.reset();
+        c->r_herr.reset();
+        c->r_hmain.reset();
+        c->r_hrl2.reset();
+        c->r_hdeg2.reset();
         c->r_cap = 0;
         c->r_n_used = nu;
-        C2_CHECK(c, rs_alloc(&c->r_sp, (size_t)c->B * nu * c->N));
-        C2_CHECK(c, rs_alloc(&c->r_unk, (size_t)c->B * nu));
+        MTIP_HIP_CHECK(c, c->r_sp.alloc((size_t)c->B * nu * c->N));
+        MTIP_HIP_CHECK(c, c->r_unk.alloc((size_t)c->B * nu));
     }
     c->r_steps = 0;
     int r = rs_ensure_hist(c, 256);
@@ -1356,15 +1321,15 @@ int mtip2d_init_state(mtip2d_ctx* c) {
     // reconstruct.py:962-963: the state starts from F0 = FT(guess), rho0 = IFT(F0)
     rs_ft(c, c->r_guess, c->r_F[0], 0);
     rs_ft(c, c->r_F[0], c->r_R[0], 1);
-    for (double2* dst : {c->r_F[1], c->r_bestF}) if ((r = rs_copy_d2d(c, dst, c->r_F[0], BG * sizeof(double2)))) return r;
-    for (double2* dst : {c->r_R[1], c->r_bestR}) if ((r = rs_copy_d2d(c, dst, c->r_R[0], BG * sizeof(double2)))) return r;
+    for (double2* dst : {(double2*)c->r_F[1], (double2*)c->r_bestF}) if ((r = rs_copy_d2d(c, dst, c->r_F[0], BG * sizeof(double2)))) return r;
+    for (double2* dst : {(double2*)c->r_R[1], (double2*)c->r_bestR}) if ((r = rs_copy_d2d(c, dst, c->r_R[0], BG * sizeof(double2)))) return r;
     hipLaunchKernelGGL(k2d_rs_fill_state, rs_grid_points(c), dim3(256), 0, c->stream, (const uint8_t*)c->r_S0, c->r_sup, c->r_bestsup, c->r_besterr,
                        (long long)c->N * c->n_phi);
     c->r_cur = 0;
     c->r_fixed_valid = false;
     c->r_ft_mixed = false;
     rs_refresh_coefficients(c);
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, hipGetLastError());
     c->r_ready = true;
     return MTIP_OK;
 }
@@ -1377,7 +1342,7 @@ int mtip2d_set_ft_stab_mask(mtip2d_ctx* c, const uint8_t* mask) {
     }
     int r = rs_ensure(c);
     if (r) return r;
-    C2_CHECK(c, c2_copy(c, c->r_ft, mask, (size_t)c->B));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_ft, mask, (size_t)c->B));
     c->r_ft_mixed = true;
     return MTIP_OK;
 }
@@ -1392,17 +1357,14 @@ int mtip2d_set_reciprocal_metrics(mtip2d_ctx* c, uint32_t which, const mtip_cdou
     int r = rs_ensure(c);
     if (r) return r;
     if (which & 1) {
-        C2_CHECK(c, hipStreamSynchronize(c->stream));
-        for (void* p : {(void*)c->r_deg2ref, (void*)c->r_deg2norm})
-            if (p) (void)hipFree(p);
-        c->r_deg2ref = nullptr; c->r_deg2norm = nullptr;
+        MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
         const size_t nn = (size_t)c->n_used * c->N * c->N;
-        C2_CHECK(c, rs_alloc(&c->r_deg2ref, nn));
-        C2_CHECK(c, rs_alloc(&c->r_deg2norm, (size_t)c->n_used));
-        C2_CHECK(c, c2_copy(c, c->r_deg2ref, deg2_reference, nn * sizeof(double2)));
-        C2_CHECK(c, c2_copy(c, c->r_deg2norm, deg2_norms, (size_t)c->n_used * sizeof(double)));
+        MTIP_HIP_CHECK(c, c->r_deg2ref.alloc(nn));
+        MTIP_HIP_CHECK(c, c->r_deg2norm.alloc((size_t)c->n_used));
+        MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_deg2ref, deg2_reference, nn * sizeof(double2)));
+        MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_deg2norm, deg2_norms, (size_t)c->n_used * sizeof(double)));
     }
-    if (which & 2) C2_CHECK(c, c2_copy(c, c->r_recw, l2_weights, (size_t)c->N * c->n_phi * sizeof(double)));
+    if (which & 2) MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_recw, l2_weights, (size_t)c->N * c->n_phi * sizeof(double)));
     c->r_metrics = which;
     return MTIP_OK;
 }
@@ -1450,7 +1412,7 @@ int mtip2d_run_async(mtip2d_ctx* c, int method, int ft_stab, int n_steps, const 
     }
     const int ft_mode = !ft_stab ? 0 : (c->r_ft_mixed ? 2 : 1);
     for (int s = 0; s < n_steps; ++s) rs_enqueue_step(c, method, ft_mode, betas[s]);
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -1458,7 +1420,7 @@ int mtip2d_fetch_errors(mtip2d_ctx* c, int64_t first, int64_t n, double* real_er
     if (!c) return MTIP_EINVAL;
     if (first < 0 || n < 0 || first + n > c->r_steps || !real_err) C2_FAIL(c, MTIP_EINVAL, "fetch_errors: range beyond the steps done / null buffer");
     (void)hipSetDevice(c->device);
-    if (n) C2_CHECK(c, c2_copy(c, real_err, c->r_herr + (size_t)first * c->B, (size_t)n * c->B * sizeof(double)));
+    if (n) MTIP_HIP_CHECK(c, mtip_copy(c->stream, real_err, c->r_herr + (size_t)first * c->B, (size_t)n * c->B * sizeof(double)));
     return MTIP_OK;
 }
 
@@ -1466,7 +1428,7 @@ int mtip2d_fetch_main_errors(mtip2d_ctx* c, int64_t first, int64_t n, double* ma
     if (!c) return MTIP_EINVAL;
     if (first < 0 || n < 0 || first + n > c->r_steps || !main_err) C2_FAIL(c, MTIP_EINVAL, "fetch_main_errors: range beyond the steps done / null buffer");
     (void)hipSetDevice(c->device);
-    if (n) C2_CHECK(c, c2_copy(c, main_err, c->r_hmain + (size_t)first * c->B, (size_t)n * c->B * sizeof(double)));
+    if (n) MTIP_HIP_CHECK(c, mtip_copy(c->stream, main_err, c->r_hmain + (size_t)first * c->B, (size_t)n * c->B * sizeof(double)));
     return MTIP_OK;
 }
 
@@ -1475,8 +1437,8 @@ int mtip2d_fetch_reciprocal_metrics(mtip2d_ctx* c, int64_t first, int64_t n, dou
     if (first < 0 || n < 0 || first + n > c->r_steps) C2_FAIL(c, MTIP_EINVAL, "fetch_reciprocal_metrics: range beyond the steps done");
     if ((deg2 && !(c->r_metrics & 1)) || (l2 && !(c->r_metrics & 2))) C2_FAIL(c, MTIP_ESTATE, "fetch_reciprocal_metrics: metric not enabled");
     (void)hipSetDevice(c->device);
-    if (n && deg2) C2_CHECK(c, c2_copy(c, deg2, c->r_hdeg2 + (size_t)first * c->B * c->r_n_used, (size_t)n * c->B * c->r_n_used * sizeof(double)));
-    if (n && l2) C2_CHECK(c, c2_copy(c, l2, c->r_hrl2 + (size_t)first * c->B, (size_t)n * c->B * sizeof(double)));
+    if (n && deg2) MTIP_HIP_CHECK(c, mtip_copy(c->stream, deg2, c->r_hdeg2 + (size_t)first * c->B * c->r_n_used, (size_t)n * c->B * c->r_n_used * sizeof(double)));
+    if (n && l2) MTIP_HIP_CHECK(c, mtip_copy(c->stream, l2, c->r_hrl2 + (size_t)first * c->B, (size_t)n * c->B * sizeof(double)));
     return MTIP_OK;
 }
 
@@ -1484,7 +1446,7 @@ int mtip2d_run(mtip2d_ctx* c, int method, int ft_stab, int n_steps, const double
     int r = mtip2d_run_async(c, method, ft_stab, n_steps, betas);
     if (r) return r;
     if (!real_err) {
-        C2_CHECK(c, hipStreamSynchronize(c->stream));
+        MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
         return MTIP_OK;
     }
     return mtip2d_fetch_errors(c, c->r_steps - n_steps, n_steps, real_err);
@@ -1511,8 +1473,8 @@ int mtip2d_shrinkwrap(mtip2d_ctx* c, double sigma, double threshold, double erro
     hipLaunchKernelGGL(k2d_rs_support, rs_grid_points(c), dim3(256), 0, c->stream, (const uint8_t*)c->r_swnew, (const uint8_t*)c->r_S0, c->r_sup,
                        c->r_steps > 0 ? (const double*)(c->r_hmain + (size_t)(c->r_steps - 1) * c->B) : (const double*)nullptr, error_limit, c->r_enf,
                        (long long)c->N * c->n_phi);
-    C2_CHECK(c, hipGetLastError());
-    if (enforced) C2_CHECK(c, c2_copy(c, enforced, c->r_enf, (size_t)c->B));
+    MTIP_HIP_CHECK(c, hipGetLastError());
+    if (enforced) MTIP_HIP_CHECK(c, mtip_copy(c->stream, enforced, c->r_enf, (size_t)c->B));
     return MTIP_OK;
 }
 
@@ -1525,7 +1487,7 @@ int mtip2d_refresh_reciprocal_density(mtip2d_ctx* c) {
     if ((r = rs_copy_d2d(c, c->r_F[c->r_cur], c->r_R[c->r_cur], bytes))) return r;
     if ((r = rs_copy_d2d(c, c->r_R[c->r_cur], c->d_c, bytes))) return r;
     rs_refresh_coefficients(c);
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -1544,12 +1506,12 @@ int mtip2d_select_best_where(mtip2d_ctx* c, const uint8_t* select) {
     if (!c) return MTIP_EINVAL;
     int r = rs_require_state(c, "select_best");
     if (r) return r;
-    if (select) C2_CHECK(c, c2_copy(c, c->r_sel, select, (size_t)c->B));
+    if (select) MTIP_HIP_CHECK(c, mtip_copy(c->stream, c->r_sel, select, (size_t)c->B));
     hipLaunchKernelGGL(k2d_rs_select, rs_grid_points(c), dim3(256), 0, c->stream, select ? (const uint8_t*)c->r_sel : (const uint8_t*)nullptr,
                        c->r_F[c->r_cur], c->r_R[c->r_cur], c->r_sup, (const double2*)c->r_bestF, (const double2*)c->r_bestR,
                        (const uint8_t*)c->r_bestsup, (long long)c->N * c->n_phi);
     rs_refresh_coefficients(c);
-    C2_CHECK(c, hipGetLastError());
+    MTIP_HIP_CHECK(c, hipGetLastError());
     return MTIP_OK;
 }
 
@@ -1561,7 +1523,7 @@ static int rs_get(mtip2d_ctx* c, int batch, int which, void* out, const void* la
     if (r) return r;
     if (batch < 0 || batch >= c->B || which < 0 || which > 1 || !out) C2_FAIL(c, MTIP_EINVAL, "get: batch index, which = 0 (latest) / 1 (best), buffer not null");
     const size_t G = (size_t)c->N * c->n_phi;
-    C2_CHECK(c, c2_copy(c, out, (const char*)(which ? best : latest) + (size_t)batch * G * elem, G * elem));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, out, (const char*)(which ? best : latest) + (size_t)batch * G * elem, G * elem));
     return MTIP_OK;
 }
 
@@ -1585,7 +1547,7 @@ int mtip2d_get_unknowns(mtip2d_ctx* c, int batch, mtip_cdouble* unknowns) {
     int r = rs_require_state(c, "get_unknowns");
     if (r) return r;
     if (batch < 0 || batch >= c->B || !unknowns || c->n_used == 0) C2_FAIL(c, MTIP_EINVAL, "get_unknowns: batch index / null buffer / no projection");
-    C2_CHECK(c, c2_copy(c, unknowns, c->r_unk + (size_t)batch * c->n_used, (size_t)c->n_used * sizeof(double2)));
+    MTIP_HIP_CHECK(c, mtip_copy(c->stream, unknowns, c->r_unk + (size_t)batch * c->n_used, (size_t)c->n_used * sizeof(double2)));
     return MTIP_OK;
 }
 
@@ -1593,7 +1555,7 @@ int mtip2d_get_best_error(mtip2d_ctx* c, double* best_error, int64_t* n_steps_do
     if (!c) return MTIP_EINVAL;
     int r = rs_require_state(c, "get_best_error");
     if (r) return r;
-    if (best_error) C2_CHECK(c, c2_copy(c, best_error, c->r_besterr, (size_t)c->B * sizeof(double)));
+    if (best_error) MTIP_HIP_CHECK(c, mtip_copy(c->stream, best_error, c->r_besterr, (size_t)c->B * sizeof(double)));
     if (n_steps_done) *n_steps_done = c->r_steps;
     return MTIP_OK;
 }
@@ -1601,7 +1563,7 @@ int mtip2d_get_best_error(mtip2d_ctx* c, double* best_error, int64_t* n_steps_do
 int mtip2d_synchronize(mtip2d_ctx* c) {
     if (!c) return MTIP_EINVAL;
     (void)hipSetDevice(c->device);
-    C2_CHECK(c, hipStreamSynchronize(c->stream));
+    MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     return MTIP_OK;
 }
 

@@ -959,7 +959,7 @@ static int build_proj_tiles(mtip_ctx* c) {
         }
         if (t.empty()) t.push_back(0);
         c->n_pg_tiles[op] = (int)t.size();
-        if (hipMalloc((void**)&c->d_pg_tiles[op], t.size() * sizeof(int)) != hipSuccess) return MTIP_ENOMEM;
+        if (c->d_pg_tiles[op].alloc(t.size()) != hipSuccess) return MTIP_ENOMEM;
         (void)mtip_copy(c, c->d_pg_tiles[op], t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
     }
     // the fused pairs: 4 = k_proj_xw (order | row tile << 8, active orders), 5 = k_proj_ua (order | column tile << 8, used orders)
@@ -971,7 +971,7 @@ static int build_proj_tiles(mtip_ctx* c) {
         }
         c->n_pg_tiles[op] = (int)t.size();
         if (t.empty()) t.push_back(0);
-        if (hipMalloc((void**)&c->d_pg_tiles[op], t.size() * sizeof(int)) != hipSuccess) return MTIP_ENOMEM;
+        if (c->d_pg_tiles[op].alloc(t.size()) != hipSuccess) return MTIP_ENOMEM;
         (void)mtip_copy(c, c->d_pg_tiles[op], t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
     }
     return MTIP_OK;
@@ -1063,10 +1063,9 @@ int build_jacobi_schedule(mtip_ctx* c, int kmax) {
         for (auto& rd : rounds) all.insert(all.end(), rd.begin(), rd.end());
     }
     if (all.empty()) all.push_back(0);
-    if (c->d_jsched) { (void)hipFree(c->d_jsched); (void)hipFree(c->d_jsched_off); (void)hipFree(c->d_jsched_rounds); }
-    if (hipMalloc((void**)&c->d_jsched, all.size() * sizeof(int)) != hipSuccess) return MTIP_ENOMEM;
-    if (hipMalloc((void**)&c->d_jsched_off, off.size() * sizeof(int)) != hipSuccess) return MTIP_ENOMEM;
-    if (hipMalloc((void**)&c->d_jsched_rounds, nrd.size() * sizeof(int)) != hipSuccess) return MTIP_ENOMEM;
+    if (c->d_jsched.alloc(all.size()) != hipSuccess) return MTIP_ENOMEM;
+    if (c->d_jsched_off.alloc(off.size()) != hipSuccess) return MTIP_ENOMEM;
+    if (c->d_jsched_rounds.alloc(nrd.size()) != hipSuccess) return MTIP_ENOMEM;
     (void)mtip_copy(c, c->d_jsched, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice);
     (void)mtip_copy(c, c->d_jsched_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice);
     (void)mtip_copy(c, c->d_jsched_rounds, nrd.data(), nrd.size() * sizeof(int), hipMemcpyHostToDevice);
@@ -1199,7 +1198,7 @@ static int launch_project_coefficients_impl(mtip_ctx* c, const double2* Ilm, dou
             std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return c->kl[x] * (2 * x + 1) > c->kl[y] * (2 * y + 1); });
             c->n_jorder = (int)ord.size();
             if (ord.empty()) ord.push_back(0);
-            if (hipMalloc((void**)&c->d_jorder, ord.size() * sizeof(int)) != hipSuccess) {
+            if (c->d_jorder.alloc(ord.size()) != hipSuccess) {
                 c->err = "polar factor order list: out of device memory";
                 return MTIP_ENOMEM;
             }

@@ -1301,9 +1301,9 @@ static int build_rproj_tables(mtip_ctx* c) {
     std::vector<int> flat(slots.size() * slot_len, -1);
     for (size_t s = 0; s < slots.size(); ++s)
         for (size_t i = 0; i < slots[s].size(); ++i) flat[s * slot_len + i] = slots[s][i];
-    if (hipMalloc((void**)&c->d_rp_DV, DV.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&c->d_rp_Vt, Vt.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&c->d_rp_slots, flat.size() * sizeof(int)) != hipSuccess)
+    if (c->d_rp_DV.alloc(DV.size()) != hipSuccess ||
+        c->d_rp_Vt.alloc(Vt.size()) != hipSuccess ||
+        c->d_rp_slots.alloc(flat.size()) != hipSuccess)
         return MTIP_ENOMEM;
     (void)mtip_copy(c, c->d_rp_DV, DV.data(), DV.size() * sizeof(double), hipMemcpyHostToDevice);
     (void)mtip_copy(c, c->d_rp_Vt, Vt.data(), Vt.size() * sizeof(double), hipMemcpyHostToDevice);
@@ -1316,12 +1316,9 @@ static int build_rproj_tables(mtip_ctx* c) {
 void free_rproj_tables(mtip_ctx* c) {
     if (c->d_rp_slots == nullptr && c->d_rp_DV == nullptr) return;
     (void)hipStreamSynchronize(c->stream);
-    if (c->d_rp_DV) (void)hipFree(c->d_rp_DV);
-    if (c->d_rp_Vt) (void)hipFree(c->d_rp_Vt);
-    if (c->d_rp_slots) (void)hipFree(c->d_rp_slots);
-    c->d_rp_DV = nullptr;
-    c->d_rp_Vt = nullptr;
-    c->d_rp_slots = nullptr;
+    c->d_rp_DV.reset();
+    c->d_rp_Vt.reset();
+    c->d_rp_slots.reset();
 }
 
 // in place on `coef` (the caller has copied I_lm there when its output is a different buffer)
@@ -1336,7 +1333,7 @@ int launch_rproj(mtip_ctx* c, double2* coef) {
     RProjArgs a;
     a.coef = reinterpret_cast<double*>(coef);
     a.DV = c->d_rp_DV; a.Vt = c->d_rp_Vt;
-    a.Vr = reinterpret_cast<double*>(c->d_Vr);
+    a.Vr = reinterpret_cast<double*>((double2*)c->d_Vr);
     a.U = c->d_U;
     a.rmask = c->d_rmask;
     a.kl = c->d_kl; a.voff = c->d_voff; a.uoff = c->d_uoff; a.xoff = c->d_xoff;

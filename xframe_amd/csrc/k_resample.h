@@ -314,22 +314,15 @@ struct mtip_resample {
     mtip_resample_cfg cfg{};
     int npole = 0;
     double z[2] = {0.0, 0.0}, zn_h[2] = {0.0, 0.0}, zn_w[2] = {0.0, 0.0}, gain = 1.0;
-    double *d_x = nullptr, *d_y = nullptr, *d_bg = nullptr;
-    uint8_t* d_bin = nullptr;
-    double* d_ci = nullptr;            // (RS_CHUNK, H, W)
-    double* d_cm = nullptr;            // (RS_CHUNK, H, W), allocated by the first batch with per-pattern masks
-    double* d_cms = nullptr;           // (H, W) the static mask's coefficients
-    uint8_t* d_mstat = nullptr;        // (n_points) its polar values
+    DevBuf<double> d_x, d_y, d_bg;
+    DevBuf<uint8_t> d_bin;
+    DevBuf<double> d_ci;               // (RS_CHUNK, H, W)
+    DevBuf<double> d_cm;               // (RS_CHUNK, H, W), allocated by the first batch with per-pattern masks
+    DevBuf<double> d_cms;              // (H, W) the static mask's coefficients
+    DevBuf<uint8_t> d_mstat;           // (n_points) its polar values
     bool have_static = false;
-    int* d_bad = nullptr;              // [0] of the batch, [1] of the static set-up
+    DevBuf<int> d_bad;                 // [0] of the batch, [1] of the static set-up
 };
-
-static inline void rs_free(mtip_resample* r) {
-    for (void* p : {(void*)r->d_x, (void*)r->d_y, (void*)r->d_bg, (void*)r->d_bin, (void*)r->d_ci, (void*)r->d_cm, (void*)r->d_cms,
-                    (void*)r->d_mstat, (void*)r->d_bad})
-        if (p) (void)hipFree(p);
-    delete r;
-}
 
 extern "C" mtip_resample* mtip_resample_create(mtip_ctx* c, const mtip_resample_cfg* cfg, const double* cart_x, const double* cart_y,
                                                const uint8_t* binary_mask, const double* background) {
@@ -352,7 +345,7 @@ extern "C" mtip_resample* mtip_resample_create(mtip_ctx* c, const mtip_resample_
     }
     (void)hipSetDevice(c->device);
     const size_t frame = (size_t)cfg->H * cfg->W, np = (size_t)cfg->n_points;
-    const size_t need = frame * 8 * (2 * RS_CHUNK + 2) + frame + np * 17, fr = cor_free_memory();
+    const size_t need = frame * 8 * (2 * RS_CHUNK + 2) + frame + np * 17, fr = mtip_free_memory();
     if (need > fr) {
         snprintf(msg, sizeof msg, "resample_create: %d patterns of %d x %d coefficients need %.3f GB; %.3f GB of device memory are free",
                  RS_CHUNK, cfg->H, cfg->W, (double)need * 1e-9, (double)fr * 1e-9);
@@ -383,19 +376,19 @@ extern "C" mtip_resample* mtip_resample_create(mtip_ctx* c, const mtip_resample_
         gain *= (1.0L - zl[k]) * (1.0L - 1.0L / zl[k]);
     }
     r->gain = (double)gain;
-    hipError_t e = hipMalloc(&r->d_x, np * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&r->d_y, np * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&r->d_ci, frame * RS_CHUNK * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&r->d_bad, 2 * sizeof(int));
-    if (e == hipSuccess && cfg->has_binary_mask) e = hipMalloc(&r->d_bin, frame);
-    if (e == hipSuccess && cfg->has_background) e = hipMalloc(&r->d_bg, frame * sizeof(double));
+    hipError_t e = r->d_x.alloc(np);
+    if (e == hipSuccess) e = r->d_y.alloc(np);
+    if (e == hipSuccess) e = r->d_ci.alloc(frame * RS_CHUNK);
+    if (e == hipSuccess) e = r->d_bad.alloc(2);
+    if (e == hipSuccess && cfg->has_binary_mask) e = r->d_bin.alloc(frame);
+    if (e == hipSuccess && cfg->has_background) e = r->d_bg.alloc(frame);
     if (e == hipSuccess) e = mtip_copy(c, r->d_x, cart_x, np * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = mtip_copy(c, r->d_y, cart_y, np * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && cfg->has_binary_mask) e = mtip_copy(c, r->d_bin, binary_mask, frame, hipMemcpyHostToDevice);
     if (e == hipSuccess && cfg->has_background) e = mtip_copy(c, r->d_bg, background, frame * sizeof(double), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         c->err = std::string("resample_create: ") + hipGetErrorString(e);
-        rs_free(r);
+        delete r;
         return nullptr;
     }
     return r;
@@ -405,7 +398,7 @@ extern "C" void mtip_resample_destroy(mtip_resample* r) {
     if (!r) return;
     (void)hipSetDevice(r->c->device);
     (void)hipStreamSynchronize(r->c->stream);
-    rs_free(r);
+    delete r;
 }
 
 // the Cartesian mask does not depend on the pattern
@@ -477,8 +470,8 @@ static inline hipError_t rs_run(mtip_resample* r, int P, const void* images, boo
     g.W = f.W;
     g.n_points = f.n_points;
     if (e == hipSuccess && stat && !r->have_static) {
-        e = hipMalloc(&r->d_cms, frame * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&r->d_mstat, np);
+        e = r->d_cms.alloc(frame);
+        if (e == hipSuccess) e = r->d_mstat.alloc(np);
         if (e == hipSuccess) {
             RsArgs am = a;
             am.coef[1] = r->d_cms;
@@ -493,7 +486,7 @@ static inline hipError_t rs_run(mtip_resample* r, int P, const void* images, boo
             r->have_static = true;
         }
     }
-    if (e == hipSuccess && !stat && !r->d_cm) e = hipMalloc(&r->d_cm, frame * RS_CHUNK * sizeof(double));
+    if (e == hipSuccess && !stat && !r->d_cm) e = r->d_cm.alloc(frame * RS_CHUNK);
     const size_t px = f32 ? sizeof(float) : sizeof(double);
     for (int p0 = 0; e == hipSuccess && p0 < P; p0 += RS_CHUNK) {
         const int pc = std::min(RS_CHUNK, P - p0);
@@ -505,9 +498,9 @@ static inline hipError_t rs_run(mtip_resample* r, int P, const void* images, boo
         a.narr = stat ? 1 : 2;
         rs_filter(r, a, pc, f32);
         g.ci = r->d_ci;
-        g.cm = stat ? nullptr : r->d_cm;
+        g.cm = stat ? nullptr : (const double*)r->d_cm;
         g.cm_stride = frame;
-        g.mstat = stat ? r->d_mstat : nullptr;
+        g.mstat = stat ? (const uint8_t*)r->d_mstat : nullptr;
         g.out_img = out_img + (size_t)p0 * np;
         g.out_mask = out_mask + (size_t)p0 * np;
         g.bad = r->d_bad;
@@ -574,25 +567,21 @@ extern "C" int mtip_correlate_add_detector(mtip_correlate* h, mtip_resample* r, 
     const size_t frame = (size_t)r->cfg.H * r->cfg.W, np = (size_t)r->cfg.n_points, P = (size_t)n_patterns;
     DevView v_img(c, images, P * frame * (is_float32 ? sizeof(float) : sizeof(double)), true, false);
     DevView v_mask(c, masks, P * frame, true, false);
-    double* d_pi = nullptr;
-    uint8_t* d_pm = nullptr;
+    DevBuf<double> d_pi;
+    DevBuf<uint8_t> d_pm;
     int64_t bad = 0;
     hipError_t e = v_img.err != hipSuccess ? v_img.err : v_mask.err;
-    if (e == hipSuccess) e = hipMalloc(&d_pi, P * np * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_pm, P * np);
+    if (e == hipSuccess) e = d_pi.alloc(P * np);
+    if (e == hipSuccess) e = d_pm.alloc(P * np);
     if (e == hipSuccess) e = rs_run(r, n_patterns, v_img.dev, is_float32 != 0, (const uint8_t*)v_mask.dev, d_pi, d_pm, &bad);
     if (n_bad_mask) *n_bad_mask = bad;
-    int rc = MTIP_OK;
     if (e != hipSuccess) {
         c->err = std::string("correlate_add_detector: ") + hipGetErrorString(e);
-        rc = e == hipErrorOutOfMemory ? MTIP_ENOMEM : MTIP_EHIP;
-    } else if (bad != 0) {
-        c->err = "correlate_add_detector: mask values other than 0 / 1 after the resampling; nothing was accumulated";
-        rc = MTIP_EINVAL;
-    } else {
-        rc = mtip_correlate_add(h, n_patterns, d_pi, d_pm);
+        return e == hipErrorOutOfMemory ? MTIP_ENOMEM : MTIP_EHIP;
     }
-    if (d_pi) (void)hipFree(d_pi);
-    if (d_pm) (void)hipFree(d_pm);
-    return rc;
+    if (bad != 0) {
+        c->err = "correlate_add_detector: mask values other than 0 / 1 after the resampling; nothing was accumulated";
+        return MTIP_EINVAL;
+    }
+    return mtip_correlate_add(h, n_patterns, d_pi, d_pm);
 }

@@ -441,7 +441,7 @@ int launch_sht_forward(mtip_ctx* c, const double2* grid, double2* coeff, int pro
     size_t sm;
     fft_launch_dims(c, nrows, &gr, &bl, &sm);
     const double norm = 2.0 * 3.14159265358979323846 / c->np;
-    const int* sl = in_slot >= 0 ? c->d_slot : nullptr;
+    const int* sl = in_slot >= 0 ? (const int*)c->d_slot : nullptr;
     if (prologue == MTIP_PRE_SQUARE)
         hipLaunchKernelGGL(k_fft_fwd<MTIP_PRE_SQUARE>, gr, bl, sm, c->stream, grid, c->d_g, c->d_tw, c->d_gw, c->np, c->nt, c->L, nrows, norm, sl, in_slot, c->B, (long long)c->N * c->nt);
     else if (prologue == MTIP_PRE_ABS)
@@ -472,7 +472,7 @@ int launch_sht_inverse(mtip_ctx* c, const double2* coeff, double2* grid, const I
     fft_launch_dims(c, nrows, &gr, &bl, &sm);
     const double2* g = c->d_g;
     const double2* tw = c->d_tw;
-    const int* sl = epi.out_slot >= 0 ? c->d_slot : nullptr;
+    const int* sl = epi.out_slot >= 0 ? (const int*)c->d_slot : nullptr;
     switch (epi.mode) {
         case EPI_MODULUS:
             hipLaunchKernelGGL(k_fft_inv<EPI_MODULUS>, gr, bl, sm, c->stream, g, grid, tw, c->np, c->nt, c->L, c->N, nrows, epi.F, epi.shell_scale, sl, epi.out_slot, c->B);

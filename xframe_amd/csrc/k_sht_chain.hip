@@ -505,7 +505,7 @@ int launch_sht_chain(mtip_ctx* c, const double2* coeff, double2* grid, const Inv
     a.cost = c->d_cost;
     a.twN_g = c->d_twN;
     a.Fin = epi.F;
-    a.slot = (epi.out_slot >= 0 || epi.mode == EPI_REAL_UPDATE) ? c->d_slot : nullptr;
+    a.slot = (epi.out_slot >= 0 || epi.mode == EPI_REAL_UPDATE) ? (const int*)c->d_slot : nullptr;
     a.mk = c->d_mk;
     a.re = epi.real;
     a.npairs = c->npairs;

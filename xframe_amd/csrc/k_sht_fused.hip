@@ -257,7 +257,7 @@ template <int PRE>
 static void launch_fwd_t(mtip_ctx* c, const double2* grid, double2* coeff, int in_slot) {
     const ShtPlan& p = c->sht;
     const double norm = 2.0 * 3.14159265358979323846 / c->np;
-    const int* sl = in_slot >= 0 ? c->d_slot : nullptr;
+    const int* sl = in_slot >= 0 ? (const int*)c->d_slot : nullptr;
     const dim3 gr((unsigned)(c->B * c->N)), bl(SF_THREADS);
 #define FWD_ARGS grid, coeff, (const double*)c->d_PT, (const int*)c->d_lmtab, (const double2*)c->d_tw, (const double*)c->d_gw, \
                  c->np, c->nt, c->L, c->npairs, p.fwd_rp, norm, sl, in_slot, c->B, c->N
@@ -275,7 +275,7 @@ void launch_sht_forward_fused(mtip_ctx* c, const double2* grid, double2* coeff, 
 
 int launch_sht_inverse_fused(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
     const ShtPlan& p = c->sht;
-    const int* sl = epi.out_slot >= 0 ? c->d_slot : nullptr;
+    const int* sl = epi.out_slot >= 0 ? (const int*)c->d_slot : nullptr;
     const dim3 gr((unsigned)(c->B * c->N)), bl(SF_THREADS);
 #define INV_ARGS coeff, grid, (const double*)c->d_PT, (const int*)c->d_poff, (const double2*)c->d_tw, c->np, c->nt, c->L, \
                  c->npairs, p.inv_rp, p.inv_jl, c->N, epi.F, epi.shell_scale, sl, epi.out_slot, c->B

@@ -641,7 +641,7 @@ template <int PRE, int R1, int R2>
 static void launch_fwd_r(mtip_ctx* c, const double2* grid, double2* coeff, int in_slot) {
     const ShtPlan& p = c->sht;
     const double norm = 2.0 * 3.14159265358979323846 / c->np;
-    const int* sl = in_slot >= 0 ? c->d_slot : nullptr;
+    const int* sl = in_slot >= 0 ? (const int*)c->d_slot : nullptr;
     const dim3 gr((unsigned)(c->B * c->N)), bl(SR_THREADS);
     if (p.fwd == SHT_FWD_PAIR) {
         // k_sht_fwd_pair: half the rows per pass, the table rows of a pass prefetched (one round trip per pass).  Measured at
@@ -689,14 +689,14 @@ template <int EPI, int R1, int R2>
 static void launch_inv_r(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
     const ShtPlan& p = c->sht;
     if (p.inv == SHT_INV_WIDE) {
-        const int* slw = (epi.out_slot >= 0 || EPI == EPI_REAL_UPDATE) ? c->d_slot : nullptr;
+        const int* slw = (epi.out_slot >= 0 || EPI == EPI_REAL_UPDATE) ? (const int*)c->d_slot : nullptr;
         hipLaunchKernelGGL((k_sht_inv_wide<EPI, R1, R2>), dim3((unsigned)(c->B * c->N * p.inv_nsplit)), dim3(SW_THREADS), p.inv_lds, c->stream,
                            coeff, grid, (const double*)c->d_P, (const int*)c->d_poff, (const double2*)c->d_AB,
                            (const double*)c->d_cost, c->npairs, (const double2*)c->d_twN, c->nt, c->L, p.inv_rp, c->N, epi.F, epi.shell_scale, slw, epi.out_slot, c->B, epi.coeff_sub, epi.real, p.inv_nsplit);
         return;
     }
     if constexpr (EPI != EPI_REAL_UPDATE) {            // the pass-wise kernel has no real-space epilogue
-        const int* sl = epi.out_slot >= 0 ? c->d_slot : nullptr;
+        const int* sl = epi.out_slot >= 0 ? (const int*)c->d_slot : nullptr;
         const dim3 gr((unsigned)(c->B * c->N)), bl(SR_THREADS);
         hipLaunchKernelGGL((k_sht_inv_reg<EPI, R1, R2>), gr, bl, p.inv_lds, c->stream, coeff, grid, (const double*)c->d_PT,
                            (const int*)c->d_poff, (const double2*)c->d_twN, c->nt, c->L, c->npairs, p.inv_rp, c->N, epi.F,

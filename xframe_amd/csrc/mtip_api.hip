@@ -29,11 +29,10 @@ static int post_launch(mtip_ctx* c, const char* what) {
 }
 
 template <typename T>
-static int dev_alloc(mtip_ctx* c, T** p, size_t n) {
-    hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
+static int dev_alloc(mtip_ctx* c, DevBuf<T>* p, size_t n) {
+    const hipError_t e = p->alloc(n);
     if (e != hipSuccess) {
         c->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        *p = nullptr;
         return MTIP_ENOMEM;
     }
     return MTIP_OK;
@@ -53,21 +52,12 @@ void mtip_destroy(mtip_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_invariant_metrics(c);
-    void* ptrs[] = {c->d_cost, c->d_gw, c->d_P, c->d_r, c->d_q, c->d_poff, c->d_PT, c->d_AB, c->d_lmtab, c->d_twN, c->d_tw, c->d_W, c->d_htiles32, c->d_kl, c->d_used, c->d_active, c->d_sweeps, c->d_jsched, c->d_jsched_off, c->d_jsched_rounds, c->d_jorder, c->d_pg_tiles[0], c->d_pg_tiles[1], c->d_pg_tiles[2], c->d_pg_tiles[3], c->d_pg_tiles[4], c->d_pg_tiles[5], c->d_voff,
-                    c->d_xoff, c->d_uoff, c->d_V, c->d_rmask, c->d_Bref, c->d_Bnorm, c->d_deg2_part, c->d_S0, c->d_sup, c->d_err_wr,
-                    c->d_err_wt, c->d_rho, c->d_Fp, c->d_slot, c->d_best_err, c->d_last_err, c->d_op_err, c->d_gq, c->d_polar_dbg, c->d_so3_d, c->d_so3_tw, c->d_so3_T, c->d_so3_S, c->d_so3_P, c->d_so3_D, c->d_so3_C, c->d_err_hist, c->d_main_hist,
-                    c->d_deg2_hist, c->d_F, c->d_T1, c->d_T2, c->d_fixed, c->d_g, c->d_c[0], c->d_c[1], c->d_c[2],
-                    c->d_c[3], c->d_c[4], c->d_c[5], c->d_X, c->d_Vr, c->d_U, c->d_partial, c->d_minmax, c->d_Bl,
-                    c->d_rp_DV, c->d_rp_Vt, c->d_rp_slots, c->d_c0n, c->d_mk, c->d_chain_dbg, c->d_PTc, c->d_lmc, c->d_ftmask};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : c->prof_events) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->turn_ev) (void)hipEventDestroy(c->turn_ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                            // the device buffers go with it: after the synchronisation above
 }
 
 static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
@@ -303,15 +293,11 @@ int mtip_set_projection_matrix(mtip_ctx* c, int l, const mtip_cdouble* V, int k_
     (void)hipSetDevice(c->device);
     if (c->d_jorder != nullptr) {                        // ... and so does the order list of the polar-factor kernel
         (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(c->d_jorder);
-        c->d_jorder = nullptr;
+        c->d_jorder.reset();
     }
     if (c->d_pg_tiles[0] != nullptr) {                   // the tile lists of the projection GEMMs depend on k_l / used
         (void)hipStreamSynchronize(c->stream);
-        for (int op = 0; op < 6; ++op) {
-            (void)hipFree(c->d_pg_tiles[op]);
-            c->d_pg_tiles[op] = nullptr;
-        }
+        for (int op = 0; op < 6; ++op) c->d_pg_tiles[op].reset();
     }
     // the storage slot has room for kmax columns; a narrower matrix is zero padded (zero columns of V
     // do not contribute to V_l U_l)
@@ -490,45 +476,32 @@ static int ensure_hist(mtip_ctx* c, long long need) {
     if (need <= c->err_cap) return MTIP_OK;
     long long cap = c->err_cap;
     while (cap < need) cap *= 2;
-    double *nh = nullptr, *nd = nullptr, *nm = nullptr;
-    int r = dev_alloc(c, &nh, (size_t)cap * c->B);
-    if (r) return r;
-    r = dev_alloc(c, &nd, (size_t)cap * c->B * (c->L + 1));
-    if (!r) r = dev_alloc(c, &nm, (size_t)cap * c->B);
-    if (r) {
-        (void)hipFree(nh);
-        if (nd) (void)hipFree(nd);
-        return r;
-    }
+    DevBuf<double> nh, nd, nm;
+    TRY(dev_alloc(c, &nh, (size_t)cap * c->B));
+    TRY(dev_alloc(c, &nd, (size_t)cap * c->B * (c->L + 1)));
+    TRY(dev_alloc(c, &nm, (size_t)cap * c->B));
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     MTIP_HIP_CHECK(c, hipMemcpyAsync(nh, c->d_err_hist, (size_t)c->n_steps_done * c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     MTIP_HIP_CHECK(c, hipMemcpyAsync(nm, c->d_main_hist, (size_t)c->n_steps_done * c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     MTIP_HIP_CHECK(c, hipMemcpyAsync(nd, c->d_deg2_hist, (size_t)c->n_steps_done * c->B * (c->L + 1) * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_main_hist);
-    c->d_main_hist = nm;
-    (void)hipFree(c->d_err_hist);
-    (void)hipFree(c->d_deg2_hist);
-    c->d_err_hist = nh;
-    c->d_deg2_hist = nd;
+    c->d_main_hist = std::move(nm);
+    c->d_err_hist = std::move(nh);
+    c->d_deg2_hist = std::move(nd);
     if (c->d_rl2_hist) {
-        double* ni = nullptr;
-        r = dev_alloc(c, &ni, (size_t)cap * c->B);
-        if (r) return r;
+        DevBuf<double> ni;
+        TRY(dev_alloc(c, &ni, (size_t)cap * c->B));
         MTIP_HIP_CHECK(c, hipMemcpyAsync(ni, c->d_rl2_hist, (size_t)c->n_steps_done * c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_rl2_hist);
-        c->d_rl2_hist = ni;
+        c->d_rl2_hist = std::move(ni);
     }
     if (c->d_im_hist) {
-        double* ni = nullptr;
+        DevBuf<double> ni;
         const size_t rowlen = (size_t)c->B * (2 + c->N);
-        r = dev_alloc(c, &ni, (size_t)cap * rowlen);
-        if (r) return r;
+        TRY(dev_alloc(c, &ni, (size_t)cap * rowlen));
         MTIP_HIP_CHECK(c, hipMemcpyAsync(ni, c->d_im_hist, (size_t)c->n_steps_done * rowlen * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_im_hist);
-        c->d_im_hist = ni;
+        c->d_im_hist = std::move(ni);
     }
     c->err_cap = cap;
     return MTIP_OK;
@@ -540,7 +513,7 @@ static int ensure_hist(mtip_ctx* c, long long need) {
 enum { STEP_HEAD = 1, STEP_PROJ = 2, STEP_TAIL = 4, STEP_ALL = 7 };
 static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int phases = STEP_ALL) {
     const bool fxs = (method == MTIP_HIO || method == MTIP_ER);
-    double2 **cc = c->d_c;
+    DevBuf<double2>* cc = c->d_c;
     InvEpilogue store;
     // Chained kernels (k_sht_chain.hip): in the fused step every inverse SHT hands its shell to the forward SHT that reads the
     // same grid next -- F -> SHT(|F|^2), F' -> SHT(F'), rho_new -> SHT(rho_new) of the NEXT step (kept in d_c0n, valid while
@@ -586,7 +559,7 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
     // per-restart ft_stab (mtip_set_ft_stab_mask: the reference decides the link to enforce_initial_support per reconstruction
     // process, reconstruct.py:836-850): the restarts without it neither subtract SHT(F) here nor add rho_prev back in the epilogue
     // (run_prelude has checked that such a mask meets the one-pass step)
-    const uint8_t* ftm = (ft_stab && c->ftmask_mixed) ? c->d_ftmask : nullptr;
+    const uint8_t* ftm = (ft_stab && c->ftmask_mixed) ? (const uint8_t*)c->d_ftmask : nullptr;
     if (one_pass_diff) {
         ProfScope ps(c, "hankel");
         launch_hankel_mfma_sub(c, cc[4], cc[1], cc[5], 1, ftm);
@@ -600,7 +573,7 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
             // this step is written once and nothing else of grid size moves
             InvEpilogue ru;
             ru.mode = EPI_REAL_UPDATE;
-            ru.coeff_sub = one_pass_diff ? nullptr : cc[0];
+            ru.coeff_sub = one_pass_diff ? nullptr : (const double2*)cc[0];
             ru.real.prev = c->d_rho;
             ru.real.out = c->d_rho;
             ru.real.sup = c->d_sup;
@@ -990,7 +963,7 @@ int mtip_shrinkwrap(mtip_ctx* c, double sigma, double threshold, double error_li
     TRY(ft_pipeline(c, c->d_rho, SL_CUR, c->d_T1, 0, MTIP_PRE_ABS, scale, c->d_c[0], c->d_c[1]));
     // IFT
     TRY(ft_pipeline(c, c->d_T1, -1, c->d_T2, 1, MTIP_PRE_NONE, store, c->d_c[0], c->d_c[1]));
-    double* tmp = reinterpret_cast<double*>(c->d_T1);
+    double* tmp = reinterpret_cast<double*>((double2*)c->d_T1);
     launch_sw_clamp(c, c->d_T2, tmp);
     launch_sw_threshold(c, tmp, threshold, error_limit);
     r = post_launch(c, "mtip_shrinkwrap");
@@ -1151,21 +1124,17 @@ int mtip_op_hankel_difference(mtip_ctx* c, const mtip_cdouble* in, const mtip_cd
     SYNC();
     H2D(c->d_c[0], in, (size_t)c->B * c->C * sizeof(double2));
     H2D(c->d_c[1], sub, (size_t)c->B * c->C * sizeof(double2));
-    uint8_t* d_mask = nullptr;                                  // a buffer of its own: d_ftmask belongs to the loop's next runs
+    DevBuf<uint8_t> d_mask;                                     // a buffer of its own: d_ftmask belongs to the loop's next runs
     if (sub_mask) {
-        if (hipMalloc((void**)&d_mask, (size_t)c->B) != hipSuccess) FAIL(c, MTIP_ENOMEM, "hipMalloc failed");
-        if (mtip_copy(c, d_mask, sub_mask, (size_t)c->B, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d_mask);
+        if (d_mask.alloc((size_t)c->B) != hipSuccess) FAIL(c, MTIP_ENOMEM, "hipMalloc failed");
+        if (mtip_copy(c, d_mask, sub_mask, (size_t)c->B, hipMemcpyHostToDevice) != hipSuccess)
             FAIL(c, MTIP_EHIP, "copy of the subtraction mask failed");
-        }
     }
     {
         ProfScope ps(c, "hankel");
         launch_hankel_mfma_sub(c, c->d_c[0], c->d_c[1], c->d_c[2], inverse ? 1 : 0, d_mask);
     }
-    const hipError_t sync = hipStreamSynchronize(c->stream);
-    if (d_mask) (void)hipFree(d_mask);
-    MTIP_HIP_CHECK(c, sync);
+    SYNC();
     D2H(out, c->d_c[2], (size_t)c->B * c->C * sizeof(double2));
     return post_launch(c, "mtip_op_hankel_difference");
 }
@@ -1276,27 +1245,19 @@ int mtip_op_apply_matrix(mtip_ctx* c, const double* matrix, const double* vects,
     CTX_CHECK(c);
     if (!matrix || !vects || !out || nr < 1 || nc < 1 || nv < 1) FAIL(c, MTIP_EINVAL, "bad apply_matrix arguments");
     (void)hipSetDevice(c->device);
-    double *dM = nullptr, *dx = nullptr, *dy = nullptr;
-    int r = dev_alloc(c, &dM, (size_t)nr * nc);
-    if (!r) r = dev_alloc(c, &dx, (size_t)nc * nv);
-    if (!r) r = dev_alloc(c, &dy, (size_t)nr * nv);
-    if (!r) {
-        hipError_t e = mtip_copy(c, dM, matrix, (size_t)nr * nc * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = mtip_copy(c, dx, vects, (size_t)nc * nv * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            launch_apply_matrix(c, dM, dx, dy, nr, nc, nv);
-            e = hipStreamSynchronize(c->stream);
-        }
-        if (e == hipSuccess) e = mtip_copy(c, out, dy, (size_t)nr * nv * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            c->err = std::string("apply_matrix: ") + hipGetErrorString(e);
-            r = MTIP_EHIP;
-        }
+    DevBuf<double> dM, dx, dy;
+    TRY(dev_alloc(c, &dM, (size_t)nr * nc));
+    TRY(dev_alloc(c, &dx, (size_t)nc * nv));
+    TRY(dev_alloc(c, &dy, (size_t)nr * nv));
+    hipError_t e = mtip_copy(c, dM, matrix, (size_t)nr * nc * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = mtip_copy(c, dx, vects, (size_t)nc * nv * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_apply_matrix(c, dM, dx, dy, nr, nc, nv);
+        e = hipStreamSynchronize(c->stream);
     }
-    if (dM) (void)hipFree(dM);
-    if (dx) (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
-    return r ? r : post_launch(c, "mtip_op_apply_matrix");
+    if (e == hipSuccess) e = mtip_copy(c, out, dy, (size_t)nr * nv * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) FAIL(c, MTIP_EHIP, std::string("apply_matrix: ") + hipGetErrorString(e));
+    return post_launch(c, "mtip_op_apply_matrix");
 }
 
 // ---- timing ---------------------------------------------------------------------------------------------

@@ -2,8 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <map>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/mtip_hip.h"
 
@@ -206,6 +209,44 @@ struct ShtPlan {
     size_t chain_lds = 0;
 };
 
+// ---- device memory ----------------------------------------------------------------------------------
+// Move-only owner of one device allocation.  It converts to the raw pointer, so kernel arguments, pointer arithmetic and
+// null tests read as they do with a plain pointer; what it does not allow is a second owner of the same block.
+template <typename T>
+struct DevBuf {
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            swap(o);
+        }
+        return *this;
+    }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    // releases what it held; at least one element, so that an empty table still has an address.  Null on failure.
+    hipError_t alloc(size_t count) {
+        reset();
+        const hipError_t e = hipMalloc((void**)&p_, std::max<size_t>(count, 1) * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    void swap(DevBuf& o) noexcept { std::swap(p_, o.p_); }
+    operator T*() const { return p_; }
+
+private:
+    T* p_ = nullptr;
+};
+static_assert(!std::is_copy_constructible_v<DevBuf<double>>);
+
+struct HankelTile32;                                  // k_hankel.hip
+
 struct mtip_ctx {
     mtip_cfg cfg{};
     int device = 0;
@@ -214,117 +255,115 @@ struct mtip_ctx {
     int N = 0, L = 0, nt = 0, np = 0, B = 0, nlm = 0, nm = 0, Np = 0;
     size_t G = 0, C = 0;
     // tables
-    double *d_cost = nullptr, *d_gw = nullptr, *d_P = nullptr, *d_r = nullptr, *d_q = nullptr;
-    int* d_poff = nullptr;
-    double2* d_AB = nullptr;                          // (npairs) three-term recurrence coefficients (a_lm, b_lm), (l,m)-major
-    double* d_PT = nullptr;                           // (nt/2, npairs) theta-major Legendre table (fused SHT)
-    double* d_PTc = nullptr;                          // (nt/2, 768) the same table in the chunk layout of k_sht_chain's Legendre sums
-    int* d_lmc = nullptr;                             // (768) l | m << 8 of slot u * 256 + t, -1: none
-    uint8_t* d_ftmask = nullptr;                      // (B) per-restart ft_stab of the next runs (mtip_set_ft_stab_mask)
+    DevBuf<double> d_cost, d_gw, d_P, d_r, d_q;
+    DevBuf<int> d_poff;
+    DevBuf<double2> d_AB;                          // (npairs) three-term recurrence coefficients (a_lm, b_lm), (l,m)-major
+    DevBuf<double> d_PT;                           // (nt/2, npairs) theta-major Legendre table (fused SHT)
+    DevBuf<double> d_PTc;                          // (nt/2, 768) the same table in the chunk layout of k_sht_chain's Legendre sums
+    DevBuf<int> d_lmc;                             // (768) l | m << 8 of slot u * 256 + t, -1: none
+    DevBuf<uint8_t> d_ftmask;                      // (B) per-restart ft_stab of the next runs (mtip_set_ft_stab_mask)
     bool ftmask_mixed = false;                        // the mask has both values: steps with ft_stab take it per restart
     hipEvent_t turn_ev = nullptr;                     // mtip_run_group_async: end of this context's latest transform block
     int chain_chunks = 0;                             // chunks (threads of an accumulation group with work) in that layout; 0: it does not fit 256
-    int* d_lmtab = nullptr;                           // (npairs) l | m << 8
+    DevBuf<int> d_lmtab;                           // (npairs) l | m << 8
     int npairs = 0;
     ShtPlan sht;                                      // SHT kernel choice (plan_sht, at mtip_set_angular_grid)
-    double2* d_twN = nullptr;                         // exp(-2 pi i j / n_phi), j < n_phi
-    double2* d_tw = nullptr;
-    double* d_W = nullptr;
+    DevBuf<double2> d_twN;                         // exp(-2 pi i j / n_phi), j < n_phi
+    DevBuf<double2> d_tw;
+    DevBuf<double> d_W;
     int n_cu = 256;                                   // compute units of the device (persistent-grid sizing)
     bool jac_resident = true;                         // env MTIP_JAC_RESIDENT=0: round-robin ordering, both columns via LDS
-    int *d_jsched = nullptr, *d_jsched_off = nullptr, *d_jsched_rounds = nullptr;   // resident-column pairing schedule
+    DevBuf<int> d_jsched, d_jsched_off, d_jsched_rounds;   // resident-column pairing schedule
     int jsched_kmax = 0, jsched_ps = 0;
     std::vector<int> jsched_nrd;                      // rounds of a sweep for every column count (host copy of d_jsched_rounds)
     double rp_early = 3e-2, rp_corr2_max = 1.5e-4;     // thresholds of the closing step (k_projr.hip RP_EARLY_CORR, RP_CORR2_MAX; env MTIP_RP_EARLY, MTIP_RP_CORR2_MAX)
     bool rp_corr = true;                              // k_rproj: close the Jacobi sweeps with the first-order polar step (MTIP_RP_CORR=0: classic)
     // non-default reciprocal metrics (k_metrics.hip): flags 1 II_error | 2 ccd_diff | 4 fqc_error, their constant tables, history rows
     uint32_t im_which = 0;
-    uint8_t* d_im_zmask = nullptr;
-    double2 *d_im_IIref = nullptr, *d_im_ccdref = nullptr;
-    double *d_rl2_wr = nullptr, *d_rl2_wt = nullptr, *d_rl2_part = nullptr, *d_rl2_hist = nullptr;   // reciprocal l2_projection_diff (k_metrics.hip)
-    double* d_im_fq = nullptr;                         // (B, Nq, Nq) fqc values of a step (k_metric_fqc -> k_metric_fqc_fold)
-    double2* d_im_part = nullptr;                      // (B, IM_BLOCKS, 4) partial sums of II_error / ccd_diff
-    double *d_im_qq = nullptr, *d_im_ccdT = nullptr, *d_im_P = nullptr, *d_im_refavg = nullptr, *d_im_refw = nullptr, *d_im_hist = nullptr;
+    DevBuf<uint8_t> d_im_zmask;
+    DevBuf<double2> d_im_IIref, d_im_ccdref;
+    DevBuf<double> d_rl2_wr, d_rl2_wt, d_rl2_part, d_rl2_hist;   // reciprocal l2_projection_diff (k_metrics.hip)
+    DevBuf<double> d_im_fq;                         // (B, Nq, Nq) fqc values of a step (k_metric_fqc -> k_metric_fqc_fold)
+    DevBuf<double2> d_im_part;                      // (B, IM_BLOCKS, 4) partial sums of II_error / ccd_diff
+    DevBuf<double> d_im_qq, d_im_ccdT, d_im_P, d_im_refavg, d_im_refw, d_im_hist;
     double im_ccd_inv_norm = 0.0;
     int so_order = -1;                                // SO_freedom: order whose unknown [4][2] is made real after every projection (-1: off)
     std::vector<int> jsched_off_h;                    // offsets of the per-column-count tables in d_jsched (host copy of d_jsched_off)
-    int* d_jorder = nullptr;                          // active orders, heaviest first (grid of the polar-factor kernel)
+    DevBuf<int> d_jorder;                          // active orders, heaviest first (grid of the polar-factor kernel)
     int n_jorder = 0;
-    int* d_pg_tiles[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // (order, tile) lists of the projection GEMMs (4, 5: fused pairs)
+    DevBuf<int> d_pg_tiles[6];   // (order, tile) lists of the projection GEMMs (4, 5: fused pairs)
     int n_pg_tiles[6] = {0, 0, 0, 0, 0, 0};
-    long long* d_polar_dbg = nullptr;                 // (B, L+1, MTIP_POLAR_DBG_SLOTS) phase / round timers of k_rproj, allocated by mtip_debug_polar_timing
+    DevBuf<long long> d_polar_dbg;                 // (B, L+1, MTIP_POLAR_DBG_SLOTS) phase / round timers of k_rproj, allocated by mtip_debug_polar_timing
     int jac_tg = 16;                                  // env MTIP_JAC_TG=8|16: lanes per Jacobi column pair
-    double2* d_c0n = nullptr;                         // (B, C) SHT of the current density, written by the chained last kernel of a step
-    long long* d_chain_dbg = nullptr;                 // (3 kinds, B * Nq, MTIP_CHAIN_DBG_SLOTS) phase stamps of k_sht_chain, allocated by mtip_debug_chain_timing
+    DevBuf<double2> d_c0n;                         // (B, C) SHT of the current density, written by the chained last kernel of a step
+    DevBuf<long long> d_chain_dbg;                 // (3 kinds, B * Nq, MTIP_CHAIN_DBG_SLOTS) phase stamps of k_sht_chain, allocated by mtip_debug_chain_timing
     bool c0n_valid = false;                           // d_c0n holds SHT(rho[SL_CUR]) of every restart
-    void* d_htiles32 = nullptr;                       // workgroup tiles (order, first column) of k_hankel_tile
+    DevBuf<HankelTile32> d_htiles32;                       // workgroup tiles (order, first column) of k_hankel_tile
     int htile_force = 0;                              // env MTIP_HANKEL_CT=1|2|3|5: tile width of k_hankel_tile instead of the occupancy rule (A/B)
     int n_htiles32 = 0, htile_ct = 5;                 // 16-column MFMA tiles per workgroup
     double fwd_scale = 0, inv_scale = 0;
     bool have_angular = false, have_radial = false, have_weights = false, have_support = false, have_errw = false;
     // projection data
     std::vector<int> kl, used, active, voff, xoff, uoff;     // host copies (active = used and V_l != 0)
-    int* d_active = nullptr;
-    int* d_sweeps = nullptr;                          // (B, L+1) Jacobi sweeps of the last projection (diagnostic)
+    DevBuf<int> d_active;
+    DevBuf<int> d_sweeps;                          // (B, L+1) Jacobi sweeps of the last projection (diagnostic)
     bool vr_valid = false;                            // d_Vr holds (complex) right singular vectors of the previous call
     int vr_kind = 0;                                  // 2: d_Vr holds the REAL right singular vectors of the previous k_rproj call
     bool proj_real = true;                            // env MTIP_PROJ_REAL=0: never take the real form of the projection (k_projr.hip)
     std::vector<char> v_real;                         // per order: V_l has no imaginary part
     std::vector<double2> h_V;                         // host copy of the concatenated V_l (tables of the real projection)
-    double *d_rp_DV = nullptr, *d_rp_Vt = nullptr;    // q^2 V_l (N x k) and V_l^T (k x N), real, at voff[l]
-    int* d_rp_slots = nullptr;                        // (rp_n_slots, rp_slot_len) order | kind << 8 lists of the k_rproj workgroups
+    DevBuf<double> d_rp_DV, d_rp_Vt;    // q^2 V_l (N x k) and V_l^T (k x N), real, at voff[l]
+    DevBuf<int> d_rp_slots;                        // (rp_n_slots, rp_slot_len) order | kind << 8 lists of the k_rproj workgroups
     int rp_n_slots = 0, rp_slot_len = 0;
     long long proj_calls = 0;
     double polar_abs_tol = 0.0;                       // 0 = purely relative Jacobi criterion (env MTIP_POLAR_ABS_TOL)
-    int *d_kl = nullptr, *d_used = nullptr, *d_voff = nullptr, *d_xoff = nullptr, *d_uoff = nullptr;
+    DevBuf<int> d_kl, d_used, d_voff, d_xoff, d_uoff;
     int vtot = 0, xtot = 0, utot = 0;                 // per-restart element counts
-    double2* d_V = nullptr;                           // concatenated V_l, (Nq, k_l) row-major each
-    uint8_t* d_rmask = nullptr;                       // (L+1, Nq)
+    DevBuf<double2> d_V;                           // concatenated V_l, (Nq, k_l) row-major each
+    DevBuf<uint8_t> d_rmask;                       // (L+1, Nq)
     std::vector<char> have_V;
     double n_particles = 1.0;
     // deg2 metric
     int deg2_enable = 0;
-    double2* d_Bref = nullptr;                        // (L+1, Nq, Nq) masked reference B_l
-    double* d_Bnorm = nullptr;                        // (L+1)
-    double* d_deg2_part = nullptr;                    // (B, L+1, (Nq/16)^2) per-tile partial sums of the B_l metric
+    DevBuf<double2> d_Bref;                        // (L+1, Nq, Nq) masked reference B_l
+    DevBuf<double> d_Bnorm;                        // (L+1)
+    DevBuf<double> d_deg2_part;                    // (B, L+1, (Nq/16)^2) per-tile partial sums of the B_l metric
     bool proj_fuse = true;                            // env MTIP_PROJ_FUSE=0: four separate projection products instead of the two fused pairs
     bool deg2_simple = false;                         // env MTIP_DEG2_SIMPLE=1: one thread per B_l element instead of MFMA tiles
     bool bref_dirty = true;
     // real-space constraints and error metric
     RealParams rp{RC_SUPPORT | RC_VALUE_LO, RC_SUPPORT | RC_VALUE_LO, 0.0, 0.0, 0.0};
-    uint8_t *d_S0 = nullptr, *d_sup = nullptr;        // (G), (3, B, G)
-    uint16_t* d_mk = nullptr;                         // (3, B, Nq, nt, R2) the same masks packed for k_sht_chain: bit n1 = support, bit 8 + n1 = S0 of point R2 n1 + n2 of the row
-    double *d_err_wr = nullptr, *d_err_wt = nullptr;
+    DevBuf<uint8_t> d_S0, d_sup;        // (G), (3, B, G)
+    DevBuf<uint16_t> d_mk;                         // (3, B, Nq, nt, R2) the same masks packed for k_sht_chain: bit n1 = support, bit 8 + n1 = S0 of point R2 n1 + n2 of the row
+    DevBuf<double> d_err_wr, d_err_wt;
     int err_use_mask = 1;
     // state
-    double2 *d_rho = nullptr, *d_Fp = nullptr;        // (3, B, G) each
-    int* d_slot = nullptr;                            // (B, SL_N)
-    double *d_best_err = nullptr, *d_last_err = nullptr;   // (B)
-    double* d_op_err = nullptr;                       // (B) error of the single-operator entry point (never the loop's)
-    double* d_gq = nullptr;                           // (Nq) shrink-wrap Gaussian G_sigma(q)
-    double* d_err_hist = nullptr;                     // (cap, B) real l2 metric per step
-    double* d_main_hist = nullptr;                    // (cap, B) main error per step when it is not the real metric (main_mode 1)
+    DevBuf<double2> d_rho, d_Fp;        // (3, B, G) each
+    DevBuf<int> d_slot;                            // (B, SL_N)
+    DevBuf<double> d_best_err, d_last_err;   // (B)
+    DevBuf<double> d_op_err;                       // (B) error of the single-operator entry point (never the loop's)
+    DevBuf<double> d_gq;                           // (Nq) shrink-wrap Gaussian G_sigma(q)
+    DevBuf<double> d_err_hist;                     // (cap, B) real l2 metric per step
+    DevBuf<double> d_main_hist;                    // (cap, B) main error per step when it is not the real metric (main_mode 1)
     int main_mode = 0, main_type = 0;                 // mtip_set_main_error
-    double* d_deg2_hist = nullptr;                    // (cap, B, L+1)
+    DevBuf<double> d_deg2_hist;                    // (cap, B, L+1)
     long long err_cap = 0, n_steps_done = 0;
     bool state_ready = false, fixed_valid = false;
     // work buffers
-    double2 *d_F = nullptr, *d_T1 = nullptr, *d_T2 = nullptr;   // grids (B, G)
-    double* d_fixed = nullptr;                        // real grid (B, G)
-    double2* d_g = nullptr;                           // (B, Nq, nt, 2L+1)
-    double2* d_c[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // coefficient arrays (B, C)
-    double2 *d_X = nullptr, *d_Vr = nullptr, *d_U = nullptr;   // projection workspaces
-    double* d_partial = nullptr;                      // (B, nblk, 2) error partial sums
+    DevBuf<double2> d_F, d_T1, d_T2;   // grids (B, G)
+    DevBuf<double> d_fixed;                        // real grid (B, G)
+    DevBuf<double2> d_g;                           // (B, Nq, nt, 2L+1)
+    DevBuf<double2> d_c[6];   // coefficient arrays (B, C)
+    DevBuf<double2> d_X, d_Vr, d_U;   // projection workspaces
+    DevBuf<double> d_partial;                      // (B, nblk, 2) error partial sums
     int n_partial_blocks = 0;
-    double* d_minmax = nullptr;                       // (B, nblk, 2)
-    double2* d_Bl = nullptr;                          // (B, L+1, Nq, Nq) scratch (lazy)
+    DevBuf<double> d_minmax;                       // (B, nblk, 2)
+    DevBuf<double2> d_Bl;                          // (B, L+1, Nq, Nq) scratch (lazy)
     // rotational alignment (k_align.hip): Wigner table d^l_mn(beta_b), DFT twiddles, work arrays
-    double* d_so3_d = nullptr;
-    double2 *d_so3_tw = nullptr, *d_so3_T = nullptr, *d_so3_S = nullptr, *d_so3_P = nullptr, *d_so3_D = nullptr;
-    double* d_so3_C = nullptr;
+    DevBuf<double> d_so3_d;
+    DevBuf<double2> d_so3_tw, d_so3_T, d_so3_S, d_so3_P, d_so3_D;
+    DevBuf<double> d_so3_C;
     int so3_bw = 0;
-    // host staging
-    void* h_stage = nullptr;
     // profiling
     int prof = 0;
     std::map<std::string, ProfEntry> prof_data;
@@ -368,7 +407,6 @@ int jacobi_groups(int k);                            // pair-groups a round of t
 int build_hankel_tiles(mtip_ctx* c);
 int hankel_row_blocks(const mtip_ctx* c);            // row blocks (128 output shells each) of k_hankel_tile: the grid's y extent
 int launch_invariant_metrics(mtip_ctx* c, const double2* Ilm, long long step);
-void free_invariant_metrics(mtip_ctx* c);
 int launch_reciprocal_l2_metric(mtip_ctx* c, const double2* F, const double2* Fp, long long step);
 void launch_deg2(mtip_ctx* c, const double2* Ilm, double2* Bl);
 void launch_coeff_diff(mtip_ctx* c, const double2* a, const double2* b, double2* out);
@@ -443,12 +481,31 @@ struct ProfScope {
 // The caller's side of a copy (`kind` names the direction the ABI documents) may itself be device memory -- the averaging keeps
 // its batch in HBM between operator calls -- so the direction is left to the runtime (unified addressing); a device-to-device
 // hipMemcpy is ordered on the null stream, which this context's stream does not wait for: wait for it here.
-static inline hipError_t mtip_copy(mtip_ctx* c, void* dst, const void* src, size_t n, hipMemcpyKind kind) {
-    (void)kind;
-    hipError_t e = hipStreamSynchronize(c->stream);
+static inline hipError_t mtip_copy(hipStream_t stream, void* dst, const void* src, size_t n) {
+    hipError_t e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
     e = hipMemcpy(dst, src, n, hipMemcpyDefault);
     return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+static inline hipError_t mtip_copy(mtip_ctx* c, void* dst, const void* src, size_t n, hipMemcpyKind kind) {
+    (void)kind;
+    return mtip_copy(c->stream, dst, src, n);
+}
+
+static inline bool mtip_is_device_pointer(const void* p) {
+    hipPointerAttribute_t at;
+    const bool is_dev = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();                        // (an unregistered host pointer sets the sticky error on some runtimes)
+    return is_dev;
+}
+
+// free device memory in bytes (handles that size their work arrays to what is left)
+static inline size_t mtip_free_memory() {
+#ifdef __HIPCC__
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess) return fr;
+#endif
+    return (size_t)8 << 30;            // (the CPU build of the tests: a fixed budget)
 }
 
 // a caller's array as device memory: itself when it is device memory, else a temporary that is filled / copied back
@@ -457,28 +514,23 @@ struct DevView {
     void* dev = nullptr;
     void* host = nullptr;
     size_t bytes = 0;
-    bool temp = false, writeback = false;
+    bool writeback = false;
     hipError_t err = hipSuccess;
+    DevBuf<char> temp;
     DevView(mtip_ctx* c_, const void* p, size_t n, bool read, bool write) : c(c_), bytes(n), writeback(write) {
         if (p == nullptr || n == 0) return;
-        hipPointerAttribute_t at;
-        const bool is_dev = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
-        (void)hipGetLastError();                    // (an unregistered host pointer sets the sticky error on some runtimes)
-        if (is_dev) {
+        if (mtip_is_device_pointer(p)) {
             dev = const_cast<void*>(p);
             return;
         }
-        temp = true;
         host = const_cast<void*>(p);
-        err = hipMalloc(&dev, n);
+        err = temp.alloc(n);
+        dev = temp;
         if (err == hipSuccess && read) err = mtip_copy(c, dev, p, n, hipMemcpyHostToDevice);
     }
     hipError_t finish() {                           // after the stream has been synchronised
         if (temp && writeback && err == hipSuccess) err = mtip_copy(c, host, dev, bytes, hipMemcpyDeviceToHost);
         return err;
-    }
-    ~DevView() {
-        if (temp && dev) (void)hipFree(dev);
     }
 };
 
