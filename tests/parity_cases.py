@@ -930,6 +930,126 @@ def check_projection_real_vs_oracle(N, L, lib_path=None, n_batch=2, seed=1, reci
     return sw
 
 
+def _projection_plan_problem(lib_path, n_batch, N=16, L=4):
+    """engine, the oracle's reciprocal projection and the SHT of the 16 shells x L4 problem of check_projection_real_vs_oracle: real
+    V_l, odd orders zero, so orders 2 and 4 are solved and the largest k_l is 9"""
+    sht = SHT(L)
+    data, _ = S.make_invariants(OracleTransforms(FourierPair(sht, N, S.data_cutoff(N), 2.0)), N, L)
+    assert all(np.all(np.asarray(p).imag == 0) for p in data['data_projection_matrices'])
+    opt = golden_settings(N, L)
+    e = Engine(opt, data, n_batch=n_batch, lib_path=lib_path)
+    return e, OM.MTIP(opt, data).rp, sht
+
+
+def _real_intensity_coefficients(rng, sht, n_batch, N):
+    grid = rng.uniform(0.0, 1.0, (n_batch, N, sht.n_theta, sht.n_phi)) * rng.uniform(0.5, 2.0, (n_batch, N, 1, 1))
+    return np.stack([np.concatenate(sht.forward_l(g.astype(complex)), axis=1) for g in grid])
+
+
+def _oracle_variant(rp, phase=None, drop_last=False):
+    """the oracle's projection with V_l of order phase[0] multiplied by exp(i phase[1]), or without its last used order"""
+    rp = copy.copy(rp)
+    pm = [np.array(m) for m in rp.projection_matrices]
+    if phase is not None:
+        pm[phase[0]] = pm[phase[0]] * np.exp(1j * phase[1])
+    rp.projection_matrices = pm
+    if drop_last:
+        rp.used_orders = dict(list(rp.used_orders.items())[:-1])
+    D2 = np.diag(rp.radial_points) ** 2
+    rp.PDs = tuple(pm[i].T.conj() @ D2 for i in rp.used_orders.values())
+    return rp
+
+
+def _oracle_projection(rp, Ilm, L):
+    out = []
+    for I in Ilm:
+        Il = [I[:, l * l:(l + 1) ** 2] for l in range(L + 1)]
+        out.append(np.concatenate(rp.mtip_projection(Il, rp.approximate_unknowns(Il)), axis=1))
+    return np.stack(out)
+
+
+def _assert_projection(proj, ref, L, tag):
+    """whole array and per order, as check_projection_real_vs_oracle"""
+    for b in range(len(ref)):
+        assert rel_l2(proj[b], ref[b]) < TOL_SHT, (tag, b, rel_l2(proj[b], ref[b]))
+        for l in range(L + 1):
+            sl = slice(l * l, (l + 1) ** 2)
+            assert rel_l2(proj[b][:, sl], ref[b][:, sl]) < TOL_SHT, (tag, b, l, rel_l2(proj[b][:, sl], ref[b][:, sl]))
+
+
+def _set_projection_order(e, l, V=None):
+    """mtip_set_projection_matrix for one order: the matrix V with the engine's radial mask, or (V is None) the order unused"""
+    from xframe_amd.fxs import _lib
+    if V is None:
+        e._ck(e.lib.mtip_set_projection_matrix(e.ctx, l, None, 1, None, 0))
+        return
+    V, mask = _lib.as_c128(V), _lib.as_u8(e.rsetup.radial_mask[l])
+    e._ck(e.lib.mtip_set_projection_matrix(e.ctx, l, _lib.ptr(V), V.shape[1], _lib.ptr(mask), 1))
+
+
+def check_projection_replans_on_new_matrices(lib_path=None, n_batch=2, N=16, L=4):
+    """The projection's plan (route, geometry, tables of V_l) follows mtip_set_projection_matrix: real V_l take the real kernel; one
+    order times exp(0.3 i) -- the same projector, a complex V_l -- takes the general kernels; the real matrix set back takes the real
+    kernel again; an order marked unused is left as it came in (tile, order and slot lists rebuilt).  Each against the oracle built
+    from the matrices then in force."""
+    e, rp, sht = _projection_plan_problem(lib_path, n_batch, N, L)
+    Ilm = _real_intensity_coefficients(np.random.default_rng(5), sht, n_batch, N)
+    ref = _oracle_projection(rp, Ilm, L)
+    l_c, V_real = 2, np.array(e.rsetup.projection_matrices[2])
+    assert np.abs(V_real).max() > 0 and rp.used_orders[L] == L
+    _assert_projection(e.project_coefficients(Ilm, real_intensity=True), ref, L, 'real V_l')
+    assert e.projection_slots() > 0
+    _set_projection_order(e, l_c, V_real * np.exp(0.3j))
+    ref_c = _oracle_projection(_oracle_variant(rp, phase=(l_c, 0.3)), Ilm, L)
+    _assert_projection(e.project_coefficients(Ilm, real_intensity=True), ref_c, L, 'complex V_l')
+    assert e.projection_slots() == 0
+    _set_projection_order(e, l_c, V_real)
+    _assert_projection(e.project_coefficients(Ilm, real_intensity=True), ref, L, 'real V_l again')
+    assert e.projection_slots() > 0
+    _set_projection_order(e, L, None)
+    ref_d = _oracle_projection(_oracle_variant(rp, drop_last=True), Ilm, L)
+    assert np.array_equal(ref_d[:, :, L * L:], Ilm[:, :, L * L:]) and rel_l2(ref_d, ref) > 1e-3
+    for real_intensity in (True, False):
+        _assert_projection(e.project_coefficients(Ilm, real_intensity=real_intensity), ref_d, L, ('order unused', real_intensity))
+        assert (e.projection_slots() > 0) == real_intensity
+    e.close()
+
+
+def check_projection_routes_alternate(lib_path=None, n_batch=2, N=16, L=4):
+    """real_intensity True, False, True, False on four inputs of one context: every result against the oracle, and the real kernel's
+    workgroups reported after its calls only -- neither route warm-starts from the V_r the other one left in d_Vr"""
+    e, rp, sht = _projection_plan_problem(lib_path, n_batch, N, L)
+    rng = np.random.default_rng(6)
+    for call in range(4):
+        real_intensity = call % 2 == 0
+        Ilm = _real_intensity_coefficients(rng, sht, n_batch, N)
+        proj = e.project_coefficients(Ilm, real_intensity=real_intensity)
+        assert (e.projection_slots() > 0) == real_intensity, (call, e.projection_slots())
+        _assert_projection(proj, _oracle_projection(rp, Ilm, L), L, call)
+    e.close()
+
+
+def check_projection_schedule_growth(lib_path=None, expect_real=True, n_batch=2, N=16, L=4):
+    """The pairing schedule grows (mtip_debug_check_jacobi_schedule: 40 columns, rows of 20 pair-groups instead of 4) between two
+    projections of the same input: the launch geometry, which depends on the schedule's row length, must follow it.  expect_real:
+    the real kernel runs (False under MTIP_PROJ_REAL=0, set by the caller before the engine is made: the general kernels)."""
+    e, rp, sht = _projection_plan_problem(lib_path, n_batch, N, L)
+    assert max(e.rsetup.projection_matrices[l].shape[1] for l in rp.used_orders.values()) == 9
+    Ilm = _real_intensity_coefficients(np.random.default_rng(7), sht, n_batch, N)
+    ref = _oracle_projection(rp, Ilm, L)
+    first = e.project_coefficients(Ilm, real_intensity=True)
+    e.jacobi_sweeps()                                       # (raises if an order's LDS layout did not fit its launch)
+    assert (e.projection_slots() > 0) == expect_real
+    _assert_projection(first, ref, L, 'before')
+    e._ck(e.lib.mtip_debug_check_jacobi_schedule(e.ctx, 40))
+    second = e.project_coefficients(Ilm, real_intensity=True)
+    e.jacobi_sweeps()
+    assert (e.projection_slots() > 0) == expect_real
+    _assert_projection(second, ref, L, 'after')
+    _assert_projection(second, first, L, 'after against before')
+    e.close()
+
+
 def check_config_trajectory_vs_oracle(cfg, lib_path=None, fused=True, n_hio=10, n_er=10):
     """BASELINE config sizes the oracle still walks in seconds (config 2: 64 x L16): n_hio HIO + SW + n_er ER ft_stab
     steps of the product worker against the oracle's phasing loop on the same synthetic invariants and the same seeded

@@ -281,6 +281,24 @@ def test_projection_real_switches(emul_lib, env, closing, monkeypatch):
     PC.check_projection_real_vs_oracle(24, 10, emul_lib, n_batch=1, closing=closing)
 
 
+def test_projection_replans_on_new_matrices(emul_lib):
+    """mtip_set_projection_matrix drops the projection's plan: route, tile, order and slot lists follow the new V_l and used flags"""
+    PC.check_projection_replans_on_new_matrices(emul_lib, n_batch=2)
+
+
+def test_projection_routes_alternate(emul_lib):
+    """the real and the general kernels in turn on one context: neither warm-starts from the other's V_r"""
+    PC.check_projection_routes_alternate(emul_lib, n_batch=2)
+
+
+@pytest.mark.parametrize('proj_real', [True, False])
+def test_projection_schedule_growth(emul_lib, proj_real, monkeypatch):
+    """a larger pairing schedule under a planned projection: the geometry of k_rproj and of the complex Jacobi kernel follows it"""
+    if not proj_real:
+        monkeypatch.setenv('MTIP_PROJ_REAL', '0')
+    PC.check_projection_schedule_growth(emul_lib, expect_real=proj_real, n_batch=2)
+
+
 def test_prtf_golden(emul_lib):
     PC.check_prtf_golden(emul_lib)
 

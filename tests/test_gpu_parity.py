@@ -143,8 +143,26 @@ def test_projection_real_switches(N, L, env, closing, monkeypatch):
 
 def test_projection_order_49_takes_the_general_kernels():
     """l = 49 (99 columns) needs 832 threads in the real kernel's pairing -- beyond its 768-thread instantiation: the launcher must
-    refuse it (rproj_supported) and the general kernels run; odd orders active"""
+    refuse it (plan_rproj) and the general kernels run; odd orders active"""
     PC.check_projection_real_vs_oracle(100, 49, n_batch=1, reciprocal_opt={'odd_orders_to_0': False}, expect_real=False)
+
+
+def test_projection_replans_on_new_matrices():
+    """mtip_set_projection_matrix drops the projection's plan: route, tile, order and slot lists follow the new V_l and used flags"""
+    PC.check_projection_replans_on_new_matrices()
+
+
+def test_projection_routes_alternate():
+    """k_rproj and the general kernels in turn on one context: neither warm-starts from the other's V_r"""
+    PC.check_projection_routes_alternate()
+
+
+@pytest.mark.parametrize('proj_real', [True, False])
+def test_projection_schedule_growth(proj_real, monkeypatch):
+    """a larger pairing schedule under a planned projection: the geometry of k_rproj and of k_polar_jacobi_lds follows it"""
+    if not proj_real:
+        monkeypatch.setenv('MTIP_PROJ_REAL', '0')
+    PC.check_projection_schedule_growth(expect_real=proj_real)
 
 
 def test_prtf_golden():

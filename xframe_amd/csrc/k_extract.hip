@@ -455,7 +455,7 @@ template <int NR>
 static void launch_sym_eig_block(mtip_ctx* c, double* dW, int n, const int2* d_pairs, int n_pairs, int n_mat, int* d_flags) {
     const size_t lds = (size_t)2 * SB_BW * (NR * 16 + 1) * sizeof(double);
     hipLaunchKernelGGL((k_sym_eig_block<NR>), dim3((unsigned)(n_mat * n_pairs)), dim3(SB_BW * 16), lds, c->stream, dW, n, d_pairs, n_pairs,
-                       (const int*)(c->d_jsched) + c->jsched_off_h[2 * SB_BW], c->jsched_nrd[2 * SB_BW], c->jsched_ps, d_flags);
+                       (const int*)(c->js.d_tab) + c->js.off[2 * SB_BW], c->js.nrd[2 * SB_BW], c->js.ps, d_flags);
 }
 
 // n in (128, 288]: blocked solve; dA, dU, dl device buffers as in mtip_op_symmetric_eig.  Returns the outer sweeps done (< 0: error).
@@ -554,7 +554,7 @@ extern "C" int mtip_op_symmetric_eig(mtip_ctx* c, int n, int n_mat, const double
         const size_t lds = ((size_t)n * (n | 1) + 128) * sizeof(double);
         ProfScope ps(c, "sym_eig");
         hipLaunchKernelGGL(k_sym_eig, dim3((unsigned)n_mat), dim3((unsigned)threads), lds, c->stream, (const double*)dA, dU, dl, n,
-                           (const int*)c->d_jsched, (const int*)c->d_jsched_off, (const int*)c->d_jsched_rounds, c->jsched_ps,
+                           (const int*)c->js.d_tab, (const int*)c->js.d_off, (const int*)c->js.d_rounds, c->js.ps,
                            n_mat <= c->B * (c->L + 1) ? c->d_sweeps : (int*)nullptr);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

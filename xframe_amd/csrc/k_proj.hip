@@ -8,6 +8,7 @@
 // The polar factor is computed with a one-sided (Hestenes) Jacobi SVD on X_l = A_l^+ (n_l x k_l,
 // k_l <= n_l, stored column-major so that column operations are contiguous):
 //   X V_r = W (orthogonal columns), sigma_c = |W_c|,  polar(X) = W Sigma^-1 V_r^+,  U_l = polar(X)^+.
+// Kernels (the real form of k_projr.hip or the complex ones here) and geometry: once per set of V_l, plan_projection below.
 #include "mtip_internal.h"
 #include "k_jacobi.h"
 
@@ -940,11 +941,20 @@ __global__ void __launch_bounds__(PF_THREADS) k_proj_ua(ProjGemmArgs a, double2*
     }
 }
 
-// tile lists of the four products (order | tile_m << 8 | tile_n << 16), heavy orders first
-static int build_proj_tiles(mtip_ctx* c) {
-    if (c->d_pg_tiles[0] != nullptr) return MTIP_OK;
+// The complex route's tables, on its first call after an invalidation: the tile lists of the four products (order | tile_m << 8 |
+// tile_n << 16), heavy orders first, and (order_list: the polar factors in LDS) the active orders, largest k_l (2l+1) first
+static int build_proj_tables(mtip_ctx* c, bool order_list) {
+    ProjPlan& pp = c->pp;
+    auto upload = [&](DevBuf<int>& d, std::vector<int>& t) {
+        if (t.empty()) t.push_back(0);
+        const bool ok = d.alloc(t.size()) == hipSuccess;
+        if (ok) (void)mtip_copy(c, d, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
+        else c->err = "projection tile and order lists: out of device memory";
+        return ok;
+    };
+    const bool tiles = pp.d_pg_tiles[0] == nullptr;
     const int tm_edge = 16, tn_edge = 64;                        // 16 x (4 x 16) outputs per workgroup
-    for (int op = 0; op < 4; ++op) {
+    for (int op = 0; tiles && op < 4; ++op) {
         std::vector<int> t;
         for (int l = c->L; l >= 0; --l) {
             const int k = c->kl[l], n = 2 * l + 1;
@@ -957,30 +967,34 @@ static int build_proj_tiles(mtip_ctx* c) {
             for (int tm = 0; tm < div_up(M, tm_edge); ++tm)
                 for (int tn = 0; tn < div_up(Nn, tn_edge); ++tn) t.push_back(l | (tm << 8) | (tn << 16));
         }
-        if (t.empty()) t.push_back(0);
-        c->n_pg_tiles[op] = (int)t.size();
-        if (c->d_pg_tiles[op].alloc(t.size()) != hipSuccess) return MTIP_ENOMEM;
-        (void)mtip_copy(c, c->d_pg_tiles[op], t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
+        pp.n_pg_tiles[op] = std::max((int)t.size(), 1);
+        if (!upload(pp.d_pg_tiles[op], t)) return MTIP_ENOMEM;
     }
     // the fused pairs: 4 = k_proj_xw (order | row tile << 8, active orders), 5 = k_proj_ua (order | column tile << 8, used orders)
-    for (int op = 4; op < 6; ++op) {
+    for (int op = 4; tiles && op < 6; ++op) {
         std::vector<int> t;
         for (int l = c->L; l >= 0; --l) {
             if (op == 4 ? !c->active[l] : !(c->used[l] || c->active[l])) continue;
             for (int tt = 0; tt < div_up(2 * l + 1, 16); ++tt) t.push_back(l | (tt << 8));
         }
-        c->n_pg_tiles[op] = (int)t.size();
-        if (t.empty()) t.push_back(0);
-        if (c->d_pg_tiles[op].alloc(t.size()) != hipSuccess) return MTIP_ENOMEM;
-        (void)mtip_copy(c, c->d_pg_tiles[op], t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
+        pp.n_pg_tiles[op] = (int)t.size();
+        if (!upload(pp.d_pg_tiles[op], t)) return MTIP_ENOMEM;
+    }
+    if (order_list && pp.d_jorder == nullptr) {
+        std::vector<int> ord;
+        for (int l = 0; l <= c->L; ++l)
+            if (c->active[l]) ord.push_back(l);
+        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return c->kl[x] * (2 * x + 1) > c->kl[y] * (2 * y + 1); });
+        pp.n_jorder = (int)ord.size();
+        if (!upload(pp.d_jorder, ord)) return MTIP_ENOMEM;
     }
     return MTIP_OK;
 }
 
 template <int OP>
 static void launch_proj_gemm(mtip_ctx* c, const ProjGemmArgs& a) {
-    hipLaunchKernelGGL(k_proj_mfma<OP>, dim3((unsigned)c->n_pg_tiles[OP], (unsigned)c->B), dim3(256), 0, c->stream, a,
-                       (const int*)c->d_pg_tiles[OP]);
+    hipLaunchKernelGGL(k_proj_mfma<OP>, dim3((unsigned)c->pp.n_pg_tiles[OP], (unsigned)c->B), dim3(256), 0, c->stream, a,
+                       (const int*)c->pp.d_pg_tiles[OP]);
 }
 
 // Divide-and-conquer pairing schedule for every column count 2..kmax (see jl_sweep_resident).  Entry
@@ -1008,7 +1022,9 @@ static void js_build(const std::vector<int>& cols, int g0, int round0, int ps, s
 }
 
 int build_jacobi_schedule(mtip_ctx* c, int kmax) {
-    if (c->d_jsched != nullptr && c->jsched_kmax >= kmax) return MTIP_OK;
+    JacobiSchedule& js = c->js;
+    if (js.d_tab != nullptr && js.kmax >= kmax) return MTIP_OK;
+    c->pp.planned = false;                                       // the projection's geometry depends on ps and nrd (ProjPlan)
     int ps = 1;
     for (int ke = 2; ke <= kmax; ++ke) ps = std::max(ps, js_groups(ke));
     std::vector<int> all, off(kmax + 1, 0), nrd(kmax + 1, 0);
@@ -1063,16 +1079,16 @@ int build_jacobi_schedule(mtip_ctx* c, int kmax) {
         for (auto& rd : rounds) all.insert(all.end(), rd.begin(), rd.end());
     }
     if (all.empty()) all.push_back(0);
-    if (c->d_jsched.alloc(all.size()) != hipSuccess) return MTIP_ENOMEM;
-    if (c->d_jsched_off.alloc(off.size()) != hipSuccess) return MTIP_ENOMEM;
-    if (c->d_jsched_rounds.alloc(nrd.size()) != hipSuccess) return MTIP_ENOMEM;
-    (void)mtip_copy(c, c->d_jsched, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice);
-    (void)mtip_copy(c, c->d_jsched_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice);
-    (void)mtip_copy(c, c->d_jsched_rounds, nrd.data(), nrd.size() * sizeof(int), hipMemcpyHostToDevice);
-    c->jsched_kmax = kmax;
-    c->jsched_ps = ps;
-    c->jsched_nrd = nrd;                                         // host copy: rounds per sweep by column count
-    c->jsched_off_h = off;
+    if (js.d_tab.alloc(all.size()) != hipSuccess) return MTIP_ENOMEM;
+    if (js.d_off.alloc(off.size()) != hipSuccess) return MTIP_ENOMEM;
+    if (js.d_rounds.alloc(nrd.size()) != hipSuccess) return MTIP_ENOMEM;
+    (void)mtip_copy(c, js.d_tab, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice);
+    (void)mtip_copy(c, js.d_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice);
+    (void)mtip_copy(c, js.d_rounds, nrd.data(), nrd.size() * sizeof(int), hipMemcpyHostToDevice);
+    js.kmax = kmax;
+    js.ps = ps;
+    js.nrd = nrd;
+    js.off = off;
     return MTIP_OK;
 }
 
@@ -1088,10 +1104,7 @@ static void fill_gemm_args(mtip_ctx* c, ProjGemmArgs& ga, const double2* Ilm) {
 int launch_apply_unknowns(mtip_ctx* c, const double2* Ilm, double2* out) {
     ProjGemmArgs ga;
     fill_gemm_args(c, ga, Ilm);
-    if (build_proj_tiles(c) != MTIP_OK) {
-        c->err = "projection tile lists: out of device memory";
-        return MTIP_ENOMEM;
-    }
+    if (int rc = build_proj_tables(c, false)) return rc;
     if (out != Ilm)
         (void)hipMemcpyAsync(out, Ilm, (size_t)c->B * c->C * sizeof(double2), hipMemcpyDeviceToDevice, c->stream);
     ga.dst = out;
@@ -1099,12 +1112,46 @@ int launch_apply_unknowns(mtip_ctx* c, const double2* Ilm, double2* out) {
     return MTIP_OK;
 }
 
-// largest k_l over the orders the apply product touches (LDS of k_proj_ua)
-static int kmax_used(const mtip_ctx* c) {
-    int k = 1;
-    for (int l = 0; l <= c->L; ++l)
-        if (c->used[l] || c->active[l]) k = std::max(k, c->kl[l]);
-    return k;
+// Decides c->pp (ProjPlan, mtip_internal.h) from V_l, k_l, used, active, the switches and the pairing schedule
+void plan_projection(mtip_ctx* c) {
+    ProjPlan& pp = c->pp;
+    if (pp.planned) return;
+    pp.kmax = pp.nmax = pp.kmax_used = 1;
+    for (int l = 0; l <= c->L; ++l) {
+        if (c->used[l] || c->active[l]) pp.kmax_used = std::max(pp.kmax_used, c->kl[l]);
+        if (!c->active[l]) continue;
+        pp.kmax = std::max(pp.kmax, c->kl[l]);
+        pp.nmax = std::max(pp.nmax, 2 * l + 1);
+    }
+    const int kmax = pp.kmax, nmax = pp.nmax;
+    // fused pairs (k_proj_xw, k_proj_ua) when X_l fits the 8 waves of k_proj_xw
+    pp.fuse = c->psw.fuse && kmax <= 16 * (PF_THREADS / 64);
+    pp.xw_lds = (size_t)16 * (kmax | 1) * sizeof(double2);
+    pp.ua_lds = (size_t)pp.kmax_used * 17 * sizeof(double2);
+    const size_t lds = ((size_t)kmax * (nmax | 1) + (size_t)kmax * (kmax | 1)) * sizeof(double2);   // unpadded minimum
+    const bool sched_ok = c->psw.jac_resident && kmax <= 255 && kmax >= 2 && build_jacobi_schedule(c, kmax) == MTIP_OK;
+    pp.lds_path = lds <= 158 * 1024;                            // X_l and V_r of the largest order share one CU's LDS (2l+1 <= 71)
+    const int pairs_max = kmax / 2;                             // valid pairs per round (odd k: dummy pair skipped)
+    // 16 lanes per pair when all pairs of a round still fit one workgroup, else 8
+    pp.tg = (c->psw.jac_tg == 16 && pairs_max * 16 <= JL_MAX_THREADS && nmax <= 5 * 16) ? 16 : 8;
+    pp.jac_inst = pp.tg == 16 ? PROJ_JAC_5x16 : nmax <= 9 * 8 ? PROJ_JAC_9x8 : PROJ_JAC_16x8;
+    // the launch's LDS must hold the padded (or tight) X_l and V_r of EVERY active order: they are sized by the largest
+    // k_l and 2l+1, which bound every order's
+    const size_t lds_pad = ((size_t)kmax * (div_up(nmax, pp.tg) * pp.tg + 1) + (size_t)kmax * (div_up(kmax, pp.tg) * pp.tg + 1)) * sizeof(double2);
+    pp.pad = lds_pad <= 158 * 1024 ? 1 : 0;
+    pp.lds_use = (pp.pad ? lds_pad : lds) + 16 * sizeof(double2);
+    pp.use_sched = pp.tg == 16 && sched_ok && c->js.ps * 16 <= JL_MAX_THREADS;
+    const int threads = (((pp.use_sched ? c->js.ps : pairs_max) * pp.tg + 63) / 64) * 64;
+    pp.threads = std::min(std::max(threads, 64), JL_MAX_THREADS);
+    plan_rproj(c);                                              // (after the schedule has its final size: its orders are among the above)
+    pp.planned = true;
+}
+
+// V_l, used or active change (mtip_set_projection_matrix): the plan, its tables and the carried V_r go; the pairing schedule stays
+void invalidate_projection(mtip_ctx* c) {
+    (void)hipStreamSynchronize(c->stream);                      // (kernels in flight may still read the tables)
+    c->pp = ProjPlan();
+    c->vr = VR_NONE;
 }
 
 // SO_freedom (fxs_Projections.py:768-780): `u_SO[4, 2] = u_SO[4, 2].real` on the unknowns of the chosen order after the polar
@@ -1127,7 +1174,73 @@ __global__ void __launch_bounds__(256) k_so_freedom(double2* __restrict__ U, dou
     }
 }
 
-static int launch_project_coefficients_impl(mtip_ctx* c, const double2* Ilm, double2* out, bool real_intensity);
+static int launch_project_coefficients_impl(mtip_ctx* c, const double2* Ilm, double2* out, bool real_intensity) {
+    ProfScope ps(c, "proj");
+    plan_projection(c);
+    const ProjPlan& pp = c->pp;
+    if (real_intensity && pp.real_ok) {
+        // real V_l and coefficients of a real intensity: the whole projection is one kernel in real arithmetic (k_projr.hip)
+        if (out != Ilm)
+            (void)hipMemcpyAsync(out, Ilm, (size_t)c->B * c->C * sizeof(double2), hipMemcpyDeviceToDevice, c->stream);
+        return launch_rproj(c, out);
+    }
+    // general case (complex V_l, or coefficients without the symmetry of a real intensity): complex one-sided Jacobi between
+    // the fused product pairs
+    if (int rc = build_proj_tables(c, pp.lds_path)) return rc;
+    ProjGemmArgs ga;
+    fill_gemm_args(c, ga, Ilm);
+    // cold start every 64 calls bounds the accumulated rounding drift of the carried V_r
+    const int warm = (pp.lds_path && c->vr == VR_COMPLEX && (c->proj_calls % 64) != 0) ? 1 : 0;
+    c->vr = pp.lds_path ? VR_COMPLEX : VR_NONE;
+    c->proj_calls += 1;
+    if (!(pp.fuse && warm)) launch_proj_gemm<PG_X>(c, ga);      // (fused warm start: X_l never leaves the workgroups of k_proj_xw)
+    if (pp.lds_path) {
+        const double2* src = c->d_X;
+        if (warm) {
+            ga.dst = c->d_U;
+            if (pp.fuse)                                        // X_l rows stay in LDS, W = X_l V_r straight into d_U
+                hipLaunchKernelGGL(k_proj_xw, dim3((unsigned)std::max(pp.n_pg_tiles[4], 1), (unsigned)c->B), dim3(PF_THREADS),
+                                   pp.xw_lds, c->stream, ga, (const int*)pp.d_pg_tiles[4]);
+            else
+                launch_proj_gemm<PG_WARM>(c, ga);
+            src = c->d_U;
+        }
+        const dim3 gj((unsigned)c->B, (unsigned)std::max(pp.n_jorder, 1)), bj((unsigned)pp.threads);
+        JacobiArgs ja;
+        ja.Xin_all = src; ja.Pn_all = c->d_X; ja.Vr_all = c->d_Vr;
+        ja.kl = c->d_kl; ja.active = c->d_active; ja.xoff = c->d_xoff; ja.roff = c->d_uoff;
+        ja.xtot = c->xtot; ja.rtot = c->utot; ja.L = c->L; ja.warm = warm;
+        ja.tabs2 = c->psw.polar_abs_tol * c->psw.polar_abs_tol;
+        ja.sweeps_out = c->d_sweeps; ja.pad = pp.pad;
+        ja.sched = pp.use_sched ? (const int*)c->js.d_tab : (const int*)nullptr;
+        ja.sched_off = c->js.d_off; ja.sched_rounds = c->js.d_rounds; ja.sched_ps = c->js.ps;
+        ja.order_list = pp.d_jorder;
+        {
+            ProfScope pj(c, "polar");                            // the polar-factor kernel alone (nested in "proj")
+            if (pp.jac_inst == PROJ_JAC_5x16) hipLaunchKernelGGL((k_polar_jacobi_lds<5, 16, JL_MAX_THREADS>), gj, bj, pp.lds_use, c->stream, ja);
+            else if (pp.jac_inst == PROJ_JAC_9x8) hipLaunchKernelGGL((k_polar_jacobi_lds<9, 8, JL_MAX_THREADS>), gj, bj, pp.lds_use, c->stream, ja);
+            else hipLaunchKernelGGL((k_polar_jacobi_lds<16, 8, JL_MAX_THREADS>), gj, bj, pp.lds_use, c->stream, ja);
+        }
+        if (pp.fuse) {
+            // U_l = V_r Pn^+ by column blocks, each block at once the operand of its part of I'_l = V_l U_l
+            if (out != Ilm)
+                (void)hipMemcpyAsync(out, Ilm, (size_t)c->B * c->C * sizeof(double2), hipMemcpyDeviceToDevice, c->stream);
+            ga.dst = out;
+            hipLaunchKernelGGL(k_proj_ua, dim3((unsigned)std::max(pp.n_pg_tiles[5], 1), (unsigned)c->B), dim3(PF_THREADS),
+                               pp.ua_lds, c->stream, ga, c->d_U, (const int*)pp.d_pg_tiles[5]);
+            return MTIP_OK;
+        }
+        ga.dst = c->d_U;
+        launch_proj_gemm<PG_U>(c, ga);
+    } else {
+        // X_l and V_r do not share a CU's LDS (complex 2l+1 > 71): global-memory Jacobi, cold start
+        ProfScope pj(c, "polar");
+        hipLaunchKernelGGL(k_polar_jacobi, dim3((unsigned)(c->L + 1), (unsigned)c->B), dim3(256), 0, c->stream, c->d_X,
+                           c->d_Vr, c->d_U, (const int*)c->d_kl, (const int*)c->d_active, (const int*)c->d_xoff,
+                           (const int*)c->d_uoff, c->xtot, c->utot);
+    }
+    return launch_apply_unknowns(c, Ilm, out);                  // I'_l = V_l U_l in place; a separate output first receives a copy of I_l
+}
 
 int launch_project_coefficients(mtip_ctx* c, const double2* Ilm, double2* out, bool real_intensity) {
     const int rc = launch_project_coefficients_impl(c, Ilm, out, real_intensity);
@@ -1137,119 +1250,6 @@ int launch_project_coefficients(mtip_ctx* c, const double2* Ilm, double2* out, b
                            (const uint8_t*)c->d_rmask, l, std::min(2 * l + 1, c->N), c->N, c->nlm, c->xtot, c->xoff[l], c->voff[l]);
     }
     return rc;
-}
-
-static int launch_project_coefficients_impl(mtip_ctx* c, const double2* Ilm, double2* out, bool real_intensity) {
-    ProfScope ps(c, "proj");
-    if (real_intensity && rproj_supported(c)) {
-        // real V_l and coefficients of a real intensity: the whole projection is one kernel in real arithmetic (k_projr.hip)
-        if (out != Ilm)
-            (void)hipMemcpyAsync(out, Ilm, (size_t)c->B * c->C * sizeof(double2), hipMemcpyDeviceToDevice, c->stream);
-        c->vr_valid = false;
-        return launch_rproj(c, out);
-    }
-    // general case (complex V_l, or coefficients without the symmetry of a real intensity): complex one-sided Jacobi between
-    // the fused product pairs
-    c->vr_kind = 0;
-    int kmax = 1, nmax = 1;
-    for (int l = 0; l <= c->L; ++l) {
-        if (!c->active[l]) continue;
-        kmax = std::max(kmax, c->kl[l]);
-        nmax = std::max(nmax, 2 * l + 1);
-    }
-    ProjGemmArgs ga;
-    fill_gemm_args(c, ga, Ilm);
-    if (build_proj_tiles(c) != MTIP_OK) {
-        c->err = "projection tile lists: out of device memory";
-        return MTIP_ENOMEM;
-    }
-    // fused pairs (k_proj_xw, k_proj_ua) when X_l fits the 8 waves of k_proj_xw
-    const bool fuse = c->proj_fuse && kmax <= 16 * (PF_THREADS / 64);
-    const size_t lds = ((size_t)kmax * (nmax | 1) + (size_t)kmax * (kmax | 1)) * sizeof(double2);   // unpadded minimum
-    const bool sched_ok = c->jac_resident && kmax <= 255 && kmax >= 2 && build_jacobi_schedule(c, kmax) == MTIP_OK;
-    const bool lds_path = lds <= 158 * 1024;                    // X_l and V_r of the largest order share one CU's LDS (2l+1 <= 71)
-    // cold start every 64 calls bounds the accumulated rounding drift of the carried V_r
-    const int warm = (lds_path && c->vr_valid && (c->proj_calls % 64) != 0) ? 1 : 0;
-    if (!(fuse && warm)) launch_proj_gemm<PG_X>(c, ga);         // (fused warm start: X_l never leaves the workgroups of k_proj_xw)
-    if (lds_path) {
-        const double2* src = c->d_X;
-        if (warm) {
-            ga.dst = c->d_U;
-            if (fuse)                                           // X_l rows stay in LDS, W = X_l V_r straight into d_U
-                hipLaunchKernelGGL(k_proj_xw, dim3((unsigned)std::max(c->n_pg_tiles[4], 1), (unsigned)c->B), dim3(PF_THREADS),
-                                   (size_t)16 * (kmax | 1) * sizeof(double2), c->stream, ga, (const int*)c->d_pg_tiles[4]);
-            else
-                launch_proj_gemm<PG_WARM>(c, ga);
-            src = c->d_U;
-        }
-        const int pairs_max = kmax / 2;                         // valid pairs per round (odd k: dummy pair skipped)
-        // 16 lanes per pair when all pairs of a round still fit one workgroup, else 8
-        const int tg = (c->jac_tg == 16 && pairs_max * 16 <= JL_MAX_THREADS && nmax <= 5 * 16) ? 16 : 8;
-        const size_t lds_pad = ((size_t)kmax * (div_up(nmax, tg) * tg + 1) + (size_t)kmax * (div_up(kmax, tg) * tg + 1)) * sizeof(double2);
-        const int pad = lds_pad <= 158 * 1024 ? 1 : 0;
-        const size_t lds_use = (pad ? lds_pad : lds) + 16 * sizeof(double2);
-        const bool use_sched = tg == 16 && sched_ok && c->jsched_ps * 16 <= JL_MAX_THREADS;
-        int threads = (((use_sched ? c->jsched_ps : pairs_max) * tg + 63) / 64) * 64;
-        threads = std::min(std::max(threads, 64), JL_MAX_THREADS);
-        if (c->d_jorder == nullptr) {                           // active orders, heaviest (largest k_l) first
-            std::vector<int> ord;
-            for (int l = 0; l <= c->L; ++l)
-                if (c->active[l]) ord.push_back(l);
-            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return c->kl[x] * (2 * x + 1) > c->kl[y] * (2 * y + 1); });
-            c->n_jorder = (int)ord.size();
-            if (ord.empty()) ord.push_back(0);
-            if (c->d_jorder.alloc(ord.size()) != hipSuccess) {
-                c->err = "polar factor order list: out of device memory";
-                return MTIP_ENOMEM;
-            }
-            (void)mtip_copy(c, c->d_jorder, ord.data(), ord.size() * sizeof(int), hipMemcpyHostToDevice);
-        }
-        // the launch's LDS must hold the padded (or tight) X_l and V_r of EVERY active order: they are sized by the largest
-        // k_l and 2l+1 above, which bound every order's
-        const dim3 gj((unsigned)c->B, (unsigned)std::max(c->n_jorder, 1));
-        JacobiArgs ja;
-        ja.Xin_all = src; ja.Pn_all = c->d_X; ja.Vr_all = c->d_Vr;
-        ja.kl = c->d_kl; ja.active = c->d_active; ja.xoff = c->d_xoff; ja.roff = c->d_uoff;
-        ja.xtot = c->xtot; ja.rtot = c->utot; ja.L = c->L; ja.warm = warm;
-        ja.tabs2 = c->polar_abs_tol * c->polar_abs_tol;
-        ja.sweeps_out = c->d_sweeps; ja.pad = pad;
-        ja.sched = use_sched ? (const int*)c->d_jsched : (const int*)nullptr;
-        ja.sched_off = c->d_jsched_off; ja.sched_rounds = c->d_jsched_rounds; ja.sched_ps = c->jsched_ps;
-        ja.order_list = c->d_jorder;
-        {
-            ProfScope pp(c, "polar");                            // the polar-factor kernel alone (nested in "proj")
-            if (tg == 16) hipLaunchKernelGGL((k_polar_jacobi_lds<5, 16, JL_MAX_THREADS>), gj, dim3(threads), lds_use, c->stream, ja);
-            else if (nmax <= 9 * 8) hipLaunchKernelGGL((k_polar_jacobi_lds<9, 8, JL_MAX_THREADS>), gj, dim3(threads), lds_use, c->stream, ja);
-            else hipLaunchKernelGGL((k_polar_jacobi_lds<16, 8, JL_MAX_THREADS>), gj, dim3(threads), lds_use, c->stream, ja);
-        }
-        c->vr_valid = true;
-        c->proj_calls += 1;
-        if (fuse) {
-            // U_l = V_r Pn^+ by column blocks, each block at once the operand of its part of I'_l = V_l U_l
-            if (out != Ilm)
-                (void)hipMemcpyAsync(out, Ilm, (size_t)c->B * c->C * sizeof(double2), hipMemcpyDeviceToDevice, c->stream);
-            ga.dst = out;
-            hipLaunchKernelGGL(k_proj_ua, dim3((unsigned)std::max(c->n_pg_tiles[5], 1), (unsigned)c->B), dim3(PF_THREADS),
-                               (size_t)kmax_used(c) * 17 * sizeof(double2), c->stream, ga, c->d_U, (const int*)c->d_pg_tiles[5]);
-            return MTIP_OK;
-        }
-        ga.dst = c->d_U;
-        launch_proj_gemm<PG_U>(c, ga);
-    } else {
-        // X_l and V_r do not share a CU's LDS (complex 2l+1 > 71): global-memory Jacobi, cold start
-        ProfScope pp(c, "polar");
-        hipLaunchKernelGGL(k_polar_jacobi, dim3((unsigned)(c->L + 1), (unsigned)c->B), dim3(256), 0, c->stream, c->d_X,
-                           c->d_Vr, c->d_U, (const int*)c->d_kl, (const int*)c->d_active, (const int*)c->d_xoff,
-                           (const int*)c->d_uoff, c->xtot, c->utot);
-        c->vr_valid = false;
-        c->proj_calls += 1;
-    }
-    // I'_l = V_l U_l in place on the coefficient buffer; a separate output first receives a copy of I_l
-    if (out != Ilm)
-        (void)hipMemcpyAsync(out, Ilm, (size_t)c->B * c->C * sizeof(double2), hipMemcpyDeviceToDevice, c->stream);
-    ga.dst = out;
-    launch_proj_gemm<PG_APPLY>(c, ga);
-    return MTIP_OK;
 }
 
 // ---- B_l = I_l I_l^+ ------------------------------------------------------------------------------

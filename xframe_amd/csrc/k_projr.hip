@@ -8,7 +8,8 @@
 // real Legendre matrices, 460-515) its imaginary part is exactly zero and V_l exactly real; on the `density` route
 // (extract.py:288, `Il @ Il.T.conj()`) rounding residue remains (measured with the reference here: <= 1e-17 |B_l| at even l,
 // up to 1e-7 max|V_l| in the null-space columns of V_l) -- the host takes this kernel only when Im V_l == 0 exactly for
-// every used order (or below MTIP_PROJ_REAL_TOL when that opt-in is set), otherwise the general kernels of k_proj.hip.
+// every used order (or below MTIP_PROJ_REAL_TOL when that opt-in is set), otherwise the general kernels of k_proj.hip: decided
+// once per set of V_l, with the launch geometry, by plan_rproj below (ProjPlan, mtip_internal.h).
 // I_lm are the coefficients of the REAL intensity |F|^2, so I_{l,-m} = (-1)^m conj(I_{l,m}).  Then M = V_l^T D^2 I_l (k x (2l+1), complex) is unitarily equivalent
 // to a REAL matrix: with the unitary T that maps the column pair (m, -m) to (sqrt2 Re, sqrt2 Im) of column m,
 //   M~ = M T,   M~[:, rho'] = sum_q V[q, :] q^2 I~[q, rho'],   I~[q, .] = (Re I_l0, 0, sqrt2 Re I_l1, sqrt2 Im I_l1, ...)
@@ -215,7 +216,7 @@ __host__ __device__ __forceinline__ constexpr int rp_pad_ns(int nc, int tg) { re
 __host__ __device__ __forceinline__ constexpr int rp_pad_voff(int nc, int tg) { return 16 * nc * rp_pad_ns(nc, tg); } // doubles from X~ to V_r
 
 // sums over the TG lanes of a pair-group, every lane receives them
-// The carve-up of a workgroup's dynamic LDS for one order (k columns, n2 = 2l+2 rows): the ONE definition the launcher sizes the
+// The carve-up of a workgroup's dynamic LDS for one order (k columns, n2 = 2l+2 rows): the ONE definition the plan sizes the
 // block from and the kernel takes its pointers from (gfx950 drops stores beyond the allocation silently -- two rounds in a row a
 // hand-kept second copy of this arithmetic went out of step).  Offsets in doubles from the start of the block.
 struct RpLayout {
@@ -564,7 +565,7 @@ __device__ __forceinline__ void rp_solve(const RProjArgs& A, int b, int l, RpSha
     // up to RP_PAD_MAX_NR row slots: zero-padded columns, one stride, V_r a fixed distance behind X~ (rp_sweep_pad); beyond
     // (config 5) the matrices fill the CU: tight columns, predicates on the last row slot (rp_sweep)
     const RpLayout lay = rp_layout(k, n2, TG, A.tab_ints, A.tab2_entries);
-    if (lay.end_bytes > (size_t)A.lds_bytes) {           // never with the launcher of this file: host and device share rp_layout
+    if (lay.end_bytes > (size_t)A.lds_bytes) {           // never with the plan of this file: host and device share rp_layout
         if (tid == 0) A.sweeps_out[b * (A.L + 1) + l] = RP_LAYOUT_ERROR;
         return;
     }
@@ -1166,31 +1167,34 @@ __global__ void __launch_bounds__(MAXT) k_rproj(RProjArgs A) {
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-// lanes per column pair, threads and dynamic LDS of a k_rproj launch.  LDS: the largest order's matrices -- padded layout up to
-// RP_PAD_MAX_NR blocks of 16 columns, behind them the raw pairing table and its per-sweep translation (one int2 per round and
-// group); tight layout beyond (table read from L2) -- whichever needs more; tab_ints = ints reserved for the raw table
-struct RpGeom {
-    int tg = 16, threads = 256, tab_ints = 0, tab2_entries = 0, acc = RP_ACC_MAX;
-    bool big = false;                  // some order has the tight layout (k_rproj<768, ...>)
-    size_t lds = 0;
-};
-static RpGeom rp_launch_geometry(const mtip_ctx* c) {
-    RpGeom g;
+// The real route of the plan (ProjPlan, RpGeom: mtip_internal.h).  The geometry's LDS: the largest order's matrices -- padded layout
+// up to RP_PAD_MAX_NR blocks of 16 columns, behind them the raw pairing table and its per-sweep translation (one int2 per round
+// and group); tight layout beyond (table read from L2) -- whichever needs more.
+void plan_rproj(mtip_ctx* c) {
+    ProjPlan& pp = c->pp;
+    RpGeom& g = pp.rg;
+    g = RpGeom();
+    pp.real_ok = false;
+    if (!c->psw.real) return;
     int kpad = 0, kbig = 0;
-    for (int l = 1; l <= c->L; ++l) {
-        if (!c->active[l]) continue;
+    for (int l = 0; l <= c->L; ++l) {
+        if (!c->used[l]) continue;
+        if (!c->v_real[l]) return;
+        if (!c->active[l] || l == 0) continue;
+        if (c->kl[l] != 2 * l + 1) return;
         if ((c->kl[l] + 1 + 15) / 16 <= RP_PAD_MAX_NR) kpad = std::max(kpad, c->kl[l]);
         else kbig = std::max(kbig, c->kl[l]);
     }
     const int kmax = std::max(kpad, kbig);
-    const int ps = kmax >= 2 ? std::max(c->jsched_ps, 1) : 1;        // row length of the pairing table (it may have been built for more columns)
+    if (kmax > 111) return;
+    if (kmax >= 2 && build_jacobi_schedule(c, kmax) != MTIP_OK) return;
+    const int ps = kmax >= 2 ? std::max(c->js.ps, 1) : 1;            // row length of the pairing table (it may have been built for more columns)
     const int groups = kmax >= 2 ? std::max(jacobi_groups(kmax), 1) : 1; // pair-groups the largest order keeps busy
-    g.tg = 16;
     g.big = kbig > 0;
     g.threads = std::max(256, (groups * g.tg + 63) / 64 * 64);
     if (kpad >= 2) {
         int nrd = 1;                                             // (the schedule has more rounds than columns: 70 at k = 65)
-        for (int ke = 2; ke <= kpad && ke < (int)c->jsched_nrd.size(); ++ke) nrd = std::max(nrd, c->jsched_nrd[ke]);
+        for (int ke = 2; ke <= kpad && ke < (int)c->js.nrd.size(); ++ke) nrd = std::max(nrd, c->js.nrd[ke]);
         g.tab_ints = (nrd * ps + 1) & ~1;
         g.tab2_entries = nrd * (g.threads / g.tg);
     }
@@ -1202,31 +1206,10 @@ static RpGeom rp_launch_geometry(const mtip_ctx* c) {
     // the in-place products hold all their 16 x 16 tiles in registers across a barrier
     const int nt16 = (kmax + 1 + 15) / 16;
     g.acc = div_up(nt16 * nt16, g.threads / 64);
-    return g;
-}
-
-// every solved order square (k_l = 2l+1), V_l real, 2l+2 <= 7 row slots of 16, the schedule and the matrices fit
-bool rproj_supported(mtip_ctx* c) {
-    if (!c->proj_real) return false;
-    int kmax = 0;
-    for (int l = 0; l <= c->L; ++l) {
-        if (!c->used[l]) continue;
-        if (!c->v_real[l]) return false;
-        if (c->active[l] && l > 0) {
-            if (c->kl[l] != 2 * l + 1) return false;
-            kmax = std::max(kmax, c->kl[l]);
-        }
-    }
-    if (kmax > 111) return false;
-    if (kmax >= 2) {
-        if (build_jacobi_schedule(c, kmax) != MTIP_OK) return false;
-        const RpGeom g = rp_launch_geometry(c);
-        // the instantiations of launch_rproj: <512, ...> up to 512 threads, <768, ...> (tight layout, config 5) up to 768
-        if (g.threads > 768) return false;             // (l = 49: 49 pair-groups = 832 threads -> the general kernels)
-        if (g.lds + sizeof(RpShared) + 256 > 160 * 1024) return false;
-        if (g.acc > (g.threads <= 512 ? 4 : RP_ACC_MAX)) return false;    // tiles per wave of those instantiations
-    }
-    return true;
+    // the instantiations of launch_rproj: <512, ...> up to 512 threads, <768, ...> (tight layout, config 5) up to 768
+    pp.real_ok = kmax < 2 || (g.threads <= 768                   // (l = 49: 49 pair-groups = 832 threads -> the general kernels)
+                              && g.lds + sizeof(RpShared) + 256 <= 160 * 1024
+                              && g.acc <= (g.threads <= 512 ? 4 : RP_ACC_MAX));   // tiles per wave of those instantiations
 }
 
 // cost model of one order inside a slot, in cycles, from the in-kernel timers at 128 x L32 (profiles/r03_rproj_round_timers.txt):
@@ -1236,7 +1219,8 @@ bool rproj_supported(mtip_ctx* c) {
 static double rp_cost(int k) { return 38e3 + 1550.0 * k + 3.0 * (1.08 * k) * (2000.0 + 8.0 * k); }
 
 static int build_rproj_tables(mtip_ctx* c) {
-    if (c->d_rp_slots != nullptr) return MTIP_OK;
+    ProjPlan& pp = c->pp;
+    if (pp.d_rp_slots != nullptr) return MTIP_OK;
     const int L = c->L, N = c->N;
     // real tables: q^2 V (N x k) and V^T (k x N) per order, from the host copy of V
     std::vector<double> q(N);
@@ -1301,61 +1285,51 @@ static int build_rproj_tables(mtip_ctx* c) {
     std::vector<int> flat(slots.size() * slot_len, -1);
     for (size_t s = 0; s < slots.size(); ++s)
         for (size_t i = 0; i < slots[s].size(); ++i) flat[s * slot_len + i] = slots[s][i];
-    if (c->d_rp_DV.alloc(DV.size()) != hipSuccess ||
-        c->d_rp_Vt.alloc(Vt.size()) != hipSuccess ||
-        c->d_rp_slots.alloc(flat.size()) != hipSuccess)
+    if (pp.d_rp_DV.alloc(DV.size()) != hipSuccess ||
+        pp.d_rp_Vt.alloc(Vt.size()) != hipSuccess ||
+        pp.d_rp_slots.alloc(flat.size()) != hipSuccess)
         return MTIP_ENOMEM;
-    (void)mtip_copy(c, c->d_rp_DV, DV.data(), DV.size() * sizeof(double), hipMemcpyHostToDevice);
-    (void)mtip_copy(c, c->d_rp_Vt, Vt.data(), Vt.size() * sizeof(double), hipMemcpyHostToDevice);
-    (void)mtip_copy(c, c->d_rp_slots, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice);
-    c->rp_n_slots = (int)slots.size();
-    c->rp_slot_len = slot_len;
+    (void)mtip_copy(c, pp.d_rp_DV, DV.data(), DV.size() * sizeof(double), hipMemcpyHostToDevice);
+    (void)mtip_copy(c, pp.d_rp_Vt, Vt.data(), Vt.size() * sizeof(double), hipMemcpyHostToDevice);
+    (void)mtip_copy(c, pp.d_rp_slots, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice);
+    pp.rp_n_slots = (int)slots.size();
+    pp.rp_slot_len = slot_len;
     return MTIP_OK;
 }
 
-void free_rproj_tables(mtip_ctx* c) {
-    if (c->d_rp_slots == nullptr && c->d_rp_DV == nullptr) return;
-    (void)hipStreamSynchronize(c->stream);
-    c->d_rp_DV.reset();
-    c->d_rp_Vt.reset();
-    c->d_rp_slots.reset();
-}
-
-// in place on `coef` (the caller has copied I_lm there when its output is a different buffer)
+// in place on `coef` (the caller has copied I_lm there when its output is a different buffer); geometry from the plan
 int launch_rproj(mtip_ctx* c, double2* coef) {
-    if (int rc = build_rproj_tables(c)) {
+    if (int rc = build_rproj_tables(c)) {                        // (the route's first call after an invalidation)
         c->err = "real projection tables: out of device memory";
         return rc;
     }
-    int kmax = 1;
-    for (int l = 1; l <= c->L; ++l)
-        if (c->active[l]) kmax = std::max(kmax, c->kl[l]);
+    const ProjPlan& pp = c->pp;
     RProjArgs a;
     a.coef = reinterpret_cast<double*>(coef);
-    a.DV = c->d_rp_DV; a.Vt = c->d_rp_Vt;
+    a.DV = pp.d_rp_DV; a.Vt = pp.d_rp_Vt;
     a.Vr = reinterpret_cast<double*>((double2*)c->d_Vr);
     a.U = c->d_U;
     a.rmask = c->d_rmask;
     a.kl = c->d_kl; a.voff = c->d_voff; a.uoff = c->d_uoff; a.xoff = c->d_xoff;
-    a.slots = c->d_rp_slots; a.slot_len = c->rp_slot_len;
-    a.sched = c->d_jsched; a.sched_off = c->d_jsched_off; a.sched_rounds = c->d_jsched_rounds;
-    a.sched_ps = std::max(c->jsched_ps, 1);
+    a.slots = pp.d_rp_slots; a.slot_len = pp.rp_slot_len;
+    a.sched = c->js.d_tab; a.sched_off = c->js.d_off; a.sched_rounds = c->js.d_rounds;
+    a.sched_ps = std::max(c->js.ps, 1);
     a.N = c->N; a.L = c->L; a.nlm = c->nlm; a.utot = c->utot; a.xtot = c->xtot;
     // cold start every 64 calls bounds the accumulated rounding drift of the carried V_r
-    a.warm = (c->vr_kind == 2 && (c->proj_calls % 64) != 0) ? 1 : 0;
-    a.tabs2 = c->polar_abs_tol * c->polar_abs_tol;
-    a.corr = c->rp_corr ? 1 : 0;
-    a.rp_early = c->rp_early;
-    a.rp_corr2_max = c->rp_corr2_max;
+    a.warm = (c->vr == VR_REAL && (c->proj_calls % 64) != 0) ? 1 : 0;
+    a.tabs2 = c->psw.polar_abs_tol * c->psw.polar_abs_tol;
+    a.corr = c->psw.rp_corr ? 1 : 0;
+    a.rp_early = c->psw.rp_early;
+    a.rp_corr2_max = c->psw.rp_corr2_max;
     a.inv_sqrt_np = 1.0 / std::sqrt(c->n_particles);
     a.sweeps_out = c->d_sweeps;
     a.dbg = c->d_polar_dbg;
-    const RpGeom g = rp_launch_geometry(c);
+    const RpGeom& g = pp.rg;
     a.tab_ints = g.tab_ints;
     a.tab2_entries = g.tab2_entries;
     a.lds_bytes = (int)g.lds;
-    ProfScope pp(c, "polar");                                    // (the whole projection is this one kernel)
-    const dim3 grid((unsigned)c->B, (unsigned)c->rp_n_slots), block((unsigned)g.threads);
+    ProfScope pj(c, "polar");                                    // (the whole projection is this one kernel)
+    const dim3 grid((unsigned)c->B, (unsigned)pp.rp_n_slots), block((unsigned)g.threads);
     // registers by launch bound: 512 threads = two waves per SIMD, 256 registers each; 768 (the 97-column orders of config 5) =
     // three, 168 each
     if (g.threads <= 512)
@@ -1367,7 +1341,7 @@ int launch_rproj(mtip_ctx* c, double2* coef) {
         c->err = std::string("k_rproj launch: ") + hipGetErrorString(le);
         return MTIP_EHIP;
     }
-    c->vr_kind = 2;
+    c->vr = VR_REAL;
     c->proj_calls += 1;
     return MTIP_OK;
 }

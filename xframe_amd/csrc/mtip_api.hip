@@ -38,6 +38,21 @@ static int dev_alloc(mtip_ctx* c, DevBuf<T>* p, size_t n) {
     return MTIP_OK;
 }
 
+// The closing-step thresholds are held to the range the parity cases cover (test_projection_real_switches): a stray shell
+// variable must not loosen the 1e-10 operator
+static ProjSwitches read_proj_switches() {
+    ProjSwitches s;
+    if (const char* e = std::getenv("MTIP_PROJ_FUSE")) s.fuse = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MTIP_JAC_RESIDENT")) s.jac_resident = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MTIP_JAC_TG")) s.jac_tg = std::atoi(e) == 8 ? 8 : 16;
+    if (const char* e = std::getenv("MTIP_PROJ_REAL")) s.real = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MTIP_POLAR_ABS_TOL")) s.polar_abs_tol = std::atof(e);
+    if (const char* e = std::getenv("MTIP_RP_CORR")) s.rp_corr = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MTIP_RP_EARLY")) s.rp_early = std::min(std::max(std::atof(e), 1e-3), 0.2);
+    if (const char* e = std::getenv("MTIP_RP_CORR2_MAX")) s.rp_corr2_max = std::min(std::max(std::atof(e), 1e-6), 5e-4);
+    return s;
+}
+
 extern "C" {
 
 int mtip_device_count(void) {
@@ -96,7 +111,6 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     c->nlm = (c->L + 1) * (c->L + 1);
     c->nm = 2 * c->L + 1;
     c->Np = cfg->hankel_trapz ? c->N - 1 : c->N;
-    if (const char* e = std::getenv("MTIP_POLAR_ABS_TOL")) c->polar_abs_tol = std::atof(e);
     c->G = (size_t)c->N * c->nt * c->np;
     c->C = (size_t)c->N * c->nlm;
     const int L = c->L, N = c->N, B = c->B;
@@ -120,10 +134,7 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     A(dev_alloc(c, &c->d_lmtab, c->npairs));
     A(dev_alloc(c, &c->d_PTc, (size_t)(c->nt / 2 + 1) * 768));
     A(dev_alloc(c, &c->d_lmc, 768));
-    if (const char* e = std::getenv("MTIP_PROJ_FUSE")) c->proj_fuse = std::atoi(e) != 0;
     if (const char* e = std::getenv("MTIP_DEG2_SIMPLE")) c->deg2_simple = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MTIP_JAC_RESIDENT")) c->jac_resident = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MTIP_JAC_TG")) c->jac_tg = std::atoi(e) == 8 ? 8 : 16;
     if (const char* e = std::getenv("MTIP_HANKEL_CT")) {
         const int v = std::atoi(e);
         c->htile_force = (v == 1 || v == 2 || v == 3 || v == 5) ? v : 0;
@@ -143,12 +154,7 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     c->uoff.assign(L + 2, 0);
     c->have_V.assign(L + 1, 0);
     c->v_real.assign(L + 1, 1);
-    if (const char* e = std::getenv("MTIP_PROJ_REAL")) c->proj_real = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MTIP_RP_CORR")) c->rp_corr = std::atoi(e) != 0;
-    // closing-step thresholds: A/B switches, held to the range the parity cases cover (test_projection_real_switches) -- a stray
-    // shell variable must not loosen the 1e-10 operator
-    if (const char* e = std::getenv("MTIP_RP_EARLY")) c->rp_early = std::min(std::max(std::atof(e), 1e-3), 0.2);
-    if (const char* e = std::getenv("MTIP_RP_CORR2_MAX")) c->rp_corr2_max = std::min(std::max(std::atof(e), 1e-6), 5e-4);
+    c->psw = read_proj_switches();
     for (int l = 0; l <= L; ++l) {
         const int n = 2 * l + 1, k = std::min(n, N);
         c->kl[l] = k;                               // default; mtip_set_projection_matrix may give a smaller k_l
@@ -291,14 +297,7 @@ int mtip_set_projection_matrix(mtip_ctx* c, int l, const mtip_cdouble* V, int k_
     if (k_l < 1 || k_l > kmax) FAIL(c, MTIP_EINVAL, "k_l must be in [1, min(2l+1, Nq)]");
     if (used && (!V || !radial_mask)) FAIL(c, MTIP_EINVAL, "null projection matrix");
     (void)hipSetDevice(c->device);
-    if (c->d_jorder != nullptr) {                        // ... and so does the order list of the polar-factor kernel
-        (void)hipStreamSynchronize(c->stream);
-        c->d_jorder.reset();
-    }
-    if (c->d_pg_tiles[0] != nullptr) {                   // the tile lists of the projection GEMMs depend on k_l / used
-        (void)hipStreamSynchronize(c->stream);
-        for (int op = 0; op < 6; ++op) c->d_pg_tiles[op].reset();
-    }
+    invalidate_projection(c);                            // route, geometry and tables depend on V_l / used: the next projection plans again
     // the storage slot has room for kmax columns; a narrower matrix is zero padded (zero columns of V
     // do not contribute to V_l U_l)
     std::vector<double2> tmp((size_t)c->N * kmax, make_double2(0.0, 0.0));
@@ -321,7 +320,6 @@ int mtip_set_projection_matrix(mtip_ctx* c, int l, const mtip_cdouble* V, int k_
     }
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_V + c->voff[l], tmp.data(), tmp.size() * sizeof(double2), hipMemcpyHostToDevice));
     std::copy(tmp.begin(), tmp.end(), c->h_V.begin() + c->voff[l]);
-    free_rproj_tables(c);                                // tables and slot lists of the real projection depend on V_l / used
     bool is_real = true;
     for (const double2& v : tmp) is_real = is_real && v.y == 0.0;
     c->v_real[l] = is_real ? 1 : 0;
@@ -330,8 +328,6 @@ int mtip_set_projection_matrix(mtip_ctx* c, int l, const mtip_cdouble* V, int k_
     bool nonzero = false;
     for (const double2& v : tmp) nonzero = nonzero || v.x != 0.0 || v.y != 0.0;
     c->active[l] = (used && nonzero) ? 1 : 0;          // V_l == 0 (odd_orders_to_0): U_l stays 0, nothing to solve
-    c->vr_valid = false;
-    c->vr_kind = 0;
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_used, c->used.data(), (c->L + 1) * sizeof(int), hipMemcpyHostToDevice));
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_active, c->active.data(), (c->L + 1) * sizeof(int), hipMemcpyHostToDevice));
     MTIP_HIP_CHECK(c, hipMemsetAsync(c->d_U, 0, (size_t)c->B * c->xtot * sizeof(double2), c->stream));
@@ -833,8 +829,7 @@ int mtip_init_state(mtip_ctx* c) {
     c->n_steps_done = 0;
     c->fixed_valid = false;
     c->c0n_valid = false;
-    c->vr_valid = false;                 // a fresh reconstruction does not warm-start its polar factors
-    c->vr_kind = 0;
+    c->vr = VR_NONE;                     // a fresh reconstruction does not warm-start its polar factors
     c->proj_calls = 0;
     c->state_ready = true;
     return post_launch(c, "mtip_init_state");
@@ -1183,8 +1178,7 @@ int mtip_op_apply_unknowns(mtip_ctx* c, const mtip_cdouble* Ilm, const mtip_cdou
     SYNC();
     H2D(c->d_c[2], Ilm, (size_t)c->B * c->C * sizeof(double2));
     H2D(c->d_U, U, (size_t)c->B * c->xtot * sizeof(double2));
-    c->vr_valid = false;                     // d_U no longer belongs to the carried right singular vectors
-    c->vr_kind = 0;
+    c->vr = VR_NONE;                         // d_U no longer belongs to the carried right singular vectors
     const int rp = launch_apply_unknowns(c, c->d_c[2], c->d_c[3]);
     if (rp != MTIP_OK) return rp;
     SYNC();
@@ -1298,7 +1292,7 @@ int mtip_debug_hankel_tiles(mtip_ctx* c, int* ct, int* n_tiles, int* n_row_block
 
 int mtip_debug_projection_slots(mtip_ctx* c) {
     CTX_CHECK(c);
-    return c->vr_kind == 2 ? c->rp_n_slots : 0;
+    return c->vr == VR_REAL ? c->pp.rp_n_slots : 0;
 }
 
 __global__ void k_debug_spin(long long ticks) {

@@ -245,6 +245,54 @@ private:
 };
 static_assert(!std::is_copy_constructible_v<DevBuf<double>>);
 
+// Pairing schedule of the one-sided Jacobi kernels (build_jacobi_schedule, k_proj.hip), shared by the projection and extract's
+// eigensolver: it depends on a column count only and grows when a caller asks for more columns
+struct JacobiSchedule {
+    DevBuf<int> d_tab, d_off, d_rounds;               // entries, offset of every column count's table, rounds of a sweep per column count
+    int kmax = 0, ps = 0;                             // column count it was built for, row length (pair-groups) of every table
+    std::vector<int> nrd, off;                        // host copies of d_rounds and d_off
+};
+struct ProjSwitches {                                 // the projection's switches, read once (read_proj_switches, at mtip_create)
+    bool fuse = true;                                 // MTIP_PROJ_FUSE=0: four separate projection products instead of the two fused pairs
+    bool jac_resident = true;                         // MTIP_JAC_RESIDENT=0: round-robin ordering, both columns via LDS
+    int jac_tg = 16;                                  // MTIP_JAC_TG=8|16: lanes per Jacobi column pair
+    bool real = true;                                 // MTIP_PROJ_REAL=0: never take the real form of the projection (k_projr.hip)
+    double polar_abs_tol = 0.0;                       // MTIP_POLAR_ABS_TOL: 0 = purely relative Jacobi criterion
+    bool rp_corr = true;                              // MTIP_RP_CORR=0: k_rproj closes its sweeps with the classic confirming sweep
+    double rp_early = 3e-2, rp_corr2_max = 1.5e-4;    // MTIP_RP_EARLY, MTIP_RP_CORR2_MAX: thresholds of the closing step (k_projr.hip)
+};
+struct RpGeom {                                       // threads and dynamic LDS of a k_rproj launch (plan_rproj, k_projr.hip)
+    int tg = 16, threads = 256, acc = 0;              // lanes per column pair; 16 x 16 tiles a wave holds in the in-place products
+    int tab_ints = 0, tab2_entries = 0;               // ints reserved for the raw pairing table, entries of its per-sweep translation
+    bool big = false;                                 // some order has the tight layout (k_rproj<768, ...>)
+    size_t lds = 0;
+};
+
+// How the reciprocal projection runs, decided once per set of V_l (plan_projection, k_proj.hip: on the first projection after
+// invalidate_projection, which every mtip_set_projection_matrix calls).  A call with real_intensity takes the one real kernel
+// (k_rproj) where `real_ok`: the switch `real`, every used V_l without imaginary part, every solved order square (k_l = 2l+1) with
+// at most 111 columns, and a geometry `rg` within k_rproj's instantiations (768 threads, 160 KiB LDS, the tiles a wave can hold).
+// Every other call takes the complex kernels: the polar factors in LDS (k_polar_jacobi_lds<jac_inst>) where X_l and V_r of the
+// largest order fit a CU (`lds_path`), else in global memory, between the fused product pairs (`fuse`) or the four products.
+// The plan owns the tables made from V_l, k_l, used and active; each route's are built when that route first runs.  `rg`,
+// `use_sched` and `threads` depend on the pairing schedule's row length and round counts (c->js.ps, c->js.nrd), which grow when
+// build_jacobi_schedule is asked for more columns: it clears `planned` and the next projection decides again (tables and V_r stay).
+enum { PROJ_JAC_5x16 = 0, PROJ_JAC_9x8, PROJ_JAC_16x8 };   // k_polar_jacobi_lds<MAXR, TG, ...>
+struct ProjPlan {
+    bool planned = false, real_ok = false;
+    RpGeom rg;
+    int kmax = 1, nmax = 1, kmax_used = 1;            // largest k_l and 2l+1 over the active orders, largest k_l the apply product touches
+    bool fuse = false, lds_path = false, use_sched = false;
+    int tg = 16, pad = 0, threads = 64, jac_inst = PROJ_JAC_5x16;
+    size_t lds_use = 0, xw_lds = 0, ua_lds = 0;       // dynamic LDS of the polar-factor kernel, of k_proj_xw and of k_proj_ua
+    DevBuf<int> d_jorder;                             // active orders, heaviest first (grid of the polar-factor kernel)
+    DevBuf<int> d_pg_tiles[6];                        // (order, tile) lists of the projection GEMMs (4, 5: fused pairs)
+    int n_jorder = 0, n_pg_tiles[6] = {0, 0, 0, 0, 0, 0}, rp_n_slots = 0, rp_slot_len = 0;
+    DevBuf<double> d_rp_DV, d_rp_Vt;                  // q^2 V_l (N x k) and V_l^T (k x N), real, at voff[l]
+    DevBuf<int> d_rp_slots;                           // (rp_n_slots, rp_slot_len) order | kind << 8 lists of the k_rproj workgroups
+};
+enum { VR_NONE = 0, VR_COMPLEX, VR_REAL };            // what d_Vr carries from the previous projection: a route warm-starts only from its own kind
+
 struct HankelTile32;                                  // k_hankel.hip
 
 struct mtip_ctx {
@@ -272,12 +320,7 @@ struct mtip_ctx {
     DevBuf<double2> d_tw;
     DevBuf<double> d_W;
     int n_cu = 256;                                   // compute units of the device (persistent-grid sizing)
-    bool jac_resident = true;                         // env MTIP_JAC_RESIDENT=0: round-robin ordering, both columns via LDS
-    DevBuf<int> d_jsched, d_jsched_off, d_jsched_rounds;   // resident-column pairing schedule
-    int jsched_kmax = 0, jsched_ps = 0;
-    std::vector<int> jsched_nrd;                      // rounds of a sweep for every column count (host copy of d_jsched_rounds)
-    double rp_early = 3e-2, rp_corr2_max = 1.5e-4;     // thresholds of the closing step (k_projr.hip RP_EARLY_CORR, RP_CORR2_MAX; env MTIP_RP_EARLY, MTIP_RP_CORR2_MAX)
-    bool rp_corr = true;                              // k_rproj: close the Jacobi sweeps with the first-order polar step (MTIP_RP_CORR=0: classic)
+    JacobiSchedule js;                                // resident-column pairing schedule
     // non-default reciprocal metrics (k_metrics.hip): flags 1 II_error | 2 ccd_diff | 4 fqc_error, their constant tables, history rows
     uint32_t im_which = 0;
     DevBuf<uint8_t> d_im_zmask;
@@ -288,13 +331,7 @@ struct mtip_ctx {
     DevBuf<double> d_im_qq, d_im_ccdT, d_im_P, d_im_refavg, d_im_refw, d_im_hist;
     double im_ccd_inv_norm = 0.0;
     int so_order = -1;                                // SO_freedom: order whose unknown [4][2] is made real after every projection (-1: off)
-    std::vector<int> jsched_off_h;                    // offsets of the per-column-count tables in d_jsched (host copy of d_jsched_off)
-    DevBuf<int> d_jorder;                          // active orders, heaviest first (grid of the polar-factor kernel)
-    int n_jorder = 0;
-    DevBuf<int> d_pg_tiles[6];   // (order, tile) lists of the projection GEMMs (4, 5: fused pairs)
-    int n_pg_tiles[6] = {0, 0, 0, 0, 0, 0};
     DevBuf<long long> d_polar_dbg;                 // (B, L+1, MTIP_POLAR_DBG_SLOTS) phase / round timers of k_rproj, allocated by mtip_debug_polar_timing
-    int jac_tg = 16;                                  // env MTIP_JAC_TG=8|16: lanes per Jacobi column pair
     DevBuf<double2> d_c0n;                         // (B, C) SHT of the current density, written by the chained last kernel of a step
     DevBuf<long long> d_chain_dbg;                 // (3 kinds, B * Nq, MTIP_CHAIN_DBG_SLOTS) phase stamps of k_sht_chain, allocated by mtip_debug_chain_timing
     bool c0n_valid = false;                           // d_c0n holds SHT(rho[SL_CUR]) of every restart
@@ -304,19 +341,15 @@ struct mtip_ctx {
     double fwd_scale = 0, inv_scale = 0;
     bool have_angular = false, have_radial = false, have_weights = false, have_support = false, have_errw = false;
     // projection data
+    ProjSwitches psw;
+    ProjPlan pp;                                      // route, geometry and V_l tables of the projection (plan_projection)
     std::vector<int> kl, used, active, voff, xoff, uoff;     // host copies (active = used and V_l != 0)
     DevBuf<int> d_active;
     DevBuf<int> d_sweeps;                          // (B, L+1) Jacobi sweeps of the last projection (diagnostic)
-    bool vr_valid = false;                            // d_Vr holds (complex) right singular vectors of the previous call
-    int vr_kind = 0;                                  // 2: d_Vr holds the REAL right singular vectors of the previous k_rproj call
-    bool proj_real = true;                            // env MTIP_PROJ_REAL=0: never take the real form of the projection (k_projr.hip)
     std::vector<char> v_real;                         // per order: V_l has no imaginary part
     std::vector<double2> h_V;                         // host copy of the concatenated V_l (tables of the real projection)
-    DevBuf<double> d_rp_DV, d_rp_Vt;    // q^2 V_l (N x k) and V_l^T (k x N), real, at voff[l]
-    DevBuf<int> d_rp_slots;                        // (rp_n_slots, rp_slot_len) order | kind << 8 lists of the k_rproj workgroups
-    int rp_n_slots = 0, rp_slot_len = 0;
-    long long proj_calls = 0;
-    double polar_abs_tol = 0.0;                       // 0 = purely relative Jacobi criterion (env MTIP_POLAR_ABS_TOL)
+    int vr = VR_NONE;                                 // what d_Vr holds (VR_*)
+    long long proj_calls = 0;                         // every 64th call starts cold: bounds the rounding drift of the carried V_r
     DevBuf<int> d_kl, d_used, d_voff, d_xoff, d_uoff;
     int vtot = 0, xtot = 0, utot = 0;                 // per-restart element counts
     DevBuf<double2> d_V;                           // concatenated V_l, (Nq, k_l) row-major each
@@ -328,7 +361,6 @@ struct mtip_ctx {
     DevBuf<double2> d_Bref;                        // (L+1, Nq, Nq) masked reference B_l
     DevBuf<double> d_Bnorm;                        // (L+1)
     DevBuf<double> d_deg2_part;                    // (B, L+1, (Nq/16)^2) per-tile partial sums of the B_l metric
-    bool proj_fuse = true;                            // env MTIP_PROJ_FUSE=0: four separate projection products instead of the two fused pairs
     bool deg2_simple = false;                         // env MTIP_DEG2_SIMPLE=1: one thread per B_l element instead of MFMA tiles
     bool bref_dirty = true;
     // real-space constraints and error metric
@@ -403,7 +435,7 @@ void launch_hankel(mtip_ctx* c, const double2* in, double2* out, int inverse);
 bool hankel_has_difference(const mtip_ctx* c);       // launch_hankel_mfma_sub is available (workgroup-tiled kernel)
 void launch_hankel_mfma_sub(mtip_ctx* c, const double2* in, const double2* in_sub, double2* out, int inverse, const uint8_t* sub_mask = nullptr);
 int build_jacobi_schedule(mtip_ctx* c, int kmax);    // k_proj.hip: resident-column pairing schedule, verified on the host
-int jacobi_groups(int k);                            // pair-groups a round of that schedule keeps busy for k columns (<= jsched_ps: the table's row length)
+int jacobi_groups(int k);                            // pair-groups a round of that schedule keeps busy for k columns (<= js.ps: the table's row length)
 int build_hankel_tiles(mtip_ctx* c);
 int hankel_row_blocks(const mtip_ctx* c);            // row blocks (128 output shells each) of k_hankel_tile: the grid's y extent
 int launch_invariant_metrics(mtip_ctx* c, const double2* Ilm, long long step);
@@ -414,11 +446,11 @@ void launch_coeff_diff(mtip_ctx* c, const double2* a, const double2* b, double2*
 // real_intensity: the caller guarantees I_{l,-m} = (-1)^m conj(I_{l,m}) (coefficients of a real grid, as in the phasing
 // loop): with real V_l the projection then takes its real form (k_projr.hip)
 int launch_project_coefficients(mtip_ctx* c, const double2* Ilm, double2* out, bool real_intensity = false);   // MTIP_OK or an error code (c->err set)
-bool rproj_supported(mtip_ctx* c);                    // k_projr.hip
+void plan_projection(mtip_ctx* c);                    // k_proj.hip: decides c->pp where it is not planned
+void plan_rproj(mtip_ctx* c);                         // k_projr.hip: real_ok and rg of c->pp
+void invalidate_projection(mtip_ctx* c);              // k_proj.hip: V_l, k_l, used or active change: drops the plan, its tables and the carried V_r
 int launch_rproj(mtip_ctx* c, double2* coef);         // in place
-void free_rproj_tables(mtip_ctx* c);
 int launch_apply_unknowns(mtip_ctx* c, const double2* Ilm, double2* out);
-void launch_deg2(mtip_ctx* c, const double2* Ilm, double2* Bl);
 void launch_deg2_metric(mtip_ctx* c, const double2* Ilm, double* out /*(B, L+1)*/);
 // elementwise / reductions
 // rho_p = IFT(F') (B,G); prev/out: slot arrays (3,B,G) when use_slots else plain (B,G); rho_rt may be null
