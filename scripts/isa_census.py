@@ -155,6 +155,20 @@ def census_of_listing(text):
                         detail['clock'] += 1
                     if a.startswith('v_mfma'):
                         detail['mfma'] += 1
+                    if a == 's_endpgm':                                     # no loop: a block placed behind the kernel's end that jumps back
+                        detail['endpgm'] += 1
+                    if a.startswith('ds_read_b128'):
+                        detail['ds_read_b128'] += 1
+                    if a.startswith('ds_write'):
+                        detail['lds_store'] += 1
+                    if a.startswith('global_'):
+                        detail['global'] += 1
+                    if a.startswith('global_load'):
+                        detail['global_load'] += 1
+                    if a.startswith('s_waitcnt') and 'vmcnt(' in b:
+                        detail['vmcnt'] += 1
+                        if 'vmcnt(0)' in b:
+                            detail['vmcnt0'] += 1
                 barriers = sum(1 for _, a, _b in span if a == 's_barrier')
                 loops.append(Loop(target, span[0][0], ln, barriers, len(span), counts, detail))
         # the figures the compiler prints behind the kernel

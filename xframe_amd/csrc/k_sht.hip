@@ -5,6 +5,7 @@
 // from shtns (xframe/externalLibraries/shtns_plugin.py:20-24, 250-261).
 #include "mtip_internal.h"
 #include "k_sht_common.h"
+#include "k_sht_legendre.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -17,7 +18,9 @@ void build_legendre_tables(mtip_ctx* c, const double* cos_theta) {
     for (int m = 0; m <= L + 1; ++m) poff[m] = m * (L + 1) - m * (m - 1) / 2;
     const size_t rows = (size_t)(L + 1) * (L + 2) / 2;
     std::vector<double> P(rows * nt);
-    std::vector<double2> AB(rows, make_double2(0.0, 0.0));   // P_lm = a_lm (x P_l-1,m - b_lm P_l-2,m), l >= m + 2
+    // P_lm = a_lm (x P_l-1,m - b_lm P_l-2,m), l >= m + 2; in the record order of the synthesis (k_sht_legendre.h): the rows of an
+    // order run to l = L + 1, and what is no step of the recurrence stays zero
+    std::vector<double2> AB((size_t)legendre_n_rec(L), make_double2(0.0, 0.0));
     const double pi = 3.14159265358979323846;
     for (int t = 0; t < nt; ++t) {
         const double x = cos_theta[t];
@@ -35,7 +38,7 @@ void build_legendre_tables(mtip_ctx* c, const double* cos_theta) {
                     const double b = std::sqrt((((double)l - 1.0) * (l - 1.0) - (double)m * m) / (4.0 * (l - 1.0) * (l - 1.0) - 1.0));
                     const double p = a * (x * p1 - b * p2);
                     P[(size_t)(poff[m] + l - m) * nt + t] = p;
-                    AB[(size_t)poff[m] + l - m] = make_double2(a, b);
+                    AB[(size_t)legendre_rec(m, L) + l - m] = make_double2(a, b);
                     p2 = p1;
                     p1 = p;
                 }
@@ -313,9 +316,12 @@ static size_t wide_lds(const mtip_ctx* c, int r1, int r2, int nsplit, int* rp) {
     if (c->nt % (2 * nsplit) != 0) return 0;
     const int ntl = c->nt / nsplit;
     if (nsplit > 1 && (ntl / 2) % 32 != 0) return 0;                   // whole 32-theta chunks per workgroup
-    const size_t fixed = (nsplit > 1 ? 0 : (size_t)c->np) + (size_t)ntl * c->nm + c->npairs;
-    // the transpose buffer aliases the coefficient block: shrink the pass until both fit
-    auto bytes = [&](int v) { return (fixed + std::max((size_t)c->nlm, (size_t)v * r1 * (r2 + 1))) * sizeof(double2); };
+    // twiddles, spectra, cos(theta) of the workgroup's theta pairs (doubles)
+    const size_t fixed = (nsplit > 1 ? 0 : (size_t)c->np) + (size_t)ntl * c->nm + (size_t)(ntl / 2 + 1) / 2;
+    // the transpose buffer aliases the records of the synthesis (recurrence and shell coefficients, zero padded, with the
+    // loop's read-ahead: k_sht_legendre.h): shrink the pass until both fit
+    const size_t recs = (size_t)legendre_lds_entries(c->L);
+    auto bytes = [&](int v) { return (fixed + std::max(recs, (size_t)v * r1 * (r2 + 1))) * sizeof(double2); };
     *rp = largest_even_divisor_le(ntl, std::min(SW_THREADS / r2, SW_THREADS / r1));
     while (*rp >= 2 && bytes(*rp) > SHT_WIDE_LDS_MAX) *rp = largest_even_divisor_le(ntl, *rp - 2);
     return *rp >= 2 ? bytes(*rp) : 0;
@@ -340,10 +346,10 @@ static void plan_chain(const mtip_ctx* c, int r1, int r2, ShtPlan& p) {
     }
     if (p.chain == SHT_CHAIN_OFF) return;
     // every wave owns 64 / R2 rows at a time and a transpose buffer for them; it, the panel staging and the groups' partial sums
-    // at the end alias the coefficient block
+    // at the end alias the records of the synthesis (recurrence and shell coefficients, zero padded, with the loop's read-ahead)
     const size_t tb = (size_t)(SW_THREADS / 64) * (64 / r2) * r1 * (r2 + 1);
-    const size_t fixed = (size_t)c->np + (size_t)c->nt * c->nm + c->npairs;
-    p.chain_lds = (fixed + std::max(std::max((size_t)c->nlm, tb), (size_t)SW_THREADS * p.chain_maxi * 2)) * sizeof(double2);
+    const size_t fixed = (size_t)c->np + (size_t)c->nt * c->nm + (size_t)(c->nt / 2 + 1) / 2;     // twiddles, spectra, cos(theta)
+    p.chain_lds = (fixed + std::max(std::max((size_t)legendre_lds_entries(c->L), tb), (size_t)SW_THREADS * p.chain_maxi * 2)) * sizeof(double2);
     if (p.chain_lds > SHT_WIDE_LDS_MAX) p.chain = SHT_CHAIN_OFF;
 }
 

@@ -82,20 +82,29 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     const int nlm = (L + 1) * (L + 1);
     double2* twN = sm;                              // N
     double2* Gs = sm + N;                           // nt * nm        spectra: row 2j = theta_j, 2j+1 = its mirror
-    double2* ABs = Gs + (size_t)nt * nm;            // npairs         recurrence coefficients
-    double2* cl = ABs + npairs;                     // nlm            (Legendre phase)
-    double2* Bm = cl;                               // nw * RW * R1 * AS   the waves' transpose buffers (both directions); at the end the groups' partial sums
+    double* cos_s = reinterpret_cast<double*>(Gs + (size_t)nt * nm);   // nt / 2   cos(theta) (read where the shell has several theta chunks)
+    double2* rec = Gs + (size_t)nt * nm + (nt / 2 + 1) / 2;            // records of the Legendre synthesis (k_sht_legendre.h)
+    double2* Bm = rec;                              // nw * RW * R1 * AS   the waves' transpose buffers (both directions); at the end the groups' partial sums
     const int tid = threadIdx.x;
     const long long shell = blockIdx.x;
     const int q = (int)(shell % Nq);
     const double2* csrc = a.coeff + (size_t)shell * nlm;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
     CHAIN_STAMP(0)
-    LegendreStart ls;
-    legendre_prefetch_first(ls, a.P, nt, L, nt >> 1, 0, wave, tid & 63);
-    for (int e = tid; e < N; e += blockDim.x) sm[e] = a.twN_g[e];
-    for (int e = tid; e < npairs; e += blockDim.x) ABs[e] = a.AB[e];
-    for (int e = tid; e < nlm; e += blockDim.x) cl[e] = csrc[e];
+    // Everything the workgroup reads from global memory before its FFT passes is requested here, at once, and waited for once in
+    // front of the staging barrier: the start values of the wave's Legendre items and cos(theta) of the lane (registers), then the
+    // twiddles, the recurrence table and the shell's coefficients (LDS), then -- youngest, so that the wait in front of the
+    // staging stores does not cover them -- the (l, m) of the closing sums and the epilogue operands of the wave's first group.
+    // LQ items per wave are held; the L = 32 plan (n_theta = 64: one chunk of 32 theta pairs, 17 items on 8 waves) never refills.
+    constexpr int LQ = 3;
+    constexpr bool L32 = LC == 32;
+    static_assert(!L32 || ((LC + 2) / 2 + SW_THREADS / 64 - 1) / (SW_THREADS / 64) <= LQ, "start-value queue");
+    // (the restart's byte of add_mask is a vector load the compiler wants in a scalar register at once: the oldest request, held
+    // in its vector register until the staging has waited anyway, costs no wait of its own)
+    unsigned add_m = 0;
+    if (EPI == EPI_REAL_UPDATE && a.re.add_mask != nullptr) add_m = a.re.add_mask[shell / Nq];
+    LegendreStart<LQ> ls;
+    legendre_prefetch<LQ, L32>(ls, a.P, a.cost, nt, L, nt >> 1, 0, wave, nw, tid & 63);
     long long dst_shell = shell;
     if (a.slot != nullptr && a.which >= 0) dst_shell += (long long)a.slot[(shell / Nq) * SL_N + a.which] * B * Nq;
     double2* gdst = a.grid + (size_t)dst_shell * nt * N;
@@ -140,15 +149,16 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     const bool role1 = SPLIT || lane < S1;
     const int r1l = (t1 / R1) % RW, k1 = t1 % R1;
     // epilogue operands of a lane's step-2 outputs in group g (previous density / F: R1 values, the packed masks: one load),
-    // requested a group ahead: those of the wave's first group before the Legendre synthesis (which touches no global memory),
-    // those of the next group as soon as the epilogue has consumed its own
+    // requested a group ahead: those of the wave's first group behind the staging loads (branch-free, from a clamped row: a branch
+    // here would make the wait in front of the staging stores cover them); the Legendre synthesis touches no global memory, so
+    // they are first waited for in the epilogue.  Those of the next group as soon as the epilogue has consumed its own.
     constexpr bool HAS_PRE = EPI == EPI_MODULUS || EPI == EPI_REAL_UPDATE;
     double2 pre[HAS_PRE ? R1 : 1];
     unsigned pre_m = 0;
     double pre_w = 0.0;                                     // theta weight of the error integral of this lane's row
-    auto load_pre = [&](int g) {
-        const int rr = g * RW + r2l;
-        if (HAS_PRE && g < n_grp && rr < nt) {
+    auto load_pre = [&](int g, auto first) {
+        const int rr = first ? min(g * RW + r2l, nt - 1) : g * RW + r2l;
+        if (HAS_PRE && (first || (g < n_grp && rr < nt))) {
             const int th = rr >> 1;
             const int row = (rr & 1) ? (nt - 1 - th) : th;
 #pragma unroll
@@ -166,17 +176,25 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     // (l, m) of this thread's pairs in the Legendre sums: loaded here, used 40 k cycles later (a global round trip at that point
     // was most of the closing loop)
     int my_lm[MAXI];
+    // the scalars of the epilogue: fetched on this side of the barrier, so that no scalar load is in flight next to the LDS reads
+    // of the synthesis loop (their waits are counted, which they can be only with LDS operations alone)
+    const RealFlags rflags = real_flags(a.re.rp, a.re.method);
+    const double wr_q = EPI == EPI_REAL_UPDATE ? a.re.wr[q] : 0.0;
+    legendre_stage<false>(sm, a.twN_g, N, cos_s, a.cost, L32 ? 0 : nt >> 1, rec, a.AB, csrc, nullptr, L, tid, LC > 0 ? SW_THREADS : (int)blockDim.x, [&]() {
 #pragma unroll
-    for (int u = 0; u < MAXI; ++u) my_lm[u] = CHK ? a.lmc[u * 256 + tg] : a.lmtab[min(tg + u * gsz, npairs - 1)];
+        for (int u = 0; u < MAXI; ++u) my_lm[u] = CHK ? a.lmc[u * 256 + tg] : a.lmtab[min(tg + u * gsz, npairs - 1)];
+        // (vmcnt counts in order: requested in front of the staging loads, these made the staging stores wait for them)
+        load_pre(wave, std::true_type());
+    });
+    if (EPI == EPI_REAL_UPDATE) {
+        unsigned z0 = 0, z1 = 0, z2 = 0;
+        MTIP_PIN_VGPRS4(add_m, z0, z1, z2)
+    }
+    const bool add_prev = EPI == EPI_REAL_UPDATE && a.re.add_prev && q > 0 && (a.re.add_mask == nullptr || add_m != 0);
     __syncthreads();
     CHAIN_STAMP(1)
-    // (behind the staging copies: vmcnt counts in order, requested before them these loads made the copies wait)
-    load_pre(wave);
-    const RealFlags rflags = real_flags(a.re.rp, a.re.method);
-    const bool add_prev = EPI == EPI_REAL_UPDATE && a.re.add_prev && q > 0 && (a.re.add_mask == nullptr || a.re.add_mask[shell / Nq] != 0);
-    const double wr_q = EPI == EPI_REAL_UPDATE ? a.re.wr[q] : 0.0;
     // ---- Legendre synthesis of every row (k_sht_legendre.h)
-    legendre_synthesis_rows(ls, Gs, cl, ABs, a.P, a.cost, nt, L, nt >> 1, 0, wave, nw, tid & 63);
+    legendre_synthesis_rows<LQ, !L32, L32>(ls, Gs, rec, cos_s, a.P, nt, L, nt >> 1, 0, wave, nw, tid & 63);
     CHAIN_STAMP(2)
     __syncthreads();
     CHAIN_STAMP(3)
@@ -262,7 +280,7 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
                 vv[n1] = v;
             }
         }
-        load_pre(g + nw);
+        load_pre(g + nw, std::false_type());
         // ---- forward phase 1: mirror fold (row 2j = theta_j, 2j+1 = its mirror: R2 lanes apart, same wave), R1-point FFTs, twiddle
 #pragma unroll
         for (int n1 = 0; n1 < R1; ++n1) {

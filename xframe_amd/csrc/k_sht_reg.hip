@@ -455,8 +455,9 @@ __global__ void __launch_bounds__(SR_THREADS) k_sht_inv_reg(const double2* __res
 // wave as the unit of work -- lanes 0-31 = 32 northern thetas for +m, lanes 32-63 = the same thetas for -m, so
 // a wave has one m (uniform trip count, no divergence) and the coefficient c_l,+-m is an LDS broadcast.  Each
 // lane runs the three-term recurrence P_lm = a_lm (x P_l-1,m - b_lm P_l-2,m) for its theta in registers
-// ("LDS-staged Legendre recursion": a_lm, b_lm sit in LDS, the two start values P_mm, P_m+1,m come from the
-// table and are prefetched one item ahead), so the synthesis loop touches no global memory.  Even and odd l-m
+// ("LDS-staged Legendre recursion": a_lm, b_lm and the coefficients sit in LDS as records, the two start values
+// P_mm, P_m+1,m of the wave's first four items are requested at kernel entry and topped up four items ahead,
+// k_sht_legendre.h), so the synthesis loop touches no global memory.  Even and odd l-m
 // accumulate separately (north = E + O, south = E - O).  Items (m, theta chunk) are dealt to the waves in
 // snake order of decreasing length, which balances them to within one column.  Then the spectra of all rows
 // sit in LDS and the two register-FFT steps run over RP rows per pass as in k_sht_inv_reg.  One 512-thread
@@ -480,9 +481,9 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_inv_wide(const double2* __re
     const int ntl = nt / nsplit;                    // rows of this workgroup
     const double2* twN = nsplit > 1 ? twN_g : sm;   // N
     double2* Gs = sm + (nsplit > 1 ? 0 : N);        // ntl * nm       spectra: row 2j = theta_(j0+j), 2j+1 = its mirror
-    double2* ABs = Gs + (size_t)ntl * nm;           // npairs         recurrence coefficients
-    double2* cl = ABs + npairs;                     // nlm            (Legendre phase)
-    double2* Bm = cl;                               // RP * R1 * AS   transpose buffer (FFT passes; reuses cl)
+    double* cos_s = reinterpret_cast<double*>(Gs + (size_t)ntl * nm);   // ntl / 2   cos(theta) of the workgroup's theta pairs
+    double2* rec = Gs + (size_t)ntl * nm + (ntl / 2 + 1) / 2;           // records of the synthesis (k_sht_legendre.h)
+    double2* Bm = rec;                              // RP * R1 * AS   transpose buffer (FFT passes; reuses the records)
     const int tid = threadIdx.x;
     const long long shell = blockIdx.x / nsplit;
     const int split = (int)(blockIdx.x - shell * nsplit);
@@ -493,18 +494,15 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_inv_wide(const double2* __re
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
     const int nth = ntl >> 1;                       // theta pairs of this workgroup, first one j0
     const int j0 = split * nth;
-    // start values P_mm, P_m+1,m of the first item: in flight while the tables are staged
-    LegendreStart ls;
-    legendre_prefetch_first(ls, P, nt, L, nth, j0, wave, tid & 63);
-    if (nsplit == 1)
-        for (int e = tid; e < N; e += blockDim.x) sm[e] = twN_g[e];
-    for (int e = tid; e < npairs; e += blockDim.x) ABs[e] = AB[e];
-    if (coeff_sub != nullptr && q > 0) {                    // ft_stab: IFT(F') - IFT(F) on shells > 0 (misk.py:326-329)
-        const double2* ssrc = coeff_sub + (size_t)shell * nlm;
-        for (int e = tid; e < nlm; e += blockDim.x) cl[e] = csub(csrc[e], ssrc[e]);
-    } else {
-        for (int e = tid; e < nlm; e += blockDim.x) cl[e] = csrc[e];
-    }
+    // start values P_mm, P_m+1,m of the wave's first items: in flight while the tables are staged; the tables with every load
+    // of a thread in flight at once
+    constexpr int NQ = 4;
+    LegendreStart<NQ> ls;
+    legendre_prefetch<NQ, false>(ls, P, cost, nt, L, nth, j0, wave, nw, tid & 63);
+    if (coeff_sub != nullptr && q > 0)                      // ft_stab: IFT(F') - IFT(F) on shells > 0 (misk.py:326-329)
+        legendre_stage<true>(sm, twN_g, nsplit == 1 ? N : 0, cos_s, cost + j0, nth, rec, AB, csrc, coeff_sub + (size_t)shell * nlm, L, tid, (int)blockDim.x, []() {});
+    else
+        legendre_stage<false>(sm, twN_g, nsplit == 1 ? N : 0, cos_s, cost + j0, nth, rec, AB, csrc, nullptr, L, tid, (int)blockDim.x, []() {});
     long long dst_shell = shell;
     if (slot != nullptr && which >= 0) dst_shell += (long long)slot[(shell / Nq) * SL_N + which] * B * Nq;
     double2* gdst = grid + (size_t)dst_shell * nt * N;
@@ -525,7 +523,7 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_inv_wide(const double2* __re
     }
     __syncthreads();
     // ---- Legendre synthesis of every row: P_lm(theta) by the three-term recurrence in l (registers only)
-    legendre_synthesis_rows(ls, Gs, cl, ABs, P, cost, nt, L, nth, j0, wave, nw, tid & 63);
+    legendre_synthesis_rows<NQ, true, false>(ls, Gs, rec, cos_s, P, nt, L, nth, j0, wave, nw, tid & 63);
     __syncthreads();
     const int n_pass = ntl / RP;
     for (int pass = 0; pass < n_pass; ++pass) {

@@ -130,7 +130,7 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     A(dev_alloc(c, &c->d_poff, L + 2));
     c->npairs = (L + 1) * (L + 2) / 2;
     A(dev_alloc(c, &c->d_PT, (size_t)(c->nt / 2 + 1) * c->npairs));
-    A(dev_alloc(c, &c->d_AB, (size_t)c->npairs));
+    A(dev_alloc(c, &c->d_AB, (size_t)c->npairs + L + 1));           // one zero entry behind l = L of every order (k_sht_legendre.h)
     A(dev_alloc(c, &c->d_lmtab, c->npairs));
     A(dev_alloc(c, &c->d_PTc, (size_t)(c->nt / 2 + 1) * 768));
     A(dev_alloc(c, &c->d_lmc, 768));

@@ -305,7 +305,7 @@ struct mtip_ctx {
     // tables
     DevBuf<double> d_cost, d_gw, d_P, d_r, d_q;
     DevBuf<int> d_poff;
-    DevBuf<double2> d_AB;                          // (npairs) three-term recurrence coefficients (a_lm, b_lm), (l,m)-major
+    DevBuf<double2> d_AB;                          // (npairs + L + 1) three-term recurrence coefficients (a_lm, b_lm) in record order (k_sht_legendre.h)
     DevBuf<double> d_PT;                           // (nt/2, npairs) theta-major Legendre table (fused SHT)
     DevBuf<double> d_PTc;                          // (nt/2, 768) the same table in the chunk layout of k_sht_chain's Legendre sums
     DevBuf<int> d_lmc;                             // (768) l | m << 8 of slot u * 256 + t, -1: none
