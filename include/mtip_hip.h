@@ -308,6 +308,33 @@ int mtip_op_symmetric_eig(mtip_ctx* ctx, int n, int n_mat, const double* A, doub
 int mtip_op_cc_to_deg2(mtip_ctx* ctx, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
                        const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
                        mtip_cdouble* b_out);
+/* The same step for MASKED data (csrc/k_extract_lsq.h); mtip_op_cc_to_deg2 above stays the unmasked operator.
+ * mtip_op_cc_prepare_masked: modify_cross_correlation (235-289) with a mask.  cc, cc_out (n_q, n_q, n_delta) float64; cc_mask,
+ * mask_out the same shape, uint8, 1 = keep; the outputs must not alias the inputs.  flags, in the reference's order:
+ *   MTIP_CC_SUBTRACT_AVERAGE, MTIP_CC_PI_PERIODICITY (values as above, mask' = mask | roll(mask, n/2)), MTIP_CC_Q1Q2_SYMMETRIC
+ *   (masked mean of C(q2, q1, -Delta) and C(q1, q2, Delta), mathLibrary.py:1346-1351; mask' = either valid),
+ *   MTIP_CC_INTERPOLATE_MASKED (335-351; needs phis (n_delta)): per row with a valid sample every masked one becomes the linear
+ *   interpolation between its nearest valid neighbours in index order; rows without a valid sample keep their values; mask_out is
+ *   all 1 afterwards (287).  status[0] counts the rows that have a masked sample outside their valid ones (scipy's interp1d raises
+ *   ValueError there; such samples keep their values and the caller must not use the result), status[1] is the first such pair
+ *   (q1 n_q + q2; INT32_MAX when there is none).
+ * mtip_op_cc_lstsq_deg2: ccd_to_deg2_invariant_3d_least_squares (452-517, 76-97).  Per pair B = argmin |F[valid] B - cc[valid]|_2,
+ *   F[Delta, k] = P_{orders[k]}(cos t1 cos t2 + sin t1 sin t2 cos Delta) / 4 pi, by Householder reflections (no normal
+ *   equations).  orders (n_orders) int32, strictly increasing, <= 127; cos_sin_theta (2, n_q): cos and sin of theta_q =
+ *   ewald_sphere_theta_pi, and cos_delta (n_delta) = cos(phis), both as the host library rounds them (dP_l/dx reaches l (l+1) / 2:
+ *   the tables are inputs so that F is the reference's to the last bit, which the kernel's recurrence then keeps);
+ *   b_out (orders[n_orders - 1] + 1, n_q, n_q) complex128, the orders that are not listed as zeros; n_valid (n_q, n_q) int32;
+ *   rcond (n_q, n_q): min |r_kk| / max |r_kk| of the triangle, 0 for a pair with fewer valid samples than orders.  A pair with
+ *   rcond = 0 (no valid sample among them, 515-516) gets zeros; rank deficiency is the caller's to reject.
+ * Both: n_q <= 4096, n_delta <= 4096, at most 64 orders, else MTIP_EINVAL with a message and untouched outputs; every buffer may
+ * be host memory or memory of the context's device (a host array gets device scratch: MTIP_ENOMEM with a message if that fails). */
+#define MTIP_CC_INTERPOLATE_MASKED 8u
+int mtip_op_cc_prepare_masked(mtip_ctx* ctx, int n_q, int n_delta, uint32_t flags, const double* cc, const uint8_t* cc_mask,
+                              const double* average_intensity, const uint8_t* bad_angles, const double* phis, double* cc_out,
+                              uint8_t* mask_out, int32_t* status);
+int mtip_op_cc_lstsq_deg2(mtip_ctx* ctx, int n_q, int n_delta, int n_orders, const int32_t* orders, const double* cc,
+                          const uint8_t* cc_mask, const double* cos_sin_theta, const double* cos_delta, mtip_cdouble* b_out, int32_t* n_valid,
+                          double* rcond);
 
 /* ---- correlate: polar patterns -> averaged two-point cross-correlation C(q1, q2, Delta) (csrc/k_correlate.h) ----------------
  * The first stage of the fxs chain (xframe/projects/fxs/correlate.py:401-452, 347-355, 249-270 and all of

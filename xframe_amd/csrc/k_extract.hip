@@ -853,6 +853,8 @@ extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_ord
     return MTIP_OK;
 }
 
+// ---- masked cross-correlation data: modify_cross_correlation with a mask, and B_l by least squares ----------------------
+#include "k_extract_lsq.h"
 // ---- patterns -> cross-correlation (the stage in front of the one above) -----------------------------------------------
 #include "k_correlate.h"
 // ---- detector frames -> patterns (the stage in front of that one) ------------------------------------------------------

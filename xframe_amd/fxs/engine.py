@@ -389,6 +389,92 @@ class Engine:
                                              _lib.ptr(avg), _lib.ptr(bad), _lib.ptr(leg), p_out))
         return out
 
+    # ------------------------------------------------------------------ extract on masked data (fxs_invariant_tools.py:235-289, 335-351, 452-517)
+    def _cc_pair(self, name, cc, cc_mask):
+        """cc float64 and cc_mask bool / uint8 (Nq, Nq, n_delta): both numpy arrays, or both tensors on this engine's device"""
+        on_device = not isinstance(cc, np.ndarray) and hasattr(cc, 'data_ptr')
+        if on_device:
+            import torch
+            if cc.dtype != torch.float64 or not cc.is_cuda or not hasattr(cc_mask, 'data_ptr') or not cc_mask.is_cuda:
+                raise TypeError('%s: tensors must be float64 data and a bool / uint8 mask, both on the GPU' % name)
+            cc = cc.contiguous()
+            cc_mask = cc_mask.contiguous().view(torch.uint8) if cc_mask.dtype == torch.bool else cc_mask.contiguous()
+            if cc_mask.dtype != torch.uint8:
+                raise TypeError('%s: the mask tensor must be bool or uint8' % name)
+        else:
+            cc = np.asarray(cc)
+            cc = _lib.as_f64(cc.real if np.iscomplexobj(cc) else cc)
+            cc_mask = _lib.as_u8(np.asarray(cc_mask, dtype=bool))
+        if cc.ndim != 3 or cc.shape[0] != cc.shape[1] or tuple(cc_mask.shape) != tuple(cc.shape):
+            raise ValueError('%s: cc and cc_mask must both have shape (Nq, Nq, n_delta), got %r and %r'
+                             % (name, tuple(cc.shape), tuple(cc_mask.shape)))
+        return on_device, cc, cc_mask
+
+    def cc_prepare_masked(self, cc, cc_mask, average_intensity=None, bad_angles=None, q1q2_symmetric=False, interpolate_phis=None):
+        """mtip_op_cc_prepare_masked: modify_cross_correlation with a mask.  cc (Nq, Nq, n_delta) float64 and cc_mask (same shape,
+        True = keep) as numpy arrays, or as tensors on this engine's device (then the results stay on it).  average_intensity
+        (Nq): subtract_average_intensity; bad_angles (n_delta) bool: pi_periodicity; interpolate_phis (n_delta): interpolate_masked
+        on these abscissae.  Returns (cc', mask' (bool), status) with status = (rows that cannot be interpolated, first such
+        pair q1 Nq + q2): the caller must raise when status[0] != 0."""
+        on_device, cc, cc_mask = self._cc_pair('cc_prepare_masked', cc, cc_mask)
+        nq, nd = int(cc.shape[0]), int(cc.shape[2])
+        flags = 0
+        avg = bad = phis = None
+        if average_intensity is not None:
+            avg = _lib.as_f64(average_intensity)
+            assert avg.shape == (nq,), avg.shape
+            flags |= 1
+        if bad_angles is not None:
+            bad = _lib.as_u8(np.asarray(bad_angles, dtype=bool))
+            assert bad.shape == (nd,), bad.shape
+            flags |= 2
+        if q1q2_symmetric:
+            flags |= 4
+        if interpolate_phis is not None:
+            phis = _lib.as_f64(interpolate_phis)
+            assert phis.shape == (nd,), phis.shape
+            flags |= 8
+        status = np.zeros(2, np.int32)
+        if on_device:
+            import torch
+            out, mout = torch.empty_like(cc), torch.empty_like(cc_mask)
+            ptrs = (self._tp(cc), self._tp(cc_mask), self._tp(out), self._tp(mout))
+        else:
+            out, mout = np.empty_like(cc), np.empty_like(cc_mask)
+            ptrs = (_lib.ptr(cc), _lib.ptr(cc_mask), _lib.ptr(out), _lib.ptr(mout))
+        self._ck(self.lib.mtip_op_cc_prepare_masked(self.ctx, nq, nd, flags, ptrs[0], ptrs[1], _lib.ptr(avg), _lib.ptr(bad), _lib.ptr(phis),
+                                                    ptrs[2], ptrs[3], _lib.ptr(status)))
+        mout = mout.view(torch.bool) if on_device else mout.view(bool)
+        return out, mout, (int(status[0]), int(status[1]))
+
+    def cc_lstsq_deg2(self, cc, cc_mask, orders, thetas, phis):
+        """mtip_op_cc_lstsq_deg2: per pair the least-squares fit of cc[q1, q2, valid] to sum_k B_k P_orders[k](x(Delta)) / 4 pi,
+        x = cos t1 cos t2 + sin t1 sin t2 cos Delta.  orders: strictly increasing ints (at most 64); thetas (Nq):
+        ewald_sphere_theta_pi of the shells; phis (n_delta).  Their cosines and sines are taken here with numpy, as the reference
+        takes them (fxs_invariant_tools.py:95).  Returns (B (max(orders) + 1, Nq, Nq)
+        complex128 with the orders that are not listed as zeros, n_valid (Nq, Nq) int32, rcond (Nq, Nq)), numpy arrays or tensors as
+        the input is.  Rank deficiency is not solved: see ``extract.masked_cross_correlation_to_deg2_invariant``."""
+        on_device, cc, cc_mask = self._cc_pair('cc_lstsq_deg2', cc, cc_mask)
+        nq, nd = int(cc.shape[0]), int(cc.shape[2])
+        orders = np.ascontiguousarray(orders, dtype=np.int32)
+        thetas, phis = np.asarray(thetas, dtype=float), np.asarray(phis, dtype=float)
+        if orders.ndim != 1 or orders.size < 1 or thetas.shape != (nq,) or phis.shape != (nd,):
+            raise ValueError('cc_lstsq_deg2: orders (n_orders >= 1), thetas (Nq) and phis (n_delta) do not fit cc %r' % (tuple(cc.shape),))
+        cth, phis = _lib.as_f64(np.stack([np.cos(thetas), np.sin(thetas)])), _lib.as_f64(np.cos(phis))
+        shape = (int(max(orders.max(), 0)) + 1, nq, nq)
+        if on_device:
+            import torch
+            out = torch.empty(shape, dtype=torch.complex128, device=cc.device)
+            nv = torch.empty((nq, nq), dtype=torch.int32, device=cc.device)
+            rc = torch.empty((nq, nq), dtype=torch.float64, device=cc.device)
+            ptrs = tuple(self._tp(t) for t in (cc, cc_mask, out, nv, rc))
+        else:
+            out, nv, rc = np.empty(shape, complex), np.empty((nq, nq), np.int32), np.empty((nq, nq))
+            ptrs = tuple(_lib.ptr(t) for t in (cc, cc_mask, out, nv, rc))
+        self._ck(self.lib.mtip_op_cc_lstsq_deg2(self.ctx, nq, nd, int(orders.size), _lib.ptr(orders), ptrs[0], ptrs[1], _lib.ptr(cth),
+                                                _lib.ptr(phis), ptrs[2], ptrs[3], ptrs[4]))
+        return out, nv, rc
+
     # ------------------------------------------------------------------ rotational alignment (average.py:920-960)
     def _so3_setup(self):
         if not getattr(self, '_so3_ready', False):

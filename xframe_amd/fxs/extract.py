@@ -206,6 +206,186 @@ def cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
     return b, np.ones(b.shape[1:], dtype=bool)
 
 
+# ---- masked cross-correlation data ------------------------------------------------------------------------------------------------
+# fxs_invariant_tools.py:100-232 (the cc_mask generators), 235-289 with a mask, 335-351 (interpolate), 452-517 (lstsq).  The function
+# above stays the unmasked operator and keeps refusing these options; extract_from_cross_correlation sends a data set whose settings
+# ask for a mask, for lstsq or for interpolate_masked here.  The masks are settings-derived tables computed once per data set (numpy);
+# the arithmetic on C runs in the two kernels of csrc/k_extract_lsq.h.
+_MASKED_MODES = ('back_substitution', 'lstsq')
+_LSTSQ_RCOND_MIN = 1e-12               # about one decade above LAPACK's own cut eps max(M, N) (2e-13 .. 9e-13 for M = 1024 .. 4096)
+
+
+def _true_cc_mask(data_grid):                                                                          # 136-139
+    return np.ones((len(data_grid['qs']),) * 2 + (len(data_grid['phis']),), dtype=bool)
+
+
+def _ewald_shifted_angles(data_grid, wavelength):
+    """what pixel_arc_cc_mask reads of cartesian_to_spherical(spherical_to_cartesian(grid) - (0, 0, 2 pi / lambda)) on the
+    uniform_dependent grid (q, theta_q, phi) (115-118; mathLibrary.py:629-698, gridLibrary.py:959-1016): theta of every shell at the
+    first phi, and phi along the SECOND shell (sic, 122: index 1)"""
+    qs, thetas, phis = (np.asarray(data_grid[k], dtype=float) for k in ('qs', 'thetas', 'phis'))
+    r, theta, phi = qs[:, None], thetas[:, None], phis[None, :]
+    xy = r * np.sin(theta)
+    x, y, z = np.cos(phi) * xy, np.sin(phi) * xy, r * np.cos(theta) + 0 * phi
+    z = z - 2 * np.pi / wavelength
+    rr = np.sqrt(np.square(x) + np.square(y) + np.square(z))
+    new_theta = np.zeros(rr.shape)
+    nz = rr != 0
+    new_theta[nz] = np.arccos(z[nz] / rr[nz])
+    new_phi = np.arctan2(y, x)
+    new_phi = np.where(new_phi < 0, new_phi + 2 * np.pi, new_phi)
+    return new_theta[:, 0], new_phi[1, :]
+
+
+def _pixel_arc_cc_mask(data_grid, d):                                                                  # 100-135
+    ewald_r = 2 * np.pi / d['xray_wavelength']
+    ew_theta, ew_phi = _ewald_shifted_angles(data_grid, d['xray_wavelength'])
+    ct, st = np.cos(ew_theta), np.sin(ew_theta)
+
+    def arc(cos_phi):
+        return np.abs(ewald_r * np.arccos(ct[:, None, None] * ct[None, :, None] + st[:, None, None] * st[None, :, None] * cos_phi[None, None, :]))
+    r_pixel_size = 2 * np.pi / d['pixel_size']
+    mask = arc(np.cos(ew_phi)) > r_pixel_size
+    if d['mask_at_pi']:
+        mask = mask & (arc(np.cos(ew_phi - np.pi)) > r_pixel_size)
+    return mask
+
+
+def _pixel_custom_cc_mask(data_grid, d):                                                               # 140-171
+    n_phis, n_qs = len(data_grid['phis']), len(data_grid['qs'])
+    n = int(n_phis * d['n_masked_pixels_phi'])
+    nq = int(n_qs * d['n_masked_pixels_q'])
+    pi_index = int(n_phis / 2)
+    ids = list(range(n)) + list(range(n_phis - n, n_phis, 1))
+    if d['mask_at_pi']:
+        ids = list(range(n)) + list(range(pi_index - (n - 1), pi_index + (n - 1), 1)) + list(range(n_phis - n, n_phis, 1))
+    mask = np.full((n_qs, n_qs, n_phis), True)
+    mask[..., ids] = False
+    mask[np.abs(np.arange(n_qs)[:, None] - np.arange(n_qs)[None, :]) > nq] = True
+    return mask
+
+
+def _pixel_flat_cc_mask(data_grid, d):                                                                 # 172-195
+    qs, phis = np.asarray(data_grid['qs'], dtype=float), np.asarray(data_grid['phis'], dtype=float)
+    r_pixel_size = 2 * np.pi / d['pixel_size']
+    with np.errstate(divide='ignore'):
+        phi_min = 2 * np.pi / ((2 * np.pi * qs) / r_pixel_size)
+    phi_mask = (phis[None, :] > phi_min[:, None]) & (phis[None, :] < (2 * np.pi - phi_min[:, None]))
+    if d['mask_at_pi']:
+        phi_mask &= (phis[None, :] > np.pi + phi_min[:, None]) | (phis[None, :] < np.pi - phi_min[:, None])
+    phi_mask = phi_mask[None, :, :] & phi_mask[:, None, :]
+    radial_mask = np.abs(qs[None, :] - qs[:, None]) > r_pixel_size
+    return radial_mask[:, :, None] | phi_mask
+
+
+def _direct_cc_mask(data_grid, d):                                                                     # 218-219
+    return d['mask']
+
+
+_CC_MASK_TYPES = {'direct': _direct_cc_mask, 'none': _true_cc_mask, 'pixel_arc': _pixel_arc_cc_mask, 'pixel_flat': _pixel_flat_cc_mask,
+                  'pixel_custom': _pixel_custom_cc_mask}
+
+
+def cross_correlation_mask(data_grid, datadict):
+    """fxs_invariant_tools.py:221-232: the bool mask (Nq, Nq, n_delta), True = keep, of datadict['cc_mask']['type']; the generator of
+    a type reads the merged dict {**cc_mask[type], **datadict} (231)."""
+    given_type = datadict['cc_mask']['type']
+    generator = _CC_MASK_TYPES.get(given_type, False)
+    if isinstance(generator, bool):
+        raise AssertionError('Given Cross-Correlation mask type "{}" not known. Known types are {}'.format(given_type, _CC_MASK_TYPES.keys()))
+    if given_type == 'none':
+        return generator(data_grid)
+    return generator(data_grid, {**datadict['cc_mask'][given_type], **datadict})
+
+
+def _pair_name(flat, nq):
+    return '(q1, q2) = (%d, %d)' % (flat // nq, flat % nq)
+
+
+def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
+    """fxs_invariant_tools.py:374-422 for data with a cc_mask, for mode 'lstsq' and for modify_cc.interpolate_masked, three dimensions,
+    arithmetic on the device.  metadata as for ``cross_correlation_to_deg2_invariant``; modes: 'back_substitution' (578-645: the masked
+    samples are interpolated first, 605-608; qq_mask = mask'.all(-1)) and 'lstsq' (452-517: a fit over the unmasked samples of every
+    pair; a pair without any gets zeros; qq_mask = mask'.any(-1)).  Returns (b_coeff (max_order + 1, Nq, Nq) complex, qq_mask).
+
+    Raises ValueError where scipy's interp1d does (335-351; scipy 1.15.3): a row that has a valid sample and a masked sample outside
+    the range of its valid ones -- every mask that removes Delta = 0 or the last angle of such a row, and every row with a single
+    valid sample (its other samples lie outside the range of one point).  Rows without a valid sample and rows without a masked one
+    are fine.  Nothing is extrapolated.
+    Raises NotImplementedError for rank-deficient least-squares problems (0 < n_valid < number of orders, or a reciprocal condition
+    estimate min |r_kk| / max |r_kk| of the triangle below 1e-12): LAPACK's gelsd returns the truncated minimum-norm solution there,
+    which this route does not build."""
+    if dim == 2:
+        raise NotImplementedError('masked cross-correlation data with dimensions = 2 (fxs_invariant_tools.py:813-839 drops masked pairs)')
+    if dim != 3:
+        raise ValueError('dim must be 2 or 3')
+    mod = dict(metadata.get('modify_cc') or {})
+    built = _BUILT_MODIFY_CC + ('interpolate_masked',)
+    for key, value in mod.items():
+        if key not in built and not (isinstance(value, (bool, np.bool_)) and not value):
+            raise NotImplementedError('modify_cc.%s (fxs_invariant_tools.py:235-289): built are %s' % (key, ', '.join(built)))
+    mode = metadata.get('mode', False)
+    if mode not in _MASKED_MODES:
+        raise NotImplementedError('bl_extraction_method %r on masked data (fxs_invariant_tools.py:440): built are %s' % (mode, ', '.join(_MASKED_MODES)))
+    orders = np.asarray(metadata['orders'])
+    max_order = int(orders.max())
+    if not np.array_equal(orders, np.arange(max_order + 1)):
+        raise NotImplementedError('orders other than arange(max_order + 1) (the worker passes these, extract.py:134)')
+    n_delta = int(cc.shape[-1])
+    if n_delta < 2 * max_order:
+        raise ValueError('max_order %d cannot be resolved with %d angular points (need n_delta >= 2 max_order)' % (max_order, n_delta))
+    data_grid = metadata['data_grid']
+    qs, phis = np.asarray(data_grid['qs'], dtype=float), np.asarray(data_grid['phis'], dtype=float)
+    nq = len(qs)
+    cc_mask = np.asarray(cross_correlation_mask(data_grid, metadata), dtype=bool)
+    if cc_mask.shape != tuple(cc.shape):
+        raise ValueError('cc_mask has shape %r, the cross-correlation %r' % (cc_mask.shape, tuple(cc.shape)))
+    avg = metadata.get('average_intensity', False)
+    avg = np.asarray(getattr(avg, 'data', avg))
+    kw = {}
+    if mod.get('subtract_average_intensity', False) and avg.ndim == 1:                                    # 245
+        kw['average_intensity'] = avg
+    if mod.get('pi_periodicity', False):
+        assert n_delta % 2 == 0, 'for odd number of phi symmetry enforcing is not possible since phi+pi is not an existing grid point.'
+        assert n_delta == len(phis), 'Cross correlation has {} angular datapoints but only {} angle values are given.'.format(n_delta, len(phis))
+        kw['bad_angles'] = (phis < np.pi / 2) | (phis >= 3 * np.pi / 2)                                  # 267
+    # interpolation: the setting, or implied by back_substitution (605-608; a no-op on a mask that is all true)
+    if mod.get('interpolate_masked', False) or mode == 'back_substitution':
+        kw['interpolate_phis'] = phis
+    cc2, mask2, status = engine.cc_prepare_masked(cc, cc_mask, q1q2_symmetric=bool(mod.get('q1q2_symmetric', False)), **kw)
+    if status[0]:
+        raise ValueError('interpolate_masked: %d rows have a masked sample outside the range of their valid ones, the first at %s; scipy\'s '
+                         'interp1d raises there (fxs_invariant_tools.py:348) and nothing is extrapolated' % (status[0], _pair_name(status[1], nq)))
+    stride = 2 if metadata['assume_zero_odd_orders'] else 1
+    if mode == 'back_substitution':
+        leg = legendre_table(qs, metadata['xray_wavelength'], max_order, stride)
+        b = engine.cc_to_deg2(cc2, max_order, order_stride=stride, dimensions=3, legendre=leg)
+        return np.asarray(b), np.asarray(mask2).all(-1)                                                  # 609
+    extracted = np.arange(0, max_order + 1, stride)                                                      # orders[order_mask], 396-399
+    thetas = np.arccos(qs * metadata['xray_wavelength'] / (4 * np.pi))                                   # 471, physicsLibrary.py:94-95
+    if not np.isfinite(thetas).all():
+        raise ValueError('q * wavelength / (4 pi) > 1: the radial points do not lie on the Ewald sphere of this wavelength')
+    b, n_valid, rcond = engine.cc_lstsq_deg2(cc2, mask2, extracted, thetas, phis)
+    b, n_valid, rcond = np.asarray(b), np.asarray(n_valid), np.asarray(rcond)
+    deficient = (n_valid > 0) & ((n_valid < len(extracted)) | (rcond < _LSTSQ_RCOND_MIN))
+    if deficient.any():
+        first = int(np.flatnonzero(deficient)[0])
+        raise NotImplementedError('lstsq: %d of %d pairs are rank deficient (fewer valid samples than the %d orders, or a reciprocal '
+                                  'condition estimate below %g), the first at %s with %d valid samples, estimate %.1e; LAPACK returns the '
+                                  'truncated minimum-norm solution there (fxs_invariant_tools.py:513), which is not built'
+                                  % (int(deficient.sum()), deficient.size, len(extracted), _LSTSQ_RCOND_MIN, _pair_name(first, nq),
+                                     int(n_valid.flat[first]), float(rcond.flat[first])))
+    if b.shape[0] < max_order + 1:                                                                       # (odd max_order at stride 2)
+        b = np.concatenate([b, np.zeros((max_order + 1 - b.shape[0],) + b.shape[1:], complex)])
+    return b, n_valid > 0                                                                                # 481
+
+
+def _wants_masked_route(dopt):
+    mask_type = (dopt.get('cc_mask') or {'type': 'none'}).get('type', 'none')
+    return (mask_type != 'none' or dopt.get('bl_extraction_method') == 'lstsq'
+            or bool((dopt.get('modify_cc') or {}).get('interpolate_masked', False)))
+
+
 def calc_deg_2_invariant_line_mask(radial_points, max_order, line_specifier, invert=False):
     """extract.py:368-414: the side of one line (or, for a tuple, of two lines: q1 and q2) through two (order, q) points"""
     qs = np.asarray(radial_points, dtype=float)
@@ -317,7 +497,10 @@ def extract_from_cross_correlation(engine, ccd, settings):
     max_order = min(int(opt['max_order']), len(phis) // 2)                                               # 112-119
     meta = {**{k: v for k, v in ccd.items() if k != 'cross_correlation'}, **dopt, 'orders': np.arange(max_order + 1),
             'mode': dopt['bl_extraction_method'], 'average_intensity': avg}                              # 134
-    b_coeff, q_mask = cross_correlation_to_deg2_invariant(engine, cc_arrays['I1I1'], dim, **meta)
+    if _wants_masked_route(dopt):
+        b_coeff, q_mask = masked_cross_correlation_to_deg2_invariant(engine, cc_arrays['I1I1'], dim, **meta)
+    else:
+        b_coeff, q_mask = cross_correlation_to_deg2_invariant(engine, cc_arrays['I1I1'], dim, **meta)
     mask, q_id_limits = calc_deg_2_invariant_masks(dopt, b_coeff.shape, q_mask, qs, max_order)
     b_coeff = apply_invariant_constraints(engine, b_coeff, q_id_limits, dopt.get('bl_enforce_psd', False))
     if dopt.get('modify_cc', {}).get('subtract_average_intensity', False):                               # 160-167
