@@ -335,6 +335,25 @@ int mtip_op_cc_prepare_masked(mtip_ctx* ctx, int n_q, int n_delta, uint32_t flag
 int mtip_op_cc_lstsq_deg2(mtip_ctx* ctx, int n_q, int n_delta, int n_orders, const int32_t* orders, const double* cc,
                           const uint8_t* cc_mask, const double* cos_sin_theta, const double* cos_delta, mtip_cdouble* b_out, int32_t* n_valid,
                           double* rcond);
+/* degree-2 invariants -> cross-correlation, the inverse of mtip_op_cc_to_deg2 and the back half of the worker `simulate_ccd`
+ * (csrc/k_simulate.h; fxs_invariant_tools.py:941-990 deg2_invariant_to_cc_3d, 934-939 deg2_invariant_to_cc_2d).
+ * bl (max_order + 1, n_q, n_q) complex128.
+ *   MTIP_SIM_BACK_SUBSTITUTION, dimensions 3 (979-988, 60-74): C_n = sum_{l >= n} B_l T_l^n(q1) T_l^n(q2) / (2l + 1), n = 0 .. max_order,
+ *     then irfft(C_n 2 max_order, 2 max_order) (the imaginary parts of C_0 and C_max_order are dropped, as numpy does): cc_out
+ *     (n_q, n_q, n_delta) float64 with n_delta = 2 max_order.  legendre_t ((max_order + 1) (max_order + 2) / 2, n_q):
+ *     gsl_sf_legendre_sphPlm(l, n, cos theta_q) at row l (l + 1) / 2 + n, theta_q = ewald_sphere_theta_pi (962).
+ *   MTIP_SIM_BACK_SUBSTITUTION, dimensions 2 (934-939): irfft(B_m size, size) along the order axis, size = n_delta = 2 max_order.
+ *   MTIP_SIM_LSTSQ, dimensions 3 (963-971, 76-97, 992-1001): cc_out (n_q, n_q, n_delta) complex128 (Im B_l is kept),
+ *     C = sum_l B_l / (4 pi) P_l(cos t1 cos t2 + sin t1 sin t2 cos Delta) for the first n_delta / 2 + 1 samples (Delta <= pi), sample
+ *     j = 1 .. n_delta / 2 - 1 also written to n_delta - j (the mirror [1:-1][::-1] of 971; n_delta must be even).  cos_sin_theta
+ *     (2, n_q), cos_delta (n_delta / 2 + 1) as the host library rounds them.
+ * Built for n_q <= 4096, 1 <= max_order <= 128, n_delta <= 4096: beyond that MTIP_EINVAL with a message and untouched outputs.
+ * Every buffer may be host memory or memory of the context's device; host bl / cc_out get device copies, and when these do not fit
+ * the free device memory the call returns MTIP_ENOMEM with the sizes in the message before anything is allocated. */
+#define MTIP_SIM_BACK_SUBSTITUTION 0
+#define MTIP_SIM_LSTSQ 1
+int mtip_op_deg2_to_cc(mtip_ctx* ctx, int n_q, int max_order, int n_delta, int dimensions, int mode, const mtip_cdouble* bl,
+                       const double* legendre_t, const double* cos_sin_theta, const double* cos_delta, void* cc_out);
 
 /* ---- correlate: polar patterns -> averaged two-point cross-correlation C(q1, q2, Delta) (csrc/k_correlate.h) ----------------
  * The first stage of the fxs chain (xframe/projects/fxs/correlate.py:401-452, 347-355, 249-270 and all of

@@ -857,5 +857,7 @@ extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_ord
 #include "k_extract_lsq.h"
 // ---- patterns -> cross-correlation (the stage in front of the one above) -----------------------------------------------
 #include "k_correlate.h"
+// ---- B_l -> cross-correlation (simulate_ccd: the inverse of mtip_op_cc_to_deg2) ------------------------------------------
+#include "k_simulate.h"
 // ---- detector frames -> patterns (the stage in front of that one) ------------------------------------------------------
 #include "k_resample.h"

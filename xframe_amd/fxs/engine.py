@@ -389,6 +389,59 @@ class Engine:
                                              _lib.ptr(avg), _lib.ptr(bad), _lib.ptr(leg), p_out))
         return out
 
+    # ------------------------------------------------------------------ simulate_ccd: B_l -> cross-correlation (fxs_invariant_tools.py:934-1001)
+    def deg2_to_cc(self, bl, mode='back_substitution', dimensions=3, legendre_t=None, cos_sin_theta=None, cos_delta=None):
+        """mtip_op_deg2_to_cc: bl (max_order + 1, Nq, Nq) complex128, a numpy array or a torch tensor on this engine's device (then
+        the cross-correlation comes back as a tensor on it).  mode 'back_substitution': (Nq, Nq, 2 max_order) float64; dimensions 3
+        needs legendre_t ((max_order + 1)(max_order + 2) / 2, Nq) (``simulate_ccd.legendre_table_t``), dimensions 2 is the plain
+        inverse harmonic transform.  mode 'lstsq': (Nq, Nq, 2 len(cos_delta) - 2) complex128 from cos_sin_theta (2, Nq) and
+        cos_delta: cos of the samples Delta <= pi.  An output that does not fit the device raises MemoryError with its size."""
+        if mode not in ('back_substitution', 'lstsq'):
+            raise ValueError('deg2_to_cc: mode %r (back_substitution, lstsq)' % (mode,))
+        on_device = not isinstance(bl, np.ndarray) and hasattr(bl, 'data_ptr')
+        if on_device:
+            import torch
+            if bl.dtype != torch.complex128 or not bl.is_cuda:
+                raise TypeError('deg2_to_cc: a tensor must be complex128 on the GPU')
+            bl = bl.contiguous()
+        else:
+            bl = _lib.as_c128(bl)
+        if bl.ndim != 3 or bl.shape[1] != bl.shape[2]:
+            raise ValueError('deg2_to_cc: bl must have shape (max_order + 1, Nq, Nq), got %r' % (tuple(bl.shape),))
+        L, nq = int(bl.shape[0]) - 1, int(bl.shape[1])
+        lsq = mode == 'lstsq'
+        leg = cst = cd = None
+        if lsq:
+            cst, cd = _lib.as_f64(cos_sin_theta), _lib.as_f64(cos_delta)
+            assert cst.shape == (2, nq) and cd.ndim == 1, (cst.shape, cd.shape)
+            nd = 2 * len(cd) - 2
+        else:
+            nd = 2 * L
+            if dimensions == 3:
+                leg = _lib.as_f64(legendre_t)
+                assert leg.shape == ((L + 1) * (L + 2) // 2, nq), leg.shape
+        # the limits first: the call then writes nothing, and no output of a refused size is allocated here
+        fits = 1 <= L <= 128 and nq <= 4096 and 2 <= nd <= 4096
+        shape = (nq, nq, nd) if fits else (1,)
+        if on_device:
+            out = torch.empty(shape, dtype=torch.complex128 if lsq else torch.float64, device=bl.device)
+            p_in, p_out = self._tp(bl), self._tp(out)
+        else:
+            out = np.empty(shape, complex if lsq else float)
+            p_in, p_out = _lib.ptr(bl), _lib.ptr(out)
+        rc = self.lib.mtip_op_deg2_to_cc(self.ctx, nq, L, nd, int(dimensions), 1 if lsq else 0, p_in, _lib.ptr(leg), _lib.ptr(cst),
+                                         _lib.ptr(cd), p_out)
+        self._ck_memory(rc)
+        return out
+
+    def _ck_memory(self, rc):
+        """MTIP_ENOMEM with sizes in the message is a MemoryError (as ``correlate.Correlator`` reports its accumulator)"""
+        if rc == -4:
+            msg = self.lib.mtip_last_error(self.ctx).decode()
+            if 'GB' in msg:
+                raise MemoryError(msg)
+        self._ck(rc)
+
     # ------------------------------------------------------------------ extract on masked data (fxs_invariant_tools.py:235-289, 335-351, 452-517)
     def _cc_pair(self, name, cc, cc_mask):
         """cc float64 and cc_mask bool / uint8 (Nq, Nq, n_delta): both numpy arrays, or both tensors on this engine's device"""

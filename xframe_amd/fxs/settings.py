@@ -150,6 +150,35 @@ def resolve_correlate(overrides=None):
     return o
 
 
+def simulate_ccd_default_settings():
+    """the keys of the ``fxs simulate_ccd`` worker that the device route reads, with the reference's defaults
+    (``xframe/projects/fxs/settings/simulate_ccd/default_0.01.yaml``; its `command:` entries evaluated).  n_particles is read by the
+    reference (simulate_ccd.py:208) and never used; file names and the vtk switches stay with the caller."""
+    return {
+        'dimensions': 3,
+        'structure_name': 'default',
+        'grid': {'max_q': False, 'oversampling': 8, 'max_order': 63, 'n_phi': 0, 'n_theta': 0, 'n_radial_points': 256},
+        'fourier_transform': {'type': 'midpoint', 'reciprocity_coefficient': 1, 'allow_weight_calculation': True,
+                              'allow_weight_saving': True},
+        'shapes': {'types': ['sphere'] * 6,
+                   'centers': [(0, 0, 0)] + [(140.0, np.pi / 2, phi * 2 * np.pi / 5) for phi in range(5)],
+                   'sizes': [70] * 6,
+                   'densities': [25, 50, 25, 50, 25, 50],
+                   'random_orientation': [False] * 6},
+        'n_particles': 1,
+        'cross_correlation': {'method': 'back_substitution', 'xray_wavelength': 1.23984},
+        'GPU': {'use': True, 'n_gpu_workers': 1},
+        'n_processes': True,
+    }
+
+
+def resolve_simulate_ccd(overrides=None):
+    o = simulate_ccd_default_settings()
+    if overrides:
+        o = deep_update(o, to_plain(overrides))
+    return o
+
+
 def resolve(overrides=None):
     o = default_settings()
     if overrides:
