@@ -50,7 +50,10 @@ enum { MTIP_PRE_NONE = 0, MTIP_PRE_SQUARE = 1 /* |x|^2, misk.py:159-168 */, MTIP
 
 typedef struct {
     int32_t n_radial;      /* Nq: grid.n_radial_points                                   */
-    int32_t l_max;         /* L : grid.max_order                                         */
+    int32_t l_max;         /* L : grid.max_order, 0 <= L <= 128.  L <= 63: everything; 64 <= L <= 128: the transforms
+                              (mtip_op_sht_*, mtip_op_hankel, mtip_op_fourier_transform), mtip_op_deg2_invariants and the
+                              context-independent operators -- the phasing loop (mtip_run*, mtip_shrinkwrap, ..),
+                              mtip_set_projection_matrix, mtip_op_project_* and mtip_op_apply_unknowns return MTIP_ESTATE */
     int32_t n_theta;       /* Gauss-Legendre nodes (shtns_plugin.py:94-101 for defaults) */
     int32_t n_phi;         /* power of two, > 2L                                         */
     int32_t n_batch;       /* restarts resident in this ctx (>=1)                        */

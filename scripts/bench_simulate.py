@@ -1,5 +1,5 @@
 """GPU: B_l -> C(q1, q2, Delta) (Engine.deg2_to_cc, csrc/k_simulate.h) and the worker flow simulate_ccd around it, at 256 x L63 (the
-reference's default), 128 x L32 and, for the operator alone, 512 x L128 (the tutorial's size, beyond the engine's own L <= 63).
+reference's default), 128 x L32 and 512 x L128 (the tutorial's size: the operator here, the flow with --tutorial).
 Per size, after a warm-up, five windows each (median, min .. max):
   (a) the kernel (event bracket of the family `deg2_cc`) with B_l and the output in HBM, for back_substitution and for lstsq on the
       worker's angular grid, beside the time the output write alone (and output + B_l read) takes at 8 TB/s: the floor;
@@ -7,7 +7,10 @@ Per size, after a warm-up, five windows each (median, min .. max):
   (b) the call with host arrays (copies in and out included);
   (c) the numpy restatement of the route on this host, as context, and the device against it;
   (d) the flow simulate_ccd(settings) from the shapes to cc_data (engine set-up included), where the engine takes the size.
-usage: python scripts/bench_simulate.py [--once NQ L MODE]     (--once: one call on a device tensor, for a profiler run)"""
+  (e) --tutorial: the flow at the settings of the reference's settings/simulate_ccd/tutorial.yaml (512 shells, max_order 128, max_q
+      0.322416, its six spheres = the default shapes, back_substitution), run twice (13 GB of device memory, host arrays of 1 GB),
+      the first with the one-off Hankel weights, the second with them cached; beside it the host's Legendre table of the back half.
+usage: python scripts/bench_simulate.py [--once NQ L MODE | --tutorial]     (--once: one call on a device tensor, for a profiler run)"""
 import os
 import sys
 import time
@@ -58,9 +61,30 @@ def windows(e, fn, reps):
     return kern, call
 
 
+TUTORIAL = {'grid': {'max_q': 0.322416, 'n_radial_points': 512, 'max_order': 128},
+            'cross_correlation': {'method': 'back_substitution', 'xray_wavelength': WAVELENGTH}}
+
+
+def tutorial_flow():
+    for i in range(2):
+        t0 = time.perf_counter()
+        res = SIM.simulate_ccd(TUTORIAL)
+        t1 = time.perf_counter()
+        cc = res.cc_data['cross_correlation']['I1I1']
+        print('  (e) simulate_ccd at the tutorial\'s settings, run %d: %.1f s; grid %s, B_l %s, cc %s, integrated intensity %.6e'
+              % (i + 1, t1 - t0, res.density.shape, res.cc_data['deg_2_invariant']['I1I1'].shape, cc.shape, res.integrated_intensity))
+        assert np.isfinite(cc).all()
+    t0 = time.perf_counter()
+    SIM.legendre_table_t(res.cc_data['radial_points'], WAVELENGTH, 128)
+    print('      of which the Legendre table of the back half, on the host in every run: %.1f s (the Hankel weights are computed in the '
+          'first run and kept by hostsetup for the second)' % (time.perf_counter() - t0))
+
+
 def main():
     if not torch.cuda.is_available():
         raise SystemExit('bench_simulate needs a GPU: a timing without one measures nothing')
+    if len(sys.argv) > 1 and sys.argv[1] == '--tutorial':
+        return tutorial_flow()
     e = Engine({'grid': {'n_radial_points': 8, 'max_order': 2}}, None, n_batch=1, max_q=1.0)
     if len(sys.argv) > 1 and sys.argv[1] == '--once':
         nq, L, mode = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]

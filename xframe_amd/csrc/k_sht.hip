@@ -307,7 +307,7 @@ static void fft_launch_dims(const mtip_ctx* c, long long nrows, dim3* grid, dim3
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // The SHT plan (ShtPlan, mtip_internal.h): the only place that reads the geometry or the environment to pick an SHT kernel.
-// Tier k is taken where MTIP_SHT_TIER >= k (default 5) and the geometry fits it; the launchers below and in k_sht_reg.hip,
+// Tier k is taken where MTIP_SHT_TIER >= k (default 5) and the geometry fits it (L > 63: k_sht_big.h or tier 0); the launchers below and in k_sht_reg.hip,
 // k_sht_fused.hip, k_sht_chain.hip only read the plan.
 static constexpr size_t SHT_LDS_MAX = 160 * 1024, SHT_WIDE_LDS_MAX = 158 * 1024;
 
@@ -359,6 +359,17 @@ void plan_sht(mtip_ctx* c) {
     ShtPlan p;
     const int nt = c->nt, np = c->np;
     const size_t z = sizeof(double2);
+    if (c->L > MTIP_LOOP_L_MAX) {
+        // none of the tiers below whatever the cap says: they hold a shell's spectra in LDS and <= 9 (l, m) pairs per thread.
+        // The two-stage kernels pair theta with pi - theta (even n_theta) and their synthesis holds at most 128 pairs; both
+        // directions must fit, as for the tiers below: anything else stays with the generic kernels
+        if (cap >= 1 && nt % 2 == 0 && nt <= SHT_BIG_NT_MAX) {
+            p.fwd = SHT_FWD_BIG;
+            p.inv = SHT_INV_BIG;
+        }
+        c->sht = p;
+        return;
+    }
     // tier 2: register FFTs, taken only where the forward AND the inverse kernel fit
     int r1 = 0, r2 = 0;
     if (cap >= 2 && nt % 2 == 0 && reg_radices(np, &r1, &r2)) {
@@ -432,8 +443,11 @@ int sht_no_kernel(mtip_ctx* c, const char* what, int epi_mode) {
     return MTIP_ESTATE;
 }
 
+#include "k_sht_big.h"
+
 int launch_sht_forward(mtip_ctx* c, const double2* grid, double2* coeff, int prologue, int in_slot) {
     ProfScope ps(c, "sht_fwd");
+    if (c->sht.fwd == SHT_FWD_BIG) return launch_bigl_forward(c, grid, coeff, prologue, in_slot);
     if (c->sht.fwd == SHT_FWD_REG || c->sht.fwd == SHT_FWD_PAIR) {
         launch_sht_forward_reg(c, grid, coeff, prologue, in_slot);
         return MTIP_OK;
@@ -468,6 +482,7 @@ int launch_sht_inverse(mtip_ctx* c, const double2* coeff, double2* grid, const I
     ProfScope ps(c, epi.mode == EPI_REAL_UPDATE ? "sht_inv_real" : (epi.mode == EPI_MODULUS || epi.mode == EPI_MODULUS_FIXED) ? "sht_inv_modulus" : "sht_inv");
     if (c->sht.inv == SHT_INV_REG || c->sht.inv == SHT_INV_WIDE) return launch_sht_inverse_reg(c, coeff, grid, epi);
     if (c->sht.inv == SHT_INV_LDS) return launch_sht_inverse_fused(c, coeff, grid, epi);
+    if (c->sht.inv == SHT_INV_BIG) return launch_bigl_inverse(c, coeff, grid, epi);
     if (epi.mode != EPI_STORE && epi.mode != EPI_MODULUS && epi.mode != EPI_SCALE_SHELL) return sht_no_kernel(c, "generic inverse", epi.mode);
     const long long nrows = (long long)c->B * c->N * c->nt;
     const long long total = nrows * c->nm;

@@ -75,6 +75,15 @@ void mtip_destroy(mtip_ctx* c) {
     delete c;                                            // the device buffers go with it: after the synchronisation above
 }
 
+// The projection kernels (k_proj.hip, k_projr.hip: at most 128 columns per order) and the loop's SHT variants (chained, wide, fused
+// epilogues) are sized for L <= 63; a context beyond it has the transforms, B_l and the context-independent operators only.
+static int require_loop_band_limit(mtip_ctx* c, const char* what) {
+    if (c->L > MTIP_LOOP_L_MAX)
+        FAIL(c, MTIP_ESTATE, std::string(what) + ": the phasing loop and the projection are built for max_order <= 63; this context has L = " +
+                                 std::to_string(c->L) + " and runs the transforms only (DESIGN section 6)");
+    return MTIP_OK;
+}
+
 static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
@@ -91,9 +100,9 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
         g_create_error = "device index out of range";
         return nullptr;
     }
-    if (cfg->n_radial < 2 || cfg->l_max < 0 || cfg->l_max > 63 || cfg->n_batch < 1 || !is_pow2(cfg->n_phi) ||
+    if (cfg->n_radial < 2 || cfg->l_max < 0 || cfg->l_max > 128 || cfg->n_batch < 1 || !is_pow2(cfg->n_phi) ||
         cfg->n_phi < 4 || cfg->n_phi > 512 || cfg->n_phi <= 2 * cfg->l_max || cfg->n_theta <= cfg->l_max) {
-        g_create_error = "invalid cfg: need Nq>=2, 0<=L<=63, n_batch>=1, n_phi a power of two in [4,512] and > 2L, n_theta > L";
+        g_create_error = "invalid cfg: need Nq>=2, 0<=L<=128 (the transforms; the phasing loop and the projection: L<=63), n_batch>=1, n_phi a power of two in [4,512] and > 2L, n_theta > L";
         return nullptr;
     }
     if (hipSetDevice(device) != hipSuccess) {
@@ -292,6 +301,7 @@ int mtip_set_hankel_weights(mtip_ctx* c, const double* w_raw, double fwd_scale, 
 
 int mtip_set_projection_matrix(mtip_ctx* c, int l, const mtip_cdouble* V, int k_l, const uint8_t* radial_mask, int used) {
     CTX_CHECK(c);
+    if (int r = require_loop_band_limit(c, "mtip_set_projection_matrix")) return r;
     if (l < 0 || l > c->L) FAIL(c, MTIP_EINVAL, "order out of range");
     const int kmax = std::min(2 * l + 1, c->N);
     if (k_l < 1 || k_l > kmax) FAIL(c, MTIP_EINVAL, "k_l must be in [1, min(2l+1, Nq)]");
@@ -443,7 +453,9 @@ static int require_transforms(mtip_ctx* c) {
     return MTIP_OK;
 }
 static int require_loop(mtip_ctx* c) {
-    int r = require_transforms(c);
+    int r = require_loop_band_limit(c, "phasing loop");
+    if (r) return r;
+    r = require_transforms(c);
     if (r) return r;
     if (!c->have_radial) FAIL(c, MTIP_ESTATE, "mtip_set_radial_grid has not been called");
     if (!c->have_support) FAIL(c, MTIP_ESTATE, "mtip_set_initial_support has not been called");
@@ -1151,6 +1163,7 @@ int mtip_op_fourier_transform(mtip_ctx* c, const mtip_cdouble* in, mtip_cdouble*
 
 static int op_project(mtip_ctx* c, const mtip_cdouble* Ilm, mtip_cdouble* out, bool real_intensity) {
     CTX_CHECK(c);
+    if (int r = require_loop_band_limit(c, real_intensity ? "mtip_op_project_real_intensity" : "mtip_op_project_coefficients")) return r;
     if (!c->have_radial) FAIL(c, MTIP_ESTATE, "mtip_set_radial_grid has not been called");
     for (int l = 0; l <= c->L; ++l)
         if (!c->have_V[l]) FAIL(c, MTIP_ESTATE, "mtip_set_projection_matrix missing for some order");
@@ -1171,6 +1184,7 @@ int mtip_op_project_real_intensity(mtip_ctx* c, const mtip_cdouble* Ilm, mtip_cd
 
 int mtip_op_apply_unknowns(mtip_ctx* c, const mtip_cdouble* Ilm, const mtip_cdouble* U, mtip_cdouble* out) {
     CTX_CHECK(c);
+    if (int r = require_loop_band_limit(c, "mtip_op_apply_unknowns")) return r;
     for (int l = 0; l <= c->L; ++l)
         if (!c->have_V[l]) FAIL(c, MTIP_ESTATE, "mtip_set_projection_matrix missing for some order");
     if (!Ilm || !U || !out) FAIL(c, MTIP_EINVAL, "null buffer");

@@ -185,9 +185,12 @@ struct ProfEntry { double ms = 0; long long n = 0; };
 // MTIP_SHT_TIER (default 5) is >= k and the geometry fits it:  5 the chained inverse -> forward kernel (k_sht_chain), 4 the wide
 // inverse with the real-space epilogue, 3 the wide inverse (k_sht_inv_wide) and the paired forward (k_sht_fwd_pair), 2 the
 // pass-wise register-FFT kernels (k_sht_fwd_reg / k_sht_inv_reg: both directions must fit), 1 the LDS Stockham kernels
-// (k_sht_fused.hip), 0 the generic FFT + Legendre kernels (k_sht.hip).
-enum { SHT_FWD_GENERIC = 0, SHT_FWD_LDS, SHT_FWD_REG, SHT_FWD_PAIR };
-enum { SHT_INV_GENERIC = 0, SHT_INV_LDS, SHT_INV_REG, SHT_INV_WIDE };
+// (k_sht_fused.hip), 0 the generic FFT + Legendre kernels (k_sht.hip).  Tiers 1-5 are sized for L <= MTIP_LOOP_L_MAX; a context
+// beyond it takes the two-stage kernels of k_sht_big.h (cap >= 1, even n_theta <= SHT_BIG_NT_MAX) or the generic ones, without chain or real_update.
+#define MTIP_LOOP_L_MAX 63              // band limit of the tuned SHT tiers, the projection and with them the phasing loop
+#define SHT_BIG_NT_MAX 256              // k_sht_big.h: the synthesis holds the <= 128 theta pairs of a chunk in eight row tiles
+enum { SHT_FWD_GENERIC = 0, SHT_FWD_LDS, SHT_FWD_REG, SHT_FWD_PAIR, SHT_FWD_BIG };
+enum { SHT_INV_GENERIC = 0, SHT_INV_LDS, SHT_INV_REG, SHT_INV_WIDE, SHT_INV_BIG };
 // k_sht_chain instantiations: run-time tables (THG = 0), table rows in registers (THG = 16, n_phi = 128), and the latter with
 // L = 32 at compile time and the chunk layout of the Legendre sums
 enum { SHT_CHAIN_OFF = 0, SHT_CHAIN_RT, SHT_CHAIN_REGTAB, SHT_CHAIN_L32 };

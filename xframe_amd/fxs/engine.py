@@ -11,13 +11,15 @@ from . import _lib, hostsetup as hs
 from .settings import reciprocity_coefficient, resolve
 
 METHOD_ID = {'HIO': 0, 'ER': 1, 'HIO_non_FXS': 2, 'ER_non_FXS': 3}
+LOOP_MAX_ORDER = 63                   # the phasing loop and the projection (MTIP_LOOP_L_MAX); the transforms alone reach 128
 
 
 class Engine:
     def __init__(self, settings=None, data=None, n_batch=1, device=0, fused=True, lib_path=None,
                  n_radial=None, l_max=None, max_q=None):
         """settings: resolved (or override) settings dict; data: invariants dict (may be None for a
-        transforms-only engine, then ``max_q`` must be given)."""
+        transforms-only engine, then ``max_q`` must be given).  A transforms-only engine takes max_order <= 128 (the transforms, B_l
+        and the context-independent operators); with ``data`` the limit is that of the phasing loop, max_order <= 63."""
         self.lib = _lib.load(lib_path)
         self.device_index = int(device)
         self.emulated = hasattr(self.lib, 'mtip_emulated')          # the CPU emulation of tests/emul: its device memory is host memory
@@ -26,6 +28,10 @@ class Engine:
         g = opt['grid']
         self.N = int(n_radial if n_radial is not None else g['n_radial_points'])
         self.L = int(l_max if l_max is not None else g['max_order'])
+        if data is not None and self.L > LOOP_MAX_ORDER:
+            raise NotImplementedError('max_order = %d with invariants: the phasing loop and the projection are built for max_order <= %d; '
+                                      'beyond it (up to 128) an engine without data runs the transforms only (DESIGN section 6)'
+                                      % (self.L, LOOP_MAX_ORDER))
         self.kappa = float(reciprocity_coefficient(opt['fourier_transform']))
         self.mode = opt['fourier_transform']['type']
         if max_q is None:

@@ -160,7 +160,12 @@ def simulate_ccd(settings=None, density=None, lib_path=None, device=0):
     One fact of the reference is reproduced on purpose: number_of_particles is the constant 1 of InvariantExtractor.__init__ (71); the
     setting n_particles is read (208) and never used, so the scaling of 211-212 multiplies by 1 and cc_data['number_of_particles']
     is 1 whatever the settings say.
-    Sizes beyond the engine's own limits (max_order > 63) raise from the engine's constructor."""
+    Sizes beyond the limits of a transforms-only engine (max_order > 128, n_phi > 512) raise from the engine's constructor.  At the
+    reference's tutorial size (settings/simulate_ccd/tutorial.yaml: 512 shells, max_order 128, a 256 x 512 angular grid) the engine holds
+    about 13 GB of device memory (ten grids of 1.07 GB and the tables), every host array of grid size is 1 GB, and the one-off Hankel
+    weights (hostsetup.hankel_raw_weights(128, 512, ..)) take 32 s of one core on the CPU-only host the code was developed on and about
+    12 s on the host of the MI355X it was measured on, before the first kernel runs: the first call is not hung.  There the first call took
+    26 s and the next, with the weights cached, 14 s (profiles/simulate_timing.txt section 5)."""
     from .engine import Engine
     opt = resolve_simulate_ccd(settings)
     if int(opt['dimensions']) != 3:
