@@ -282,6 +282,9 @@ int mtip_op_grid_phase_ramp(mtip_ctx* ctx, mtip_cdouble* grids, int n, const dou
 int mtip_op_grid_combine(mtip_ctx* ctx, int op, mtip_cdouble* dst, const mtip_cdouble* a, int n, const mtip_cdouble* scalars);
 int mtip_op_prtf(mtip_ctx* ctx, const mtip_cdouble* a1, const mtip_cdouble* a2, const mtip_cdouble* I1, const mtip_cdouble* I2,
                  mtip_cdouble* mean, double* std_dev);
+/* _fsc (resolution_metrics.py:23-33) per shell of two grids: Re sum a1 conj(a2) / sqrt(sum |a1|^2 sum |a2|^2) over the sphere,
+ * 1 where the denominator vanishes; fsc (Nq) */
+int mtip_op_fsc(mtip_ctx* ctx, const mtip_cdouble* a1, const mtip_cdouble* a2, double* fsc);
 
 /* ---- upstream step `extract`: B_l -> V_l (fxs_invariant_tools.py:1079-1131, 1171-1207) -------------------------------
  * eigen-decomposition of n_mat Hermitian n x n matrices A (row-major, only their Hermitian part matters): eigvals (n_mat, n)
@@ -527,6 +530,36 @@ int mtip2d_get_unknowns(mtip2d_ctx* ctx, int batch, mtip_cdouble* unknowns);
 /* best main error per restart (n_batch doubles, reconstruct.py:934-938) and the number of steps done; either may be NULL */
 int mtip2d_get_best_error(mtip2d_ctx* ctx, double* best_error, int64_t* n_steps_done);
 int mtip2d_synchronize(mtip2d_ctx* ctx);
+
+/* ---- averaging of 2-D reconstructions (average.py:123-358, run_2d; csrc/k_average2d.h).  Stacks are (n, n_radial, n_phi)
+ *      complex128 of any length n; every array argument may be host or device memory. ---- */
+/* radial points of the real and the reciprocal grid, and the PolarIntegrator's weights (mathLibrary.py:1254-1262) as factors:
+ * w_r[q] = trapezoid weight x r on the real grid, w_q the same on the reciprocal grid, w_phi the trapezoid weights in phi */
+int mtip2d_avg_set_grid(mtip2d_ctx* ctx, const double* rs, const double* qs, const double* w_r, const double* w_q, const double* w_phi);
+/* out (n, 9) per grid: [0] integral of Re, [1], [2] integrals of Re x, Re y, [3] largest real part among the entries > 0 in
+ * numpy's order on complex numbers (-inf if none), [4], [5] complex sum of those entries, [6] their count, [7] max Re,
+ * [8] min Re */
+int mtip2d_avg_grid_stats(mtip2d_ctx* ctx, const mtip_cdouble* grids, int n, double* out);
+/* out (n, 2) per grid: integrals of |Im F - Im F_ref| and |Im F - Im conj(F_ref)| over the reciprocal grid (average.py:216-217) */
+int mtip2d_avg_inversion_metric(mtip2d_ctx* ctx, const mtip_cdouble* F, int n, const mtip_cdouble* F_ref, double* out);
+/* grids[b] *= exp(-i sign k . c_b) in place, c_b = centers_cartesian[2 b .. 2 b + 1] (fxs_Projections.py:1426-1434) */
+int mtip2d_op_grid_phase_ramp(mtip2d_ctx* ctx, mtip_cdouble* grids, int n, const double* centers_cartesian, double sign);
+/* op 0: dst[b] = conj(a[b]); 1: dst[b] = a[b] / scalars[b]; 2: dst = (sum over b of a[b]) / Re scalars[0];
+ * 3: dst = (sum over b of |a[b]|^2) / Re scalars[0]; 4: dst[b] = (a[b] - Re scalars[0]) / Re scalars[1].
+ * dst: a stack for 0, 1 and 4 (may be a itself), one grid for 2 and 3 */
+int mtip2d_op_grid_combine(mtip2d_ctx* ctx, int op, mtip_cdouble* dst, const mtip_cdouble* a, int n, const mtip_cdouble* scalars);
+/* per-shell curves of one averaged set (a_d = FT of the mean density, a_ft = mean reciprocal density, I_d, I_ft = mean
+ * intensities, real values in complex grids): prtf_mean, prtf_std (4, n_radial) in the order PRTF, PRTF_from_density,
+ * PRTF_from_ft_density, PRTF_ftI (average.py:250-263; resolution_metrics.py:63-79); fsc (n_radial) = _fsc(a_d, a_ft) (23-33) */
+int mtip2d_avg_curves(mtip2d_ctx* ctx, const mtip_cdouble* a_d, const mtip_cdouble* a_ft, const mtip_cdouble* I_d, const mtip_cdouble* I_ft,
+                      mtip_cdouble* prtf_mean, double* prtf_std, double* fsc);
+/* FQCB_2D (resolution_metrics.py:146-187) of two sets of degree-2 invariants, each given as a coefficient table I_n(q) (kind 0:
+ * n_radial rows of ld values, order n in column n < n_orders; B_n(q, q') = I_n(q) conj(I_n(q'))) or as a B_n stack (kind 1:
+ * (n_orders, n_radial, n_radial), ld ignored): orders o_start, o_start + o_step, ... below min(n1, n2); mean, std_dev (n_radial) */
+int mtip2d_avg_fqcb(mtip2d_ctx* ctx, const mtip_cdouble* in1, int kind1, int n1, int ld1, const mtip_cdouble* in2, int kind2, int n2,
+                    int ld2, int o_start, int o_step, double* mean, double* std_dev);
+/* out (n_orders, n_radial, n_radial): B_n(q, q') = I_n(q) conj(I_n(q')) of a coefficient table (fxs_invariant_tools.py:906-914) */
+int mtip2d_op_deg2_from_table(mtip2d_ctx* ctx, const mtip_cdouble* table, int n_orders, int ld, mtip_cdouble* out);
 
 /* ---- timing ----------------------------------------------------------------------------------- */
 /* average duration (ms) and launch count of kernel family `name` ("sht_fwd", "sht_inv", "hankel",

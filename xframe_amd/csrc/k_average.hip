@@ -8,6 +8,7 @@
 //   shift operator            fxs_Projections.py:1419-1444                     -> mtip_op_grid_phase_ramp
 //   sums / scaling / conj     average.py:432-437, 526-536                      -> mtip_op_grid_combine
 //   PRTF                      resolution_metrics.py:62-110                     -> mtip_op_prtf
+//   FSC                       resolution_metrics.py:23-33                      -> mtip_op_fsc
 #include "mtip_internal.h"
 
 #define AV_THREADS 256
@@ -200,6 +201,38 @@ __global__ void __launch_bounds__(AV_THREADS) k_av_prtf(const double2* __restric
     }
 }
 
+// ---- FSC (resolution_metrics.py:23-33): per shell Re sum a1 conj(a2) / sqrt(sum |a1|^2 sum |a2|^2) over the sphere, 1 where the
+//      denominator vanishes
+__global__ void __launch_bounds__(AV_THREADS) k_av_fsc(const double2* __restrict__ a1, const double2* __restrict__ a2, int npts,
+                                                       double* __restrict__ fsc) {
+    __shared__ double rn[AV_THREADS], r1[AV_THREADS], r2[AV_THREADS];
+    const int q = blockIdx.x;
+    const size_t o = (size_t)q * npts;
+    double sn = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = threadIdx.x; i < npts; i += blockDim.x) {
+        const double2 x = a1[o + i], y = a2[o + i];
+        sn += x.x * y.x + x.y * y.y;
+        s1 += cabs2(x);
+        s2 += cabs2(y);
+    }
+    rn[threadIdx.x] = sn;
+    r1[threadIdx.x] = s1;
+    r2[threadIdx.x] = s2;
+    __syncthreads();
+    for (int k = AV_THREADS / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) {
+            rn[threadIdx.x] += rn[threadIdx.x + k];
+            r1[threadIdx.x] += r1[threadIdx.x + k];
+            r2[threadIdx.x] += r2[threadIdx.x + k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double den = sqrt(r1[0] * r2[0]);
+        fsc[q] = den != 0.0 ? rn[0] / den : 1.0;
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------------------------
 #define AV_FAIL(c, code, msg)   \
     do {                        \
@@ -310,6 +343,26 @@ int mtip_op_prtf(mtip_ctx* c, const mtip_cdouble* a1, const mtip_cdouble* a2, co
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = mtip_copy(c, mean, d_out, (size_t)c->N * sizeof(double2), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = mtip_copy(c, std_dev, d_out + 2 * (size_t)c->N, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost);
+    AV_HIP(c, e);
+    AV_HIP(c, hipGetLastError());
+    return MTIP_OK;
+}
+
+int mtip_op_fsc(mtip_ctx* c, const mtip_cdouble* a1, const mtip_cdouble* a2, double* fsc) {
+    if (!c) return MTIP_EINVAL;
+    if (!a1 || !a2 || !fsc) AV_FAIL(c, MTIP_EINVAL, "fsc: null buffer");
+    (void)hipSetDevice(c->device);
+    AV_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t gb = c->G * sizeof(double2);
+    DevView v1(c, a1, gb, true, false), v2(c, a2, gb, true, false);
+    AV_HIP(c, v1.err);
+    AV_HIP(c, v2.err);
+    DevBuf<double> out_buf;
+    AV_HIP(c, out_buf.alloc((size_t)c->N));
+    hipLaunchKernelGGL(k_av_fsc, dim3((unsigned)c->N), dim3(AV_THREADS), 0, c->stream, (const double2*)v1.dev, (const double2*)v2.dev,
+                       c->nt * c->np, (double*)out_buf);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = mtip_copy(c, fsc, out_buf, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost);
     AV_HIP(c, e);
     AV_HIP(c, hipGetLastError());
     return MTIP_OK;

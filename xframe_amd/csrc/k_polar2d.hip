@@ -60,6 +60,9 @@ struct mtip2d_ctx {
     DevBuf<double2> r_deg2ref;                     // (n_used, N, N)
     DevBuf<double> r_deg2norm, r_recw;             // (n_used), (N, n_phi)
     int r_main_type = 0, r_main_n = 1, r_main_items[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // 0 real, 1 deg2, 2 reciprocal l2
+    // ---- averaging (k_average2d.h): r (N), q (N), integrator weights in r (N), in q (N), in phi (n_phi)
+    DevBuf<double> a_tab;
+    bool a_ready = false;
     std::string err;
 };
 
@@ -1568,3 +1571,6 @@ int mtip2d_synchronize(mtip2d_ctx* c) {
 }
 
 }  // extern "C"
+
+// ==== the averaging worker's grid arithmetic for dimensions = 2 (mtip2d_avg_*, mtip2d_op_grid_*) ==================================
+#include "k_average2d.h"

@@ -101,6 +101,7 @@ _SIGNATURES = {
     'mtip_op_grid_phase_ramp': (C.c_int, [c_void, c_void, C.c_int, c_void, C.c_double]),
     'mtip_op_grid_combine': (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, c_void]),
     'mtip_op_prtf': (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    'mtip_op_fsc': (C.c_int, [c_void, c_void, c_void, c_void]),
     'mtip_set_so3_tables': (C.c_int, [c_void, C.c_int, c_void]),
     'mtip_op_so3_correlation': (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void]),
     'mtip_op_rotate_coefficients': (C.c_int, [c_void, c_void, c_void, c_void]),
@@ -144,6 +145,14 @@ _SIGNATURES = {
     'mtip2d_get_unknowns': (C.c_int, [c_void, C.c_int, c_void]),
     'mtip2d_get_best_error': (C.c_int, [c_void, c_void, C.POINTER(C.c_int64)]),
     'mtip2d_synchronize': (C.c_int, [c_void]),
+    'mtip2d_avg_set_grid': (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void]),
+    'mtip2d_avg_grid_stats': (C.c_int, [c_void, c_void, C.c_int, c_void]),
+    'mtip2d_avg_inversion_metric': (C.c_int, [c_void, c_void, C.c_int, c_void, c_void]),
+    'mtip2d_op_grid_phase_ramp': (C.c_int, [c_void, c_void, C.c_int, c_void, C.c_double]),
+    'mtip2d_op_grid_combine': (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, c_void]),
+    'mtip2d_avg_curves': (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    'mtip2d_avg_fqcb': (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void]),
+    'mtip2d_op_deg2_from_table': (C.c_int, [c_void, c_void, C.c_int, C.c_int, c_void]),
     'mtip_op_so3_find_rotation': (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
     'mtip_op_rotate_coefficients_grid': (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_hermitian_eig': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
@@ -222,3 +231,29 @@ def as_f64(a):
 
 def as_u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+class TensorOperands:
+    """What the engines share for operators that work in place on torch tensors (the averaging keeps its batch in HBM and hands
+    ``tensor.data_ptr()`` across the ABI).  Needs ``self.lib`` and ``self.device_index``.
+
+    Ordering rule: a context's stream is created non-blocking, so nothing orders it against the stream torch writes the tensors on
+    (stack, cat, clone, index assignment ... right before an operator call).  Every operator call therefore first waits for torch's
+    current stream of the tensor's device (``_tp``); in the other direction every ``mtip*_op_*`` / ``mtip2d_avg_*`` entry point
+    returns after it has synchronised its own stream, so torch never reads a half-written result."""
+
+    @property
+    def emulated(self):
+        return hasattr(self.lib, 'mtip_emulated')               # the CPU emulation of tests/emul: its device memory is host memory
+
+    def torch_device(self):
+        import torch
+        return torch.device('cpu') if self.emulated else torch.device('cuda', self.device_index)
+
+    @staticmethod
+    def _tp(t):
+        assert t.is_contiguous()
+        if t.is_cuda:
+            import torch
+            torch.cuda.current_stream(t.device).synchronize()
+        return C.c_void_p(t.data_ptr())

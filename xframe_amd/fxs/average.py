@@ -23,6 +23,9 @@ reference does that change its results: ``find_rotation`` flips the angles of th
 list of valid alignments starts with the reference while the list of their errors does not (519-524); and the averaged pair is
 centred before the metrics with a shift operator that works in place (538, fxs_Projections.py:1442), so the saved averaged
 reciprocal density and the 'PRTF' metric see the shifted one.
+
+The second half of the file is the same worker for ``dimensions: 2`` (``run_2d``, 123-358): ``average_reconstructions_2d`` on an
+``Engine2D`` and the kernels of ``csrc/k_average2d.h``.
 """
 import numpy as np
 
@@ -190,6 +193,18 @@ def _normalize(al, d, d_min=False):
     return al.e.t_combine('affine', d[None].contiguous(), [d_min, 1.0 / (float(st[6]) - d_min)])[0]
 
 
+_FQCB_3D_LOGGED = False
+
+
+def _log_fqcb_3d():
+    global _FQCB_3D_LOGGED
+    if not _FQCB_3D_LOGGED:
+        import logging
+        logging.getLogger('xframe_amd').info('resolution_metrics.FQCB does nothing for dimensions = 3 (average.py:567-568 is `pass` '
+                                             'upstream): no FQCB key is added to the result')
+        _FQCB_3D_LOGGED = True
+
+
 def average_reconstructions(engine, reconstructions, errors, opt=None, dist=None, device=None):
     """run_3d (average.py:359-570).  reconstructions: list of (real_density, reciprocal_density) of THIS rank -- numpy arrays, or
     torch tensors already on the engine's device -- errors: their selection errors.  dist: torch.distributed module of an
@@ -316,6 +331,11 @@ def average_reconstructions(engine, reconstructions, errors, opt=None, dist=None
         for name, args in (('PRTF', (a_d, a_ft, i_d, i_f)), ('PRTF_from_density', (a_d, a_d, i_d, i_d)),
                            ('PRTF_from_ft_density', (a_ft, a_ft, i_f, i_f)), ('PRTF_ftI', (a_d, a_d, i_f, i_f))):
             metrics[name], metrics[name + '_std'] = e.t_prtf(*args)       # b = sqrt(I) inside the kernel
+    if o['resolution_metrics'].get('FQCB', False):
+        _log_fqcb_3d()                                                    # average.py:567-568: `pass` upstream, no key is added
+    if o['resolution_metrics'].get('pseudo_FSC', False):                  # 569-573
+        metrics['pseudo_FSC'] = e.t_fsc(ft_avg.contiguous(), average[1].contiguous())
+        metrics['FSC_0.5bit_limit'] = fsc_bit_limit(0.5, e.shape + (3,))
     dmin = o.get('average_normalization_min', False)
     on_dev = bool(o.get('keep_on_device', False))
 
@@ -339,4 +359,221 @@ def average_reconstructions(engine, reconstructions, errors, opt=None, dist=None
         # average.py:479, 520: 0 for the reference, then the position (in this rank's list without the reference) of every valid one
         'average_ids': [0] + [i for i, x in enumerate(loc_err) if x < limit],
         'input_meta': {'scaling_factors': scales}, 'so3_grid': al.soft_grid,
+    }
+
+
+# ---------------------------------------------------------------------------------------------------------------- dimensions = 2
+DEFAULTS_2D = {
+    'center_reconstructions': True, 'use_masks': False, 'normalize_reconstructions': {'use': True, 'mode': 'max'},
+    'pointinvert_reference': False, 'resolution_metrics': {'PRTF': True}, 'selection': {'n_reconstructions': 100},
+    'average_normalization_min': False,
+}
+
+
+def fsc_bit_limit(target_snr, grid_shape):
+    """FSC_bit_limit (resolution_metrics.py:9-21) as written: the points per shell are the product of ALL trailing axes of the grid
+    array -- for the polar grid (Nq, n_phi, 2) that counts the coordinate axis, 2 n_phi -- and the denominator holds
+    2 ** sqrt(x / p), not 2 sqrt(x / p)"""
+    p = np.prod(grid_shape[1:])
+    x = target_snr / 2
+    return (x + 2 * np.sqrt(x / p) + 1 / np.sqrt(p)) / (1 + x + 2 ** np.sqrt(x / p))
+
+
+class Alignment2D:
+    """``Alignment`` for dimensions = 2 (average.py:729-786, 1014-1044) on an ``Engine2D``: centre and shift operators only (there is
+    no rotational alignment in 2-D upstream).  Works on stacks (n, Nq, n_phi) complex128 on the engine's device."""
+
+    def __init__(self, engine2d):
+        import torch
+        self.torch, self.e = torch, engine2d
+        self.dev = engine2d.torch_device()
+
+    def to_device(self, x):
+        t = self.torch
+        if not t.is_tensor(x):
+            x = t.from_numpy(np.ascontiguousarray(x, dtype=np.complex128))
+        return x.to(self.dev, dtype=t.complex128)
+
+    def ft(self, X):
+        return self.e.t_fourier_transform(X)
+
+    def ift(self, X):
+        return self.e.t_fourier_transform(X, True)
+
+    def centers(self, R):
+        """generate_calc_center (misk.py:295-312) with the PolarIntegrator, through cartesian_to_spherical and back as the shift
+        operator reads it (fxs_Projections.py:1430): Cartesian centres (n, 2) and the polar ones (r, phi in [0, 2 pi)), on the host"""
+        m = self.e.t_grid_stats(R)[:, :3]
+        total = np.where(m[:, 0] == 0, 1.0, m[:, 0])
+        cx, cy = m[:, 1] / total, m[:, 2] / total
+        rad, phi = np.hypot(cx, cy), np.arctan2(cy, cx)
+        phi = np.where(phi < 0, phi + 2 * np.pi, phi)
+        return np.stack([rad * np.cos(phi), rad * np.sin(phi)], -1), np.stack([rad, phi], -1)
+
+    def shift_to_center(self, R, F):
+        """assemble_shift_to_center (1014-1027): (IFT(FT(rho) e^{i k c}), F e^{i k c}, c); F is multiplied IN PLACE, as the
+        reference's shift operator does (fxs_Projections.py:1433)"""
+        cart, polar = self.centers(R)
+        return self.ift(self.e.t_phase_ramp(self.ft(R), cart, -1.0)), self.e.t_phase_ramp(F, cart, -1.0), polar
+
+    def point_invert(self, R, F):
+        """average.py:222-223: (IFT(conj(FT(rho))), conj(F))"""
+        return self.ift(self.e.t_combine('conj', self.ft(R))), self.e.t_combine('conj', F)
+
+    def normalize(self, d, d_min=False):
+        """normalize_density (721-727) of one grid: (d - min Re) / (max Re - min Re)"""
+        st = self.e.t_grid_stats(d[None])[0]
+        if isinstance(d_min, bool):
+            d_min = float(st[8])
+        return self.e.t_combine('affine', d[None], [d_min, float(st[7]) - d_min])[0]
+
+
+def averaged_projection_matrices(projection_matrices, average_scaling_factors):
+    """get_averaged_projection_matrices (average.py:90-99)"""
+    out = []
+    for i in range(len(projection_matrices[0])):
+        temp = projection_matrices[0][i] / average_scaling_factors[0] ** 2
+        for j in range(1, len(projection_matrices)):
+            temp = temp + projection_matrices[j][i] / average_scaling_factors[j] ** 2
+        out.append(temp / len(projection_matrices))
+    return out
+
+
+def average_reconstructions_2d(engine2d, reconstructions, errors, opt=None, projection_matrices=None, reconstruction_ids_per_file=None):
+    """run_2d (average.py:123-358) on an ``Engine2D``.  reconstructions: list of (real_density, reciprocal_density) -- numpy arrays,
+    or torch tensors already on the engine's device; errors: their selection errors (the least one names the reference).
+    reconstruction_ids_per_file: lists of positions in `reconstructions` per input file (default: one file with all of them).
+    Returns the reference's result dict for the keys that do not depend on files (``average``, ``resolution_metrics``,
+    ``centered_average``, ``aligned``, ``inversion_metric``, ``input_meta``) as numpy arrays, plus ``reference_arg`` and
+    ``point_inverted``; with ``opt['keep_on_device']`` the grids of ``aligned`` stay torch tensors on the device.
+
+    The batch stays in HBM from the upload to the means; per-reconstruction scalars (centres, scaling factors, the two inversion
+    integrals) come to the host, where the decisions are taken.  Three things the reference does that change its results are kept:
+    numpy's lexicographic ``> 0`` on complex densities in the normalisation (168-180); the averaged pair is centred before the
+    metrics by a shift operator that multiplies its argument in place (246, fxs_Projections.py:1433), so the saved averaged
+    reciprocal density, ``centered_average.reciprocal_density`` and every metric see the shifted one; ``FSC_bit_limit`` as written.
+    ``use_masks`` (154-161) raises NotImplementedError.  ``resolution_metrics.FQCB`` (266-301) cannot run upstream (its first call
+    hands the harmonic transform to ``intensity_to_deg2_invariant`` as ``intensity2``): what is built is its evident intent, see
+    the comment at the branch; ``opt['FQCB_bl_arrays'] = False`` leaves the three (orders, Nq, Nq) arrays out of the result."""
+    import torch as t
+    o = dict(DEFAULTS_2D)
+    o.update(opt or {})
+    e, al = engine2d, Alignment2D(engine2d)
+    n_in = len(reconstructions)
+    if n_in < 2:
+        raise ValueError('average_reconstructions_2d: fewer than 2 reconstructions, nothing to average (average.py:105-107)')
+    metrics_opt = o['resolution_metrics']
+    if metrics_opt.get('FQCB', False) and projection_matrices is None:
+        raise ValueError('resolution_metrics.FQCB needs projection_matrices (average.py:270-271)')
+    errors = np.asarray(errors, dtype=float)
+    R = t.stack([al.to_device(r[0]) for r in reconstructions])
+    F = t.stack([al.to_device(r[1]) for r in reconstructions])
+    # ---- 135-163: centre every reconstruction
+    if o.get('center_reconstructions', False):
+        if o.get('use_masks', False):
+            raise NotImplementedError('use_masks with center_reconstructions for dimensions = 2 (average.py:154-161: the support masks '
+                                      'are shifted and applied to the centred density) is not built')
+        R, F, _ = al.shift_to_center(R, F)
+    # ---- 165-186: normalise
+    scales = np.ones(n_in)
+    norm = o['normalize_reconstructions']
+    if norm.get('use', False) and norm.get('mode') in ('max', 'mean'):
+        st = e.t_grid_stats(R)
+        if norm['mode'] == 'max':
+            # 171: np.max(r[0][r[0] > 0].real), the comparison being numpy's lexicographic one on complex numbers
+            if (st[:, 6] == 0).any():
+                raise ValueError('zero-size array to reduction operation maximum which has no identity (average.py:171: a density without '
+                                 'an entry > 0)')
+            fac = st[:, 3].astype(complex)
+        else:
+            # 178: np.mean of those entries -- complex (nan where there is none); only its real part reaches scaling_factors
+            with np.errstate(invalid='ignore', divide='ignore'):
+                fac = (st[:, 4] + 1j * st[:, 5]) / st[:, 6]
+        scales = np.real(fac).astype(float)
+        R, F = e.t_combine('div', R, fac), e.t_combine('div', F, fac)
+    ids_per_file = [np.arange(n_in)] if reconstruction_ids_per_file is None else reconstruction_ids_per_file
+    scales_per_file = np.ones(len(ids_per_file))
+    for file_id, r_ids in enumerate(ids_per_file):
+        scales_per_file[file_id] = np.mean(scales[np.asarray(r_ids, dtype=int)])
+    # ---- 192-206: the reference is popped from the list
+    ref_arg = int(np.argmin(errors))
+    keep = [i for i in range(n_in) if i != ref_arg]
+    d_ref, F_ref = R[ref_arg].clone(), F[ref_arg].clone()
+    if o.get('pointinvert_reference', False):
+        d, f = al.point_invert(d_ref[None], F_ref[None])
+        d_ref, F_ref = d[0], f[0]
+    # ---- 214-229: point inversion against the reference, decided per reconstruction on the host
+    S_rho, S_F = R[keep].contiguous(), F[keep].contiguous()
+    diffs = e.t_inversion_metric(S_F, F_ref)
+    inverted = diffs[:, 0] > diffs[:, 1]
+    if inverted.any():
+        idx = t.from_numpy(np.flatnonzero(inverted)).to(S_rho.device)
+        d, f = al.point_invert(S_rho[idx], S_F[idx])
+        S_rho[idx], S_F[idx] = d, f
+    A_rho, A_F = t.cat([d_ref[None], S_rho]), t.cat([F_ref[None], S_F])
+    # ---- 232-233: cut to n_reconstructions (113-115: anything but an int means all)
+    n_rec = o['selection'].get('n_reconstructions', 'all')
+    if not isinstance(n_rec, int) or isinstance(n_rec, bool):
+        n_rec = n_in
+    if A_rho.shape[0] >= n_rec:
+        A_rho, A_F = A_rho[:n_rec].contiguous(), A_F[:n_rec].contiguous()
+    n_avg = int(A_rho.shape[0])
+    if n_avg == 0:
+        raise ValueError('average_reconstructions_2d: selection.n_reconstructions leaves nothing to average')
+    # ---- 238-242: the means
+    avg_rho, avg_F = e.t_combine('mean', A_rho, [n_avg]), e.t_combine('mean', A_F, [n_avg])
+    I_ft, I_d = e.t_combine('abs2mean', A_F, [n_avg]), e.t_combine('abs2mean', al.ft(A_rho), [n_avg])
+    # ---- 246: centred BEFORE the metrics; the shift operator works in place on the averaged reciprocal density
+    cen_rho, avg_F_stack, _ = al.shift_to_center(avg_rho[None], avg_F[None])
+    avg_F = avg_F_stack[0]
+    # ---- 248-307
+    metrics = {}
+    want_prtf, want_fsc = bool(metrics_opt.get('PRTF', False)), bool(metrics_opt.get('pseudo_FSC', False))
+    ft_avg = al.ft(avg_rho[None])[0] if (want_prtf or want_fsc or metrics_opt.get('FQCB', False)) else None
+    if want_prtf or want_fsc:
+        mean, std, fsc = e.t_curves(ft_avg, avg_F, I_d, I_ft)
+        if want_prtf:
+            for k, name in enumerate(('PRTF', 'PRTF_from_density', 'PRTF_from_ft_density', 'PRTF_ftI')):
+                metrics[name], metrics[name + '_std'] = mean[k], std[k]
+        if want_fsc:
+            metrics['pseudo_FSC'] = fsc
+            metrics['FSC_0.5bit_limit'] = fsc_bit_limit(0.5, e.shape + (2,))
+    if metrics_opt.get('FQCB', False):
+        # 266-301 as evidently meant (upstream the transform lands in `intensity2` and the branch fails, fxs_invariant_tools.py:872):
+        # B_n of |FT(mean rho)|^2 and of |mean F|^2 through the complex harmonic transform, cut to n_phi // 2 + 1 orders (878-881)
+        n_ord = e.n_phi // 2 + 1
+        I_pair = t.stack([e.t_combine('abs2mean', ft_avg[None], [1]), e.t_combine('abs2mean', avg_F[None], [1])])
+        coeff = e.t_harmonic(I_pair)
+        tab_d, tab_ftd = (coeff[0], n_ord), (coeff[1], n_ord)
+        pr_mat = np.squeeze(np.array(averaged_projection_matrices(projection_matrices, scales_per_file)))
+        tab_t = al.to_device(np.ascontiguousarray(pr_mat.T))
+        for name, a, b, zero in (('FQCB_from_density', tab_d, tab_t, False), ('FQCB_from_ft_density', tab_ftd, tab_t, False),
+                                 ('FQCB_projected_vs_unprojected', tab_ftd, tab_d, False),
+                                 ('FQCB_from_density_with_zero_order', tab_d, tab_t, True),
+                                 ('FQCB_from_ft_density_with_zero_order', tab_ftd, tab_t, True)):
+            metrics[name], metrics[name + '_std'] = e.t_fqcb(a, b, skip_odd_orders=True, include_zero_order=zero)
+        if o.get('FQCB_bl_arrays', True):
+            metrics['FQCB_bl_from_density'] = e.t_deg2_from_table(*tab_d).cpu().numpy()
+            metrics['FQCB_bl_from_ft_density'] = e.t_deg2_from_table(*tab_ftd).cpu().numpy()
+            metrics['FQCB_bl_target'] = e.t_deg2_from_table(tab_t).cpu().numpy()
+    dmin = o.get('average_normalization_min', False)
+    on_dev = bool(o.get('keep_on_device', False))
+
+    def out(x):
+        return x if on_dev else x.cpu().numpy()
+
+    def host(x):
+        return x.cpu().numpy()
+    return {
+        'average': {'real_density': host(avg_rho), 'normalized_real_density': host(al.normalize(avg_rho, dmin)),
+                    'reciprocal_density': host(avg_F), 'intensity_from_densities': host(I_d).real.copy(),
+                    'intensity_from_ft_densities': host(I_ft).real.copy()},
+        'resolution_metrics': metrics,
+        'centered_average': {'real_density': host(cen_rho[0]), 'normalized_real_density': host(al.normalize(cen_rho[0], dmin)),
+                             'reciprocal_density': host(avg_F)},
+        'aligned': {str(i): {'real_density': out(A_rho[i]), 'reciprocal_density': out(A_F[i])} for i in range(n_avg)},
+        'input_meta': {'projection_matrices': projection_matrices, 'scaling_factors': scales,
+                       'average_scaling_factors_per_file': scales_per_file},
+        'inversion_metric': {str(i + 1): np.array([diffs[i, 0], diffs[i, 1], int(inverted[i])]) for i in range(len(keep))},
+        'reference_arg': ref_arg, 'point_inverted': [bool(x) for x in inverted], 'n_averaged': n_avg,
     }

@@ -14,7 +14,7 @@ METHOD_ID = {'HIO': 0, 'ER': 1, 'HIO_non_FXS': 2, 'ER_non_FXS': 3}
 LOOP_MAX_ORDER = 63                   # the phasing loop and the projection (MTIP_LOOP_L_MAX); the transforms alone reach 128
 
 
-class Engine:
+class Engine(_lib.TensorOperands):
     def __init__(self, settings=None, data=None, n_batch=1, device=0, fused=True, lib_path=None,
                  n_radial=None, l_max=None, max_q=None):
         """settings: resolved (or override) settings dict; data: invariants dict (may be None for a
@@ -22,7 +22,6 @@ class Engine:
         and the context-independent operators); with ``data`` the limit is that of the phasing loop, max_order <= 63."""
         self.lib = _lib.load(lib_path)
         self.device_index = int(device)
-        self.emulated = hasattr(self.lib, 'mtip_emulated')          # the CPU emulation of tests/emul: its device memory is host memory
         opt = resolve(settings)
         self.opt = opt
         g = opt['grid']
@@ -565,15 +564,6 @@ class Engine:
     # ------------------------------------------------------------------ the same operators on device-resident batches
     # torch tensors hold the memory (complex128, contiguous, leading dimension n_batch) on the context's device -- CPU tensors
     # under the emulation; the operators read and write them in place in HBM, nothing crosses PCIe.
-    def torch_device(self):
-        import torch
-        return torch.device('cpu') if self.emulated else torch.device('cuda', self.device_index)
-
-    @staticmethod
-    def _tp(t):
-        assert t.is_contiguous()
-        return C.c_void_p(t.data_ptr())
-
     def t_fourier_transform(self, g, inverse=False):
         import torch
         assert tuple(g.shape) == (self.B,) + self.shape and g.dtype == torch.complex128
@@ -633,6 +623,14 @@ class Engine:
             assert tuple(x.shape) == self.shape and x.is_contiguous()
         self._ck(self.lib.mtip_op_prtf(self.ctx, self._tp(a1), self._tp(a2), self._tp(I1), self._tp(I2), _lib.ptr(mean), _lib.ptr(std)))
         return mean, std
+
+    def t_fsc(self, a1, a2):
+        """resolution_metrics.py:23-33: per-shell Fourier shell correlation of two grids, (Nq,) on the host"""
+        fsc = np.zeros(self.N)
+        for x in (a1, a2):
+            assert tuple(x.shape) == self.shape and x.is_contiguous()
+        self._ck(self.lib.mtip_op_fsc(self.ctx, self._tp(a1), self._tp(a2), _lib.ptr(fsc)))
+        return fsc
 
     def t_state(self, kind, batch, best=False):
         """a grid of the loop state -- 'density', 'reciprocal_density' (complex128) or 'support' (uint8), current or best pair -- as a

@@ -89,6 +89,46 @@ def deg2_invariant_to_projection_matrices(engine, b_coeff, q_id_limits=False, so
     return tuple(pms), tuple(evs)
 
 
+def deg2_invariant_to_projection_matrices_2d(engine, b_coeff, q_id_limits=False, sort_mode=0):
+    """fxs_invariant_tools.py:1079-1104 (dim 2) with 1143-1169 per order: v_n = the first eigenvector of the block q_id_limits[n, 0]
+    of B_n times sqrt(its eigenvalue), embedded in Nq rows; an eigenvalue that is not >= 0 gives a zero vector and the eigenvalue 0
+    (1154-1159).  The eigen-decomposition runs on the device (Engine.hermitian_eig), the orders with the same block together.
+    Returns (tuple of v_n (Nq,) -- complex, where upstream keeps the eigenvector's dtype, real for a real block; MTIP2D casts them
+    on entry either way --, tuple of eigenvalues)."""
+    b_coeff = np.asarray(b_coeff)
+    n_orders, nq = b_coeff.shape[0], b_coeff.shape[-1]
+    if isinstance(q_id_limits, bool):                                              # 1091-1093
+        lim = np.zeros((n_orders, 2, 2), dtype=int)
+        lim[..., 1] = nq
+    else:
+        lim = np.array(q_id_limits)
+    if not (lim[:, 0, :] == lim[:, 1, :]).all():                                   # 1094-1099
+        lim[:, 1] = lim[:, 0]
+    pairs = [None] * n_orders
+    blocks = {}
+    for o in range(n_orders):
+        blocks.setdefault((int(lim[o, 0, 0]), int(lim[o, 0, 1])), []).append(o)
+    for (lo, hi), orders in blocks.items():
+        w, v = deg2_invariant_eigenvalues(engine, b_coeff[orders][:, lo:hi, lo:hi], sort_mode)
+        for i, o in enumerate(orders):
+            pairs[o] = (w[i], v[i], lo, hi)
+    pms, evs = [], []
+    for o in range(n_orders):
+        w, v, lo, hi = pairs[o]
+        if len(w) == 0:
+            raise IndexError('order %d: empty block [%d, %d) of the degree-2 invariant (fxs_invariant_tools.py:1149 indexes its first '
+                             'eigenvalue)' % (o, lo, hi))
+        eig_val, eig_vect = float(w[0]), np.array(v[:, 0])
+        if not eig_val >= 0:                                                       # 1154-1159
+            eig_val = 0.0
+            eig_vect[:] = 0
+        full = np.zeros(nq, dtype=eig_vect.dtype)
+        full[lo:hi] = eig_vect
+        pms.append((full * np.sqrt(eig_val)).astype(complex))
+        evs.append(eig_val)
+    return tuple(pms), tuple(evs)
+
+
 def nearest_positive_semidefinite_matrix(engine, A, low_positive_eigenvalues_to_zero=False):
     """mathLibrary.py:872-892 for one matrix or a stack: eigenvalues of the Hermitian part below the limit set to zero.  The
     eigen-decomposition runs on the device; the noise-floor variant needs the spectrum of the unsymmetrised A (numpy, host)."""
@@ -470,7 +510,7 @@ def calc_projection_matrix_error_estimate(deg2_invariant, proj_matrices):
 
 
 def extract_from_cross_correlation(engine, ccd, settings):
-    """extract.py:95-168 + 496-532 for the dataset I1I1 in three dimensions: `ccd` as ``io.load_ccd`` returns it, `settings` the
+    """extract.py:95-168 + 496-532 for the dataset I1I1 in three or two dimensions: `ccd` as ``io.load_ccd`` returns it, `settings` the
     extract settings as a plain dict (default_0.01.yaml: dimensions, max_order, bl_eig_sort_mode, optimize_projection_matrices,
     low_resolution_intensity_approximation, cross_correlation.datasets.I1I1 ...).  Returns the `data` dict of the reconstruct worker
     with the key names of ``io.load_invariants`` (what _database_.py:611-646 saves)."""
@@ -480,9 +520,8 @@ def extract_from_cross_correlation(engine, ccd, settings):
         raise NotImplementedError("extraction_mode %r (extract.py:72-77): this is the route 'cross_correlation'" % (opt['extraction_mode'],))
     if opt.get('optimize_projection_matrices', {}).get('use', False):
         raise NotImplementedError('optimize_projection_matrices.use: True (extract.py:446-451, prephase_projection_matrices 479-493)')
-    if dim != 3:
-        raise NotImplementedError('extract_from_cross_correlation with dimensions = 2 (extract.py:129-130; the invariants themselves are '
-                                  'built: cross_correlation_to_deg2_invariant(engine, cc, 2, ...))')
+    if dim not in (2, 3):
+        raise ValueError('dimensions must be 2 or 3')
     cco = opt['cross_correlation']
     to_process = cco.get('datasets_to_process', ['I1I1'])
     cc_arrays = ccd['cross_correlation']
@@ -506,9 +545,22 @@ def extract_from_cross_correlation(engine, ccd, settings):
     if dopt.get('modify_cc', {}).get('subtract_average_intensity', False):                               # 160-167
         b_coeff[0] = avg[:, None] * avg[None, :] * (4 * np.pi if dim == 3 else 1)
     sort_mode = 1 if opt.get('bl_eig_sort_mode', 'eigenvalues') == 'median_of_scaled_eigenvector' else 0  # 436-439
+    trapz = getattr(np, 'trapezoid', None) or np.trapz
+    if dim == 2:
+        # 129-130: the 2-D Fourier series whatever bl_extraction_method says (the kernel behind cross_correlation_to_deg2_invariant);
+        # one projection vector per order (fxs_invariant_tools.py:1143-1169); 520: the weight q, times 4 pi as written; 526-528: the
+        # low-resolution coefficients stay what the worker initialises them to (61)
+        pms, _ = deg2_invariant_to_projection_matrices_2d(engine, b_coeff, q_id_limits=q_id_limits, sort_mode=sort_mode)
+        errors = calc_projection_matrix_error_estimate(b_coeff, pms)
+        return {'dimensions': dim, 'xray_wavelength': ccd['xray_wavelength'], 'average_intensity': avg, 'data_radial_points': qs,
+                'data_angular_points': phis, 'data_min_q': float(qs.min()), 'max_order': max_order,
+                'data_projection_matrices': np.array(pms), 'data_low_resolution_intensity_coefficients': False,
+                'data_projection_matrices_q_id_limits': {'I1I1': q_id_limits[:, 0]},
+                'data_projection_matrices_masks': {'I1I1': mask.sum(axis=2)}, 'data_projection_matrix_error_estimates': {'I1I1': errors},
+                'integrated_intensity': trapz(avg * qs, x=qs, axis=0) * 4 * np.pi, 'deg_2_invariant': {'I1I1': b_coeff},
+                'deg_2_invariant_masks': {'I1I1': mask}, 'deg_2_invariant_q_id_limits': {'I1I1': q_id_limits}, 'b_coeff': {'I1I1': b_coeff}}
     pms, _ = deg2_invariant_to_projection_matrices(engine, b_coeff, q_id_limits=q_id_limits, sort_mode=sort_mode)
     errors = calc_projection_matrix_error_estimate(b_coeff, pms)
-    trapz = getattr(np, 'trapezoid', None) or np.trapz
     integrated = trapz(avg * qs ** 2, x=qs, axis=0) * 4 * np.pi                                          # 518
     low_order = int(opt.get('low_resolution_intensity_approximation', {}).get('max_order', 20))
     matrices = np.empty(len(pms), object)

@@ -86,7 +86,7 @@ def assemble_weights_2d(weights, orders, r_max, kappa, mode='midpoint'):
     return w * ((-1.j) ** signed[None, None, :] * fs), w * ((1.j) ** signed[None, None, :] * iv)
 
 
-class Engine2D:
+class Engine2D(_lib.TensorOperands):
     """transforms (and, after ``set_projection``, the reciprocal projection) of the 2-D variant for batches of ``n_batch`` grids"""
 
     def __init__(self, n_radial_points, max_order, max_q, reciprocity_coefficient=2.0, n_batch=1, device=0, lib_path=None, used_orders=None,
@@ -104,6 +104,7 @@ class Engine2D:
         self.shape = (self.N, self.n_phi)
         if self.lib.mtip_device_count() <= 0:
             raise _lib.MtipError('no HIP device visible: the 2-D operators need an MI355X (no CPU fallback)')
+        self.device_index = int(device)
         self.ctx = self.lib.mtip2d_create(self.N, self.n_phi, self.B, int(device))
         if not self.ctx:
             raise _lib.MtipError('mtip2d_create failed (sizes: n_phi odd, 3..2047; a visible device)')
@@ -377,3 +378,149 @@ class Engine2D:
 
     def synchronize(self):
         self._ck(self.lib.mtip2d_synchronize(self.ctx))
+
+    # ---- grid arithmetic of the averaging worker on stacks (csrc/k_average2d.h): torch tensors on the engine's device (they own
+    #      the memory, nothing else) or numpy arrays; stacks (n, Nq, n_phi) complex128 of any length
+    @classmethod
+    def _p(cls, x):
+        """void* of a numpy array or of a tensor (after torch's stream has finished writing it: _lib.TensorOperands)"""
+        if x is None:
+            return None
+        return _lib.ptr(x) if isinstance(x, np.ndarray) else cls._tp(x)
+
+    def _stack(self, X):
+        """a stack as the kernels read it: contiguous complex128 (n, Nq, n_phi), numpy or torch"""
+        if isinstance(X, np.ndarray):
+            X = _lib.as_c128(X)
+        else:
+            import torch
+            assert X.dtype == torch.complex128
+            X = X.contiguous()
+        assert X.ndim == 3 and tuple(X.shape[1:]) == self.shape, (tuple(X.shape), self.shape)
+        return X
+
+    @staticmethod
+    def _like(X, shape):
+        if isinstance(X, np.ndarray):
+            return np.empty(shape, complex)
+        import torch
+        return torch.empty(shape, dtype=torch.complex128, device=X.device)
+
+    def _avg_setup(self):
+        if getattr(self, '_avg_ready', False):
+            return
+
+        def trapz_w(x):                                          # PolarIntegrator.integrate (mathLibrary.py:1254-1262) as weights
+            w = np.zeros(len(x))
+            d = np.diff(x)
+            w[:-1] += d / 2
+            w[1:] += d / 2
+            return w
+        rs, qs = _lib.as_f64(self.rs), _lib.as_f64(self.qs)
+        self.int_wr, self.int_wq, self.int_wphi = _lib.as_f64(trapz_w(rs) * rs), _lib.as_f64(trapz_w(qs) * qs), _lib.as_f64(trapz_w(self.phis))
+        self._ck(self.lib.mtip2d_avg_set_grid(self.ctx, _lib.ptr(rs), _lib.ptr(qs), _lib.ptr(self.int_wr), _lib.ptr(self.int_wq),
+                                              _lib.ptr(self.int_wphi)))
+        self._avg_ready = True
+
+    def _chunked(self, fn, X, inverse):
+        """a batched transform of the C ABI over a stack of any length, in chunks of n_batch (a short last chunk is filled up with its
+        last grid); a grid's transform does not depend on its neighbours in the chunk"""
+        X = self._stack(X)
+        n, out = X.shape[0], self._like(X, tuple(X.shape))
+        for i in range(0, n, self.B):
+            m = min(self.B, n - i)
+            if m == self.B:
+                self._ck(fn(self.ctx, self._p(X[i:i + m]), self._p(out[i:i + m]), int(inverse)))
+                continue
+            buf, res = self._like(X, (self.B,) + self.shape), self._like(X, (self.B,) + self.shape)
+            buf[:m] = X[i:i + m]
+            buf[m:] = X[n - 1]
+            self._ck(fn(self.ctx, self._p(buf), self._p(res), int(inverse)))
+            out[i:i + m] = res[:m]
+        return out
+
+    def t_fourier_transform(self, X, inverse=False):
+        """mtip2d_op_fourier_transform of a stack of any length"""
+        return self._chunked(self.lib.mtip2d_op_fourier_transform, X, inverse)
+
+    def t_harmonic(self, X, inverse=False):
+        """mtip2d_op_harmonic (complex circular harmonic transform, orders 0..M, -M..-1) of a stack of any length"""
+        return self._chunked(self.lib.mtip2d_op_harmonic, X, inverse)
+
+    def t_grid_stats(self, X):
+        """(n, 9) host array per grid (mtip2d_avg_grid_stats): integral and first moments of Re, and the statistics of the entries > 0"""
+        self._avg_setup()
+        X = self._stack(X)
+        out = np.zeros((X.shape[0], 9))
+        self._ck(self.lib.mtip2d_avg_grid_stats(self.ctx, self._p(X), int(X.shape[0]), _lib.ptr(out)))
+        return out
+
+    def t_inversion_metric(self, F, F_ref):
+        """(n, 2) host array: integrals of |Im F - Im F_ref| and |Im F - Im conj(F_ref)| (average.py:216-217)"""
+        self._avg_setup()
+        F, F_ref = self._stack(F), self._stack(F_ref[None])
+        out = np.zeros((F.shape[0], 2))
+        self._ck(self.lib.mtip2d_avg_inversion_metric(self.ctx, self._p(F), int(F.shape[0]), self._p(F_ref), _lib.ptr(out)))
+        return out
+
+    def t_phase_ramp(self, X, centers_cartesian, sign):
+        """X[b] *= exp(-i sign k . c_b) IN PLACE (generate_shift_by_operator, fxs_Projections.py:1426-1434); returns X"""
+        self._avg_setup()
+        assert self._stack(X) is X, 'phase ramp works in place: a contiguous complex128 stack'
+        cc = _lib.as_f64(centers_cartesian)
+        assert cc.shape == (X.shape[0], 2)
+        self._ck(self.lib.mtip2d_op_grid_phase_ramp(self.ctx, self._p(X), int(X.shape[0]), _lib.ptr(cc), float(sign)))
+        return X
+
+    def t_combine(self, op, A, scalars=None):
+        """mtip2d_op_grid_combine on a stack: 'conj', 'div' (complex divisor per grid) -> a stack; 'mean', 'abs2mean' (sum over the
+        stack in its order, divided by scalars[0]) -> one grid; 'affine' ((a - s0) / s1, real scalars) -> a stack"""
+        code = {'conj': 0, 'div': 1, 'mean': 2, 'abs2mean': 3, 'affine': 4}[op]
+        A = self._stack(A)
+        out = self._like(A, self.shape if code in (2, 3) else tuple(A.shape))
+        sc = None if scalars is None else _lib.as_c128(np.atleast_1d(scalars))
+        assert code == 0 or sc.shape == ((A.shape[0],) if code == 1 else ((2,) if code == 4 else (1,)))
+        self._ck(self.lib.mtip2d_op_grid_combine(self.ctx, code, self._p(out), self._p(A), int(A.shape[0]), _lib.ptr(sc)))
+        return out
+
+    def t_curves(self, a_d, a_ft, I_d, I_ft):
+        """mtip2d_avg_curves: (prtf_mean (4, Nq) complex, prtf_std (4, Nq), fsc (Nq)) on the host"""
+        args = [self._stack(x[None]) for x in (a_d, a_ft, I_d, I_ft)]
+        mean, std, fsc = np.zeros((4, self.N), complex), np.zeros((4, self.N)), np.zeros(self.N)
+        self._ck(self.lib.mtip2d_avg_curves(self.ctx, *[self._p(x) for x in args], _lib.ptr(mean), _lib.ptr(std), _lib.ptr(fsc)))
+        return mean, std, fsc
+
+    def _fqcb_arg(self, x):
+        """(array, kind, n_orders, ld) of an FQCB input: a coefficient table (Nq, ld) -- a tuple (table, n_orders) reads only its first
+        n_orders columns -- or a B_n stack (n_orders, Nq, Nq)"""
+        n = None
+        if isinstance(x, tuple):
+            x, n = x
+        if isinstance(x, np.ndarray):
+            x = _lib.as_c128(x)
+        else:
+            x = x.contiguous()
+        if x.ndim == 2:
+            assert x.shape[0] == self.N and (n is None or n <= x.shape[1])
+            return x, 0, int(x.shape[1] if n is None else n), int(x.shape[1])
+        assert x.ndim == 3 and tuple(x.shape[1:]) == (self.N, self.N) and n is None
+        return x, 1, int(x.shape[0]), 0
+
+    def t_fqcb(self, b1, b2, skip_odd_orders=False, include_zero_order=False):
+        """FQCB_2D (resolution_metrics.py:146-187) on the device: (mean, std) over q' <= q, (Nq,) each, on the host"""
+        x1, k1, n1, ld1 = self._fqcb_arg(b1)
+        x2, k2, n2, ld2 = self._fqcb_arg(b2)
+        o_start, o_step = (2, 2) if skip_odd_orders else (1, 1)
+        if include_zero_order:
+            o_start = 0
+        mean, std = np.zeros(self.N), np.zeros(self.N)
+        self._ck(self.lib.mtip2d_avg_fqcb(self.ctx, self._p(x1), k1, n1, ld1, self._p(x2), k2, n2, ld2, o_start, o_step, _lib.ptr(mean), _lib.ptr(std)))
+        return mean, std
+
+    def t_deg2_from_table(self, table, n_orders=None):
+        """B_n(q, q') = I_n(q) conj(I_n(q')) (fxs_invariant_tools.py:906-914) of the first n_orders columns of a table (Nq, ld):
+        (n_orders, Nq, Nq), where the table lives"""
+        x, _, n, ld = self._fqcb_arg(table if n_orders is None else (table, n_orders))
+        out = self._like(x, (n, self.N, self.N))
+        self._ck(self.lib.mtip2d_op_deg2_from_table(self.ctx, self._p(x), n, ld, self._p(out)))
+        return out
