@@ -53,15 +53,21 @@ typedef struct {
     int32_t l_max;         /* L : grid.max_order, 0 <= L <= 128.  L <= 63: everything; 64 <= L <= 128: the transforms
                               (mtip_op_sht_*, mtip_op_hankel, mtip_op_fourier_transform), mtip_op_deg2_invariants and the
                               context-independent operators -- the phasing loop (mtip_run*, mtip_shrinkwrap, ..),
-                              mtip_set_projection_matrix, mtip_op_project_* and mtip_op_apply_unknowns return MTIP_ESTATE */
+                              mtip_set_projection_matrix, mtip_op_project_* and mtip_op_apply_unknowns return MTIP_ESTATE
+                              unless `reserved` has MTIP_CFG_LOOP_BIG_L.  With it they run up to L = 128; still refused
+                              (MTIP_ESTATE, before any launch): an active order with min(2l+1, Nq) > 128 columns, a
+                              per-restart ft_stab mask (mtip_set_ft_stab_mask with both values) */
     int32_t n_theta;       /* Gauss-Legendre nodes (shtns_plugin.py:94-101 for defaults) */
     int32_t n_phi;         /* power of two, > 2L                                         */
     int32_t n_batch;       /* restarts resident in this ctx (>=1)                        */
     int32_t hankel_trapz;  /* 0: midpoint/gauss rule (hankel_transforms.py:702-731);
                               1: trapz/Zernike (671-700: weights have Nq-1 rows, reads f[p+1]) */
     int32_t fused;         /* 1: algebraically fused step, 0: reference operator order */
-    int32_t reserved;
+    int32_t reserved;      /* flag word: MTIP_CFG_* below; any other bit makes mtip_create fail (invalid cfg) */
 } mtip_cfg;
+
+/* mtip_cfg.reserved bit 0: the phasing loop and the projection beyond L = 63 (opt-in; no effect for L <= 63) */
+#define MTIP_CFG_LOOP_BIG_L 1
 
 /* ---- life cycle ------------------------------------------------------------------------------
  * replaces Multiprocessing.get_number_of_gpus (xframe/Multiprocessing.py:892-898) and the

@@ -30,12 +30,16 @@ __device__ __forceinline__ void jacobi_pair(int r, int pi, int Cp, int* a, int* 
     }
 }
 
+#define PROJ_MAX_COLS 128   // columns k_l of a solved order: s_isig / JacShared below, the two ballots of the compaction, k_proj_xw's 8 waves
+
+// Polar factors in global memory, grid (order, restart).  Bounds: rows n = 2l+1 any (every row loop runs to n; 257 at l = 128),
+// columns k_l <= PROJ_MAX_COLS (s_isig); `used` is the list of solved orders (d_active).
 __global__ void __launch_bounds__(256) k_polar_jacobi(double2* __restrict__ Xall, double2* __restrict__ Vrall,
                                                       double2* __restrict__ Uall, const int* __restrict__ kl,
                                                       const int* __restrict__ used, const int* __restrict__ xoff,
                                                       const int* __restrict__ roff, int xtot, int rtot) {
     __shared__ int s_rotated;
-    __shared__ double s_isig[128];                        // k_l <= 2*63+1
+    __shared__ double s_isig[PROJ_MAX_COLS];
     const int l = blockIdx.x, b = blockIdx.y;
     if (!used[l]) return;                                  // uniform per block
     const int k = kl[l], n = 2 * l + 1;
@@ -397,12 +401,15 @@ struct JacobiArgs {
     const int* order_list;
 };
 
-// static LDS of a Jacobi workgroup
+// static LDS of a Jacobi workgroup.  Bounds of k_polar_jacobi_lds<MAXR, TG>: rows 2l+1 <= MAXR * TG (the row slots of a lane: 80,
+// 72 and, widest, 16 x 8 = PROJ_JAC_LDS_MAX_ROWS for the three instantiations; jl_pair_generic stops at MAXR slots), columns
+// k_l <= PROJ_MAX_COLS (isig, perm, the two 64-lane ballots), and X_l + V_r within the dynamic LDS (plan_projection).
+#define PROJ_JAC_LDS_MAX_ROWS 128
 template <int MAXT>
 struct JacShared {
     double gmax[MAXT / 8];
-    double isig[128];
-    int perm[128];
+    double isig[PROJ_MAX_COLS];
+    int perm[PROJ_MAX_COLS];
     int cont, keff;
 };
 
@@ -700,6 +707,8 @@ struct ProjGemm {
 //   B2[(k,re)] = Im B, B2[(k,im)] = Re B,
 // i.e. every lane loads ONE complex element of A and one of B per k-step of 2 complex inner indices and picks its
 // half.  PM_PF k-steps of branch-free loads are in flight (clamped addresses, zeros by select).
+// Bounds: rows, columns and the inner extent are run-time numbers; the tile word holds order (8 bits, l <= 128), row tile (8 bits:
+// <= 17 at 257 rows) and column group (<= 5 at 257 columns): nothing here is sized by L.
 #define PM_PF 4
 
 template <int OP>
@@ -824,6 +833,9 @@ __device__ __forceinline__ void pm_accumulate(const double2* ap, size_t a_sk, bo
 }
 
 #define PF_THREADS 512          // 8 waves: up to 128 columns of X_l / 128 shells per pass of I'_l
+// Bounds of the fused pairs: both loop over their 16 x 16 tiles by wave, so rows (2l+1 <= 257: 17 row / column tiles in the tile
+// word) and columns are run-time numbers; their LDS is sized by the plan (xw_lds: 16 x kmax, ua_lds: kmax_used x 17).  They run only
+// next to the LDS polar factors (pp.lds_path), whose bounds are the tighter ones.
 
 // W[16 rows of tile_m][all k columns] = (conj(I_l)^T q^2 V_l)[rows] V_r:   tiles = order | tile_m << 8
 __global__ void __launch_bounds__(PF_THREADS) k_proj_xw(ProjGemmArgs a, const int* __restrict__ tiles) {
@@ -1130,7 +1142,10 @@ void plan_projection(mtip_ctx* c) {
     pp.ua_lds = (size_t)pp.kmax_used * 17 * sizeof(double2);
     const size_t lds = ((size_t)kmax * (nmax | 1) + (size_t)kmax * (kmax | 1)) * sizeof(double2);   // unpadded minimum
     const bool sched_ok = c->psw.jac_resident && kmax <= 255 && kmax >= 2 && build_jacobi_schedule(c, kmax) == MTIP_OK;
-    pp.lds_path = lds <= 158 * 1024;                            // X_l and V_r of the largest order share one CU's LDS (2l+1 <= 71)
+    // X_l and V_r of the largest order share one CU's LDS (square orders: 2l+1 <= 71) AND its rows fit the row slots of the widest
+    // instantiation (k_polar_jacobi_lds<16, 8>: PROJ_JAC_LDS_MAX_ROWS): an order beyond L = 63 with few columns passes the first
+    // test alone (12 columns x 201 rows: 45 KiB), and the kernel would leave its rows past 128 out of every rotation
+    pp.lds_path = lds <= 158 * 1024 && nmax <= PROJ_JAC_LDS_MAX_ROWS;
     const int pairs_max = kmax / 2;                             // valid pairs per round (odd k: dummy pair skipped)
     // 16 lanes per pair when all pairs of a round still fit one workgroup, else 8
     pp.tg = (c->psw.jac_tg == 16 && pairs_max * 16 <= JL_MAX_THREADS && nmax <= 5 * 16) ? 16 : 8;
@@ -1242,7 +1257,21 @@ static int launch_project_coefficients_impl(mtip_ctx* c, const double2* Ilm, dou
     return launch_apply_unknowns(c, Ilm, out);                  // I'_l = V_l U_l in place; a separate output first receives a copy of I_l
 }
 
+// Every polar-factor kernel holds at most PROJ_MAX_COLS columns per solved order.  Up to L = 63 every order has at most 127; beyond
+// it (MTIP_CFG_LOOP_BIG_L) an active order l >= 64 has min(2l+1, Nq) columns, more than that once Nq > 128: refused before any launch.
+int require_projection_columns(mtip_ctx* c, const char* what) {
+    for (int l = 0; l <= c->L; ++l)
+        if (c->active[l] && c->kl[l] > PROJ_MAX_COLS) {
+            c->err = std::string(what) + ": order l = " + std::to_string(l) + " is solved with min(2l+1, Nq) = " + std::to_string(c->kl[l]) +
+                     " columns; the projection holds at most " + std::to_string(PROJ_MAX_COLS) +
+                     " columns per active order (Nq <= 128, or active orders up to 63: DESIGN section 6)";
+            return MTIP_ESTATE;
+        }
+    return MTIP_OK;
+}
+
 int launch_project_coefficients(mtip_ctx* c, const double2* Ilm, double2* out, bool real_intensity) {
+    if (int r = require_projection_columns(c, "projection")) return r;
     const int rc = launch_project_coefficients_impl(c, Ilm, out, real_intensity);
     if (rc == MTIP_OK && c->so_order >= 0 && c->active[c->so_order] && c->kl[c->so_order] >= 5) {
         const int l = c->so_order;

@@ -10,7 +10,8 @@
 //             k_sht_big_leg_fwd   per order |m| and tile of 16 shells:  c[l][col] = sum_theta P_lm(theta) g[theta][col],
 //                                 col = (+-m, shell, re/im)
 //   inverse   k_sht_big_leg_inv   g[theta][col] = sum_l P_lm(theta) c[l][col]
-//             k_sht_big_fft_inv   the inverse FFT of the rows, EPI_STORE / EPI_SCALE_SHELL
+//             k_sht_big_fft_inv   the inverse FFT of the rows, EPI_STORE / EPI_SCALE_SHELL / EPI_MODULUS (F' = F sqrt(I'/I): the
+//                                 step's modulus stage), the output optionally through the slot table
 //
 // The Legendre stages are real-matrix x complex-panel products on v_mfma_f64_16x16x4_f64 (lane j: A[i = j & 15][k = j >> 4],
 // B[k = j >> 4][col = j & 15], D reg r = D[(j >> 4) + 4 r][j & 15], as in k_hankel_tile).  P_lm(pi - theta) = (-1)^(l + m) P_lm(theta):
@@ -105,7 +106,8 @@ __global__ void __launch_bounds__(256) k_sht_big_fft_fwd(const double2* __restri
 template <int EPI>
 __global__ void __launch_bounds__(256) k_sht_big_fft_inv(const double2* __restrict__ gs, double2* __restrict__ grid,
                                                          const double2* __restrict__ tw, int np, int nt, int L, int N, int Q,
-                                                         const double* __restrict__ shell_scale) {
+                                                         const double* __restrict__ shell_scale, const double2* __restrict__ Fin,
+                                                         const int* __restrict__ slot, int which, int B) {
     __shared__ double2 xy[2 * 512];
     __shared__ double2 S[BL_QB * BL_NM_MAX];
     const int T = np >> 1, R = 256 / T;
@@ -132,8 +134,24 @@ __global__ void __launch_bounds__(256) k_sht_big_fft_inv(const double2* __restri
         bigl_fft_row<true>(x, y, tw, np, T, i, active);
         if (active) {
             const double sc = EPI == EPI_SCALE_SHELL ? shell_scale[bq % N] : 1.0;
-            double2* out = grid + ((long long)bq * nt + t) * np;
-            for (int e = i; e < np; e += T) out[e] = EPI == EPI_SCALE_SHELL ? cscale(x[e], sc) : x[e];
+            const long long o = ((long long)bq * nt + t) * np;
+            long long oo = o;                               // slot-indirect output: (3,B,G) pair array; the restart per row, a block
+            if (slot != nullptr) oo += (long long)slot[(bq / N) * SL_N + which] * B * N * nt * np;     // of shells may straddle two
+            for (int e = i; e < np; e += T) {
+                double2 v = x[e];
+                if (EPI == EPI_MODULUS) {
+                    // project_to_modified_intensity, fxs_Projections.py:899-909 (k_fft_inv<EPI_MODULUS>'s arithmetic); F of the
+                    // row's own point straight from global memory, a coalesced row
+                    const double2 Fv = Fin[o + e];
+                    const double I = cabs2(Fv);
+                    const bool ok = (I >= 0.0) && (v.x >= 0.0);
+                    const double mult = ok ? sqrt(v.x / I) : 0.0;
+                    v = cscale(Fv, mult);
+                } else if (EPI == EPI_SCALE_SHELL) {
+                    v = cscale(v, sc);
+                }
+                grid[oo + e] = v;
+            }
         }
         __syncthreads();                                    // x free for the next pass
     }
@@ -328,17 +346,22 @@ static int launch_bigl_forward(mtip_ctx* c, const double2* grid, double2* coeff,
 }
 
 static int launch_bigl_inverse(mtip_ctx* c, const double2* coeff, double2* grid, const InvEpilogue& epi) {
-    // the other epilogues, the slot-indirect output and the coefficient difference belong to the phasing loop (L <= 63)
-    if ((epi.mode != EPI_STORE && epi.mode != EPI_SCALE_SHELL) || epi.out_slot >= 0) return sht_no_kernel(c, "inverse beyond L = 63", epi.mode);
+    // store, shell scale and the step's modulus, each with or without the slot-indirect output; the real-space epilogue, the fixed
+    // modulus and the coefficient difference on load exist in the tiers for L <= 63 only (plan_sht leaves real_update off here)
+    if ((epi.mode != EPI_STORE && epi.mode != EPI_SCALE_SHELL && epi.mode != EPI_MODULUS) || epi.coeff_sub != nullptr)
+        return sht_no_kernel(c, "inverse beyond L = 63", epi.mode);
+    if (epi.mode == EPI_MODULUS && epi.F == nullptr) return sht_no_kernel(c, "inverse beyond L = 63 without F", epi.mode);
     const int Q = c->B * c->N;
     const dim3 fg((unsigned)div_up(Q, BL_QB), (unsigned)c->nt), lg((unsigned)(c->L + 1), (unsigned)div_up(2 * Q, BL_CT));
     hipLaunchKernelGGL(k_sht_big_leg_inv, lg, dim3(256), 0, c->stream, coeff, reinterpret_cast<double*>((double2*)c->d_g),
                        (const double*)c->d_P, (const int*)c->d_poff, c->nt, c->L, Q);
-    if (epi.mode == EPI_SCALE_SHELL)
-        hipLaunchKernelGGL(k_sht_big_fft_inv<EPI_SCALE_SHELL>, fg, dim3(256), 0, c->stream, (const double2*)c->d_g, grid,
-                           (const double2*)c->d_tw, c->np, c->nt, c->L, c->N, Q, epi.shell_scale);
-    else
-        hipLaunchKernelGGL(k_sht_big_fft_inv<EPI_STORE>, fg, dim3(256), 0, c->stream, (const double2*)c->d_g, grid,
-                           (const double2*)c->d_tw, c->np, c->nt, c->L, c->N, Q, epi.shell_scale);
+    const int* sl = epi.out_slot >= 0 ? (const int*)c->d_slot : nullptr;
+#define BL_INV(EPI)                                                                                                          \
+    hipLaunchKernelGGL(k_sht_big_fft_inv<EPI>, fg, dim3(256), 0, c->stream, (const double2*)c->d_g, grid,                    \
+                       (const double2*)c->d_tw, c->np, c->nt, c->L, c->N, Q, epi.shell_scale, epi.F, sl, epi.out_slot, c->B)
+    if (epi.mode == EPI_SCALE_SHELL) BL_INV(EPI_SCALE_SHELL);
+    else if (epi.mode == EPI_MODULUS) BL_INV(EPI_MODULUS);
+    else BL_INV(EPI_STORE);
+#undef BL_INV
     return MTIP_OK;
 }

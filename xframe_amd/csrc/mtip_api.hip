@@ -77,8 +77,10 @@ void mtip_destroy(mtip_ctx* c) {
 
 // The projection kernels (k_proj.hip, k_projr.hip: at most 128 columns per order) and the loop's SHT variants (chained, wide, fused
 // epilogues) are sized for L <= 63; a context beyond it has the transforms, B_l and the context-independent operators only.
+// MTIP_CFG_LOOP_BIG_L (cfg.reserved, opt-in) lifts the limit: the step then runs on the two-stage transforms of k_sht_big.h without
+// the chained and real-update tiers, and the projection refuses only what its kernels do not hold (require_projection_columns).
 static int require_loop_band_limit(mtip_ctx* c, const char* what) {
-    if (c->L > MTIP_LOOP_L_MAX)
+    if (c->L > MTIP_LOOP_L_MAX && !(c->cfg.reserved & MTIP_CFG_LOOP_BIG_L))
         FAIL(c, MTIP_ESTATE, std::string(what) + ": the phasing loop and the projection are built for max_order <= 63; this context has L = " +
                                  std::to_string(c->L) + " and runs the transforms only (DESIGN section 6)");
     return MTIP_OK;
@@ -103,6 +105,10 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     if (cfg->n_radial < 2 || cfg->l_max < 0 || cfg->l_max > 128 || cfg->n_batch < 1 || !is_pow2(cfg->n_phi) ||
         cfg->n_phi < 4 || cfg->n_phi > 512 || cfg->n_phi <= 2 * cfg->l_max || cfg->n_theta <= cfg->l_max) {
         g_create_error = "invalid cfg: need Nq>=2, 0<=L<=128 (the transforms; the phasing loop and the projection: L<=63), n_batch>=1, n_phi a power of two in [4,512] and > 2L, n_theta > L";
+        return nullptr;
+    }
+    if (cfg->reserved & ~MTIP_CFG_LOOP_BIG_L) {
+        g_create_error = "invalid cfg: reserved is a flag word, only MTIP_CFG_LOOP_BIG_L (bit 0) is defined";
         return nullptr;
     }
     if (hipSetDevice(device) != hipSuccess) {
@@ -462,6 +468,8 @@ static int require_loop(mtip_ctx* c) {
     if (!c->have_errw) FAIL(c, MTIP_ESTATE, "mtip_set_error_weights has not been called");
     for (int l = 0; l <= c->L; ++l)
         if (!c->have_V[l]) FAIL(c, MTIP_ESTATE, "mtip_set_projection_matrix missing for some order");
+    r = require_projection_columns(c, "phasing loop");
+    if (r) return r;
     if (!c->state_ready) FAIL(c, MTIP_ESTATE, "mtip_init_state has not been called");
     return MTIP_OK;
 }
@@ -1167,6 +1175,7 @@ static int op_project(mtip_ctx* c, const mtip_cdouble* Ilm, mtip_cdouble* out, b
     if (!c->have_radial) FAIL(c, MTIP_ESTATE, "mtip_set_radial_grid has not been called");
     for (int l = 0; l <= c->L; ++l)
         if (!c->have_V[l]) FAIL(c, MTIP_ESTATE, "mtip_set_projection_matrix missing for some order");
+    if (int r = require_projection_columns(c, real_intensity ? "mtip_op_project_real_intensity" : "mtip_op_project_coefficients")) return r;
     if (!Ilm || !out) FAIL(c, MTIP_EINVAL, "null buffer");
     (void)hipSetDevice(c->device);
     SYNC();

@@ -187,7 +187,7 @@ struct ProfEntry { double ms = 0; long long n = 0; };
 // pass-wise register-FFT kernels (k_sht_fwd_reg / k_sht_inv_reg: both directions must fit), 1 the LDS Stockham kernels
 // (k_sht_fused.hip), 0 the generic FFT + Legendre kernels (k_sht.hip).  Tiers 1-5 are sized for L <= MTIP_LOOP_L_MAX; a context
 // beyond it takes the two-stage kernels of k_sht_big.h (cap >= 1, even n_theta <= SHT_BIG_NT_MAX) or the generic ones, without chain or real_update.
-#define MTIP_LOOP_L_MAX 63              // band limit of the tuned SHT tiers, the projection and with them the phasing loop
+#define MTIP_LOOP_L_MAX 63              // band limit of the tuned SHT tiers and, unless cfg.reserved has MTIP_CFG_LOOP_BIG_L, of the projection and the phasing loop
 #define SHT_BIG_NT_MAX 256              // k_sht_big.h: the synthesis holds the <= 128 theta pairs of a chunk in eight row tiles
 enum { SHT_FWD_GENERIC = 0, SHT_FWD_LDS, SHT_FWD_REG, SHT_FWD_PAIR, SHT_FWD_BIG };
 enum { SHT_INV_GENERIC = 0, SHT_INV_LDS, SHT_INV_REG, SHT_INV_WIDE, SHT_INV_BIG };
@@ -449,6 +449,7 @@ void launch_coeff_diff(mtip_ctx* c, const double2* a, const double2* b, double2*
 // real_intensity: the caller guarantees I_{l,-m} = (-1)^m conj(I_{l,m}) (coefficients of a real grid, as in the phasing
 // loop): with real V_l the projection then takes its real form (k_projr.hip)
 int launch_project_coefficients(mtip_ctx* c, const double2* Ilm, double2* out, bool real_intensity = false);   // MTIP_OK or an error code (c->err set)
+int require_projection_columns(mtip_ctx* c, const char* what);   // k_proj.hip: MTIP_ESTATE (c->err set) where an active order has more than 128 columns
 void plan_projection(mtip_ctx* c);                    // k_proj.hip: decides c->pp where it is not planned
 void plan_rproj(mtip_ctx* c);                         // k_projr.hip: real_ok and rg of c->pp
 void invalidate_projection(mtip_ctx* c);              // k_proj.hip: V_l, k_l, used or active change: drops the plan, its tables and the carried V_r

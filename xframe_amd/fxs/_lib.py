@@ -26,6 +26,9 @@ class MtipCfg(C.Structure):
                 ('n_batch', C.c_int32), ('hankel_trapz', C.c_int32), ('fused', C.c_int32), ('reserved', C.c_int32)]
 
 
+MTIP_CFG_LOOP_BIG_L = 1           # MtipCfg.reserved bit 0 (include/mtip_hip.h): the phasing loop and the projection beyond L = 63
+
+
 class MtipCorrelateCfg(C.Structure):
     _fields_ = [('n_q', C.c_int32), ('n_phi', C.c_int32), ('n_q1', C.c_int32), ('n_q2', C.c_int32), ('filter_kind', C.c_int32),
                 ('roi_lo', C.c_int32), ('roi_hi', C.c_int32), ('roi_filter', C.c_int32), ('roi_normalize', C.c_int32),

@@ -16,10 +16,12 @@ LOOP_MAX_ORDER = 63                   # the phasing loop and the projection (MTI
 
 class Engine(_lib.TensorOperands):
     def __init__(self, settings=None, data=None, n_batch=1, device=0, fused=True, lib_path=None,
-                 n_radial=None, l_max=None, max_q=None):
+                 n_radial=None, l_max=None, max_q=None, big_l_loop=None):
         """settings: resolved (or override) settings dict; data: invariants dict (may be None for a
         transforms-only engine, then ``max_q`` must be given).  A transforms-only engine takes max_order <= 128 (the transforms, B_l
-        and the context-independent operators); with ``data`` the limit is that of the phasing loop, max_order <= 63."""
+        and the context-independent operators); with ``data`` the limit is that of the phasing loop, max_order <= 63.
+        big_l_loop (None: the setting ``GPU.big_l_loop``, default False) opts in to the phasing loop and the projection up to
+        max_order 128 (MTIP_CFG_LOOP_BIG_L: DESIGN section 6 lists what stays refused); below 64 it changes nothing."""
         self.lib = _lib.load(lib_path)
         self.device_index = int(device)
         opt = resolve(settings)
@@ -27,7 +29,8 @@ class Engine(_lib.TensorOperands):
         g = opt['grid']
         self.N = int(n_radial if n_radial is not None else g['n_radial_points'])
         self.L = int(l_max if l_max is not None else g['max_order'])
-        if data is not None and self.L > LOOP_MAX_ORDER:
+        self.big_l_loop = bool(opt.get('GPU', {}).get('big_l_loop', False) if big_l_loop is None else big_l_loop)
+        if data is not None and self.L > LOOP_MAX_ORDER and not self.big_l_loop:
             raise NotImplementedError('max_order = %d with invariants: the phasing loop and the projection are built for max_order <= %d; '
                                       'beyond it (up to 128) an engine without data runs the transforms only (DESIGN section 6)'
                                       % (self.L, LOOP_MAX_ORDER))
@@ -48,7 +51,7 @@ class Engine(_lib.TensorOperands):
         if self.lib.mtip_device_count() <= 0:
             raise _lib.MtipError('no HIP device visible: the MTIP engine needs an MI355X (no CPU fallback)')
         cfg = _lib.MtipCfg(self.N, self.L, self.n_theta, self.n_phi, self.B, 1 if hs.hankel_skips_first_shell(self.mode) else 0,
-                           1 if fused else 0, 0)
+                           1 if fused else 0, _lib.MTIP_CFG_LOOP_BIG_L if self.big_l_loop else 0)
         self.ctx = self.lib.mtip_create(C.byref(cfg), int(device))
         self.group = None                                            # EngineGroup this engine steps with (side-by-side restart groups)
         if not self.ctx:

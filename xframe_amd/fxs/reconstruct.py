@@ -55,7 +55,7 @@ class MTIP:
         cls.preinit_was_called = True
 
     def __init__(self, process_factory=None, n_restarts=1, device=0, fused=True, seeds=None, initial_densities=None,
-                 lib_path=None):
+                 lib_path=None, big_l_loop=None):
         if not MTIP.preinit_was_called:
             raise RuntimeError('MTIP.preinit(settings, invariants) must be called first')
         self.process_factory = process_factory if process_factory is not None else RecipeFactory({})
@@ -66,6 +66,7 @@ class MTIP:
         self.seeds = seeds
         self.initial_densities = initial_densities
         self.lib_path = lib_path
+        self.big_l_loop = big_l_loop                # None: the setting GPU.big_l_loop (Engine)
         self.results = {}
         self.engine = None
         self.phasing_loop = False
@@ -95,7 +96,7 @@ class MTIP:
             self.phasing_loop = loop2d
             return
         self.engine = Engine(self.opt, MTIP.mtip_data, n_batch=self.n_restarts, device=self.device, fused=self.fused,
-                             lib_path=self.lib_path)
+                             lib_path=self.lib_path, big_l_loop=self.big_l_loop)
         self._engine_seconds = time.perf_counter() - t_engine
         self.rprojection = self.engine.rsetup
         self.process_factory.addOperators(build_operators(self.engine))

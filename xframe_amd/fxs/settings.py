@@ -105,7 +105,8 @@ def default_settings():
             },
         },
         # resident_2d (this project's key): dimensions == 2 on the resident engine (mtip2d_run) instead of one operator call per step
-        'GPU': {'use': True, 'n_gpu_workers': 1, 'resident_2d': False},
+        # big_l_loop (this project's key): the 3-D phasing loop and the projection for 64 <= max_order <= 128 (Engine, MTIP_CFG_LOOP_BIG_L)
+        'GPU': {'use': True, 'n_gpu_workers': 1, 'resident_2d': False, 'big_l_loop': False},
         'multi_process': {'use': True, 'n_parallel_reconstructions': 1},
         'profiling': {'enable': False, 'reconstruction_process_id': 1, 'gpu_worker_id': -1},
         # xframe/settings/general.py:25-27 (decides which variant of the real error metric the reference uses)
