@@ -312,14 +312,24 @@ int mtip_op_symmetric_eig(mtip_ctx* ctx, int n, int n_mat, const double* A, doub
  * bad_angles (n_delta): 1 where phi < pi/2 or phi >= 3 pi/2 (267); MTIP_CC_Q1Q2_SYMMETRIC.
  * legendre (dimensions 3): (n_q, n_m (n_m + 1) / 2), n_m = max_order / stride + 1: gsl_sf_legendre_sphPlm(li stride, mi stride,
  * cos theta_q) at li (li + 1) / 2 + mi, theta_q = ewald_sphere_theta_pi (physicsLibrary.py:94-95; line 602 takes it whatever pi_in_q
- * says).  Every buffer may be host memory or memory of the context's device.  Built for n_q <= 4096, 2 max_order <= n_delta <= 4096
- * and at most 64 extracted orders; beyond that MTIP_EINVAL with a message in mtip_last_error. */
+ * says).  Every buffer may be host memory or memory of the context's device.  Two entry points with one parameter list:
+ *   mtip_op_cc_to_deg2:      n_q <= 4096, 2 max_order <= n_delta <= 4096 and at most 64 extracted orders (max_order <= 127 at
+ *                            stride 2, <= 63 at stride 1): one harmonic per lane of a wave;
+ *   mtip_op_cc_to_deg2_wide: n_q <= 4096, 2 max_order <= n_delta <= 4096, max_order <= 128 and at most 129 extracted orders (the
+ *                            limits of the inverse, mtip_op_deg2_to_cc): up to three harmonics per lane, the kernel instantiation
+ *                            chosen from the number of extracted orders; with at most 64 of them it launches the kernel of the
+ *                            first entry and returns the same bits.
+ * Beyond its limits either returns MTIP_EINVAL with a message in mtip_last_error (the entry, its limits, the values it got) and
+ * leaves b_out untouched. */
 #define MTIP_CC_SUBTRACT_AVERAGE 1u
 #define MTIP_CC_PI_PERIODICITY 2u
 #define MTIP_CC_Q1Q2_SYMMETRIC 4u
 int mtip_op_cc_to_deg2(mtip_ctx* ctx, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
                        const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
                        mtip_cdouble* b_out);
+int mtip_op_cc_to_deg2_wide(mtip_ctx* ctx, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
+                            const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
+                            mtip_cdouble* b_out);
 /* The same step for MASKED data (csrc/k_extract_lsq.h); mtip_op_cc_to_deg2 above stays the unmasked operator.
  * mtip_op_cc_prepare_masked: modify_cross_correlation (235-289) with a mask.  cc, cc_out (n_q, n_q, n_delta) float64; cc_mask,
  * mask_out the same shape, uint8, 1 = keep; the outputs must not alias the inputs.  flags, in the reference's order:

@@ -590,13 +590,23 @@ extern "C" int mtip_op_symmetric_eig(mtip_ctx* c, int n, int n_mat, const double
 //   C_m = (1/n) (sum_d E[d] cos(2 pi m' d / n') - i sum_d O[d] sin(2 pi m' d / n')),  d = 0 .. floor(n'/2)
 // The twiddles come from a table of n' entries made on the host in extended precision, indexed by (m' d) mod n' (kept by
 // addition); it sits in LDS up to CX_TW_LDS entries and in global memory (L2) beyond.
+//
+// More than 64 harmonics (k_cc_deg2<HM>, HM = 1, 2, 3 slots per lane): lane j owns the harmonic indices j, j + 64, j + 128, each with
+// its own sums, twiddle index and 1 / c_l^l; one v_readlane of a sample feeds all HM slots.  Order index li lives in slot li >> 6,
+// lane li & 63.  The back-substitution walks the slots from the highest down (the slot is wave-uniform and unrolled at compile time:
+// no register is indexed dynamically); when order li is solved every lane of the slots below and the lanes below li & 63 of its own
+// slot subtract, reading the Legendre row at m = slot * 64 + lane (consecutive lanes, consecutive addresses).  HM = 1 is the kernel
+// as it was before the slots; mtip_op_cc_to_deg2 launches only that one, mtip_op_cc_to_deg2_wide picks HM from the number of orders.
 
 #define CX_WAVES 4
 #define CX_PW 4                        // pairs per wave (register block)
 #define CX_TP (CX_WAVES * CX_PW)       // pairs per workgroup
 #define CX_DC 64                       // folded samples per register chunk: one per lane
 #define CX_TW_LDS 1024                 // twiddle entries held in LDS
-#define CX_MAX_M 64                    // harmonics per pair: one lane each
+#define CX_MAX_M 64                    // harmonics per pair and slot: one lane each
+#define CX_MAX_HM 3                    // slots per lane of the widest instantiation
+#define CX_WIDE_MAX_ORDER 128          // mtip_op_cc_to_deg2_wide: the limit of its inverse mtip_op_deg2_to_cc
+#define CX_WIDE_MAX_M (CX_WIDE_MAX_ORDER + 1)
 #define CX_MAX_NQ 4096
 #define CX_MAX_ND 4096
 
@@ -658,8 +668,9 @@ __device__ __forceinline__ double cx_lane(double v, int src) {
     return __hiloint2double(hi, lo);
 }
 
+template <int HM>
 __global__ void __launch_bounds__(CX_WAVES * 64) k_cc_deg2(CcArgs a) {
-    __shared__ double2 s_buf[CX_MAX_M * CX_TP];        // B of (order slot, pair) on its way out
+    HIP_DYNAMIC_SHARED(double2, s_buf)                 // HM * CX_MAX_M * CX_TP: B of (order index, pair) on its way out
     __shared__ double2 s_tw[CX_TW_LDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q1 = blockIdx.y, q2base = blockIdx.x * CX_TP, q2w = q2base + wave * CX_PW;
@@ -667,10 +678,15 @@ __global__ void __launch_bounds__(CX_WAVES * 64) k_cc_deg2(CcArgs a) {
     if (tw_lds)
         for (int k = tid; k < a.np; k += CX_WAVES * 64) s_tw[k] = a.tw[k];
     __syncthreads();
-    const int mp = lane < a.n_m ? lane * a.mstep : 0;  // m' of this lane
-    int k = 0;                                         // (m' d) mod n'
+    int mp[HM], k[HM];                                 // m' of this lane's slots, and (m' d) mod n'
+#pragma unroll
+    for (int s = 0; s < HM; ++s) {
+        const int mi = s * CX_MAX_M + lane;
+        mp[s] = mi < a.n_m ? mi * a.mstep : 0;
+        k[s] = 0;
+    }
     // A chunk of 64 folded samples lives in the registers of the wave, sample c0 + lane in lane `lane`; the sums read it lane by lane.
-    double E[CX_PW], O[CX_PW], En[CX_PW], On[CX_PW], re[CX_PW], im[CX_PW], shift[CX_PW];
+    double E[CX_PW], O[CX_PW], En[CX_PW], On[CX_PW], re[HM][CX_PW], im[HM][CX_PW], shift[CX_PW];
 #pragma unroll
     for (int p = 0; p < CX_PW; ++p) cx_load(a, q1, q2w + p, lane, E[p], O[p]);
     // A constant taken off the samples leaves every harmonic m != 0 unchanged (the twiddles of a full period sum to zero) and m = 0
@@ -686,7 +702,8 @@ __global__ void __launch_bounds__(CX_WAVES * 64) k_cc_deg2(CcArgs a) {
                 sw += __shfl_xor(sw, o);
             }
             shift[p] = se / sw;
-            re[p] = im[p] = 0.0;
+#pragma unroll
+            for (int s = 0; s < HM; ++s) re[s][p] = im[s][p] = 0.0;
         }
     }
     for (int c0 = 0; c0 < a.nfold; c0 += CX_DC) {
@@ -699,13 +716,21 @@ __global__ void __launch_bounds__(CX_WAVES * 64) k_cc_deg2(CcArgs a) {
         for (int p = 0; p < CX_PW; ++p) E[p] -= wd * shift[p];
         const int lim = min(CX_DC, a.nfold - c0);
         for (int dd = 0; dd < lim; ++dd) {
-            const double2 t = tw_lds ? s_tw[k] : a.tw[k];
-            k += mp;
-            if (k >= a.np) k -= a.np;
+            double2 t[HM];
+#pragma unroll
+            for (int s = 0; s < HM; ++s) {
+                t[s] = tw_lds ? s_tw[k[s]] : a.tw[k[s]];
+                k[s] += mp[s];
+                if (k[s] >= a.np) k[s] -= a.np;
+            }
 #pragma unroll
             for (int p = 0; p < CX_PW; ++p) {
-                re[p] += cx_lane(E[p], dd) * t.x;
-                im[p] -= cx_lane(O[p], dd) * t.y;
+                const double e = cx_lane(E[p], dd), o = cx_lane(O[p], dd);     // one broadcast feeds every slot
+#pragma unroll
+                for (int s = 0; s < HM; ++s) {
+                    re[s][p] += e * t[s].x;
+                    im[s][p] -= o * t[s].y;
+                }
             }
         }
         if (more)
@@ -717,50 +742,72 @@ __global__ void __launch_bounds__(CX_WAVES * 64) k_cc_deg2(CcArgs a) {
     }
 #pragma unroll
     for (int p = 0; p < CX_PW; ++p) {
-        if (lane == 0) re[p] += shift[p] * (double)a.np;
-        re[p] *= a.inv_n;
-        im[p] *= a.inv_n;
+        if (lane == 0) re[0][p] += shift[p] * (double)a.np;                     // m = 0: slot 0, lane 0
+#pragma unroll
+        for (int s = 0; s < HM; ++s) {
+            re[s][p] *= a.inv_n;
+            im[s][p] *= a.inv_n;
+        }
     }
     if (a.backsub) {
         // B_l = C_l / c_l^l,  C_m -= B_l c_l^m (m < l),  c_l^m = P_l^m(q1) P_l^m(q2) / (2 l + 1)   (fxs_invariant_tools.py:629-632)
-        // lane li prepares 1 / c_l^l of its own order once: one division per pair instead of one per pair and order
+        // lane li prepares 1 / c_l^l of its own orders once: one division per pair instead of one per pair and order
         const double* leg1 = a.leg + (size_t)q1 * a.ntri;
-        double rdiag[CX_PW];
-        {
-            const int dg = lane * (lane + 1) / 2 + lane;
-            const bool act = lane < a.n_m;
+        double rdiag[HM][CX_PW];
+#pragma unroll
+        for (int s = 0; s < HM; ++s) {
+            const int mi = s * CX_MAX_M + lane;
+            const int dg = mi * (mi + 1) / 2 + mi;
+            const bool act = mi < a.n_m;
             const double p1 = act ? leg1[dg] : 1.0;
 #pragma unroll
             for (int p = 0; p < CX_PW; ++p) {
                 const int q2 = min(q2w + p, a.nq - 1);
                 const double p2 = act ? a.leg[(size_t)q2 * a.ntri + dg] : 1.0;
-                rdiag[p] = 1.0 / (p1 * p2 / (double)(2 * lane * a.stride + 1));
+                rdiag[s][p] = 1.0 / (p1 * p2 / (double)(2 * mi * a.stride + 1));
             }
         }
-        for (int li = a.n_m - 1; li >= 0; --li) {
-            const int tri = li * (li + 1) / 2;
-            const double inv_norm = 1.0 / (double)(2 * li * a.stride + 1);
-            const bool act = lane < li;
-            const double p1 = act ? leg1[tri + lane] * inv_norm : 0.0;
+        // the slots from the highest down; `so` is a compile-time constant in every copy of the body
 #pragma unroll
-            for (int p = 0; p < CX_PW; ++p) {
-                const int q2 = min(q2w + p, a.nq - 1);
-                const double cm = act ? p1 * a.leg[(size_t)q2 * a.ntri + tri + lane] : 0.0;
-                const double r = cx_lane(rdiag[p], li);
-                const double br = cx_lane(re[p], li) * r, bi = cx_lane(im[p], li) * r;
-                if (act) {
-                    re[p] -= br * cm;
-                    im[p] -= bi * cm;
-                } else if (lane == li) {
-                    re[p] = br;
-                    im[p] = bi;
+        for (int so = HM - 1; so >= 0; --so) {
+            for (int li = min(a.n_m, (so + 1) * CX_MAX_M) - 1; li >= so * CX_MAX_M; --li) {
+                const int ll = li - so * CX_MAX_M;                                  // the owner's lane (wave-uniform)
+                const int tri = li * (li + 1) / 2;
+                const double inv_norm = 1.0 / (double)(2 * li * a.stride + 1);
+                // every lane of the slots below subtracts; in the owner's slot the lanes below ll
+                double p1[HM];
+#pragma unroll
+                for (int s = 0; s < HM; ++s)
+                    if (s <= so) p1[s] = (s < so || lane < ll) ? leg1[tri + s * CX_MAX_M + lane] * inv_norm : 0.0;
+#pragma unroll
+                for (int p = 0; p < CX_PW; ++p) {
+                    const int q2 = min(q2w + p, a.nq - 1);
+                    const double r = cx_lane(rdiag[so][p], ll);
+                    const double br = cx_lane(re[so][p], ll) * r, bi = cx_lane(im[so][p], ll) * r;
+#pragma unroll
+                    for (int s = 0; s < HM; ++s)
+                        if (s <= so) {
+                            const bool act = s < so || lane < ll;
+                            const double cm = act ? p1[s] * a.leg[(size_t)q2 * a.ntri + tri + s * CX_MAX_M + lane] : 0.0;
+                            if (act) {
+                                re[s][p] -= br * cm;
+                                im[s][p] -= bi * cm;
+                            } else if (s == so && lane == ll) {
+                                re[s][p] = br;
+                                im[s][p] = bi;
+                            }
+                        }
                 }
             }
         }
     }
-    if (lane < a.n_m)
 #pragma unroll
-        for (int p = 0; p < CX_PW; ++p) s_buf[lane * CX_TP + wave * CX_PW + p] = make_double2(re[p], im[p]);
+    for (int s = 0; s < HM; ++s) {
+        const int mi = s * CX_MAX_M + lane;
+        if (mi < a.n_m)
+#pragma unroll
+            for (int p = 0; p < CX_PW; ++p) s_buf[mi * CX_TP + wave * CX_PW + p] = make_double2(re[s][p], im[s][p]);
+    }
     __syncthreads();
     // every order 0 .. n_out - 1 is written: the ones that were not extracted as zeros (fxs_invariant_tools.py:417-419)
     for (int idx = tid; idx < a.n_out * CX_TP; idx += CX_WAVES * 64) {
@@ -772,19 +819,27 @@ __global__ void __launch_bounds__(CX_WAVES * 64) k_cc_deg2(CcArgs a) {
     }
 }
 
-extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
-                                  const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
-                                  mtip_cdouble* b_out) {
+template <int HM>
+static void launch_cc_deg2(mtip_ctx* c, const CcArgs& a) {
+    const size_t lds = (size_t)HM * CX_MAX_M * CX_TP * sizeof(double2);
+    hipLaunchKernelGGL((k_cc_deg2<HM>), dim3((unsigned)div_up(a.nq, CX_TP), (unsigned)a.nq), dim3(CX_WAVES * 64), lds, c->stream, a);
+}
+
+// the body of both entry points: `wide` only moves the limit on the extracted orders (and names the entry in the messages)
+static int cc_to_deg2_entry(mtip_ctx* c, bool wide, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
+                            const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
+                            mtip_cdouble* b_out) {
     if (!c) return MTIP_EINVAL;
-    char msg[320];
+    char msg[400];
+    const std::string name = wide ? "cc_to_deg2_wide: " : "cc_to_deg2: ";
     const int s = order_stride;
     const int n_m = (s == 1 || s == 2) && max_order >= 0 ? max_order / s + 1 : 0;
     if (!cc || !b_out || (dimensions != 2 && dimensions != 3) || (s != 1 && s != 2) || max_order < 0 || n_q < 1 || n_delta < 2 ||
         (flags & ~(uint32_t)(MTIP_CC_SUBTRACT_AVERAGE | MTIP_CC_PI_PERIODICITY | MTIP_CC_Q1Q2_SYMMETRIC))) {
-        c->err = "cc_to_deg2: null buffer, dimensions not 2 or 3, order stride not 1 or 2, or unknown flag";
+        c->err = name + "null buffer, dimensions not 2 or 3, order stride not 1 or 2, or unknown flag";
         return MTIP_EINVAL;
     }
-    if (n_q > CX_MAX_NQ || n_delta > CX_MAX_ND || n_m > CX_MAX_M || n_delta < 2 * max_order) {
+    if (!wide && (n_q > CX_MAX_NQ || n_delta > CX_MAX_ND || n_m > CX_MAX_M || n_delta < 2 * max_order)) {
         snprintf(msg, sizeof msg,
                  "cc_to_deg2: built for n_q <= %d, 2 max_order <= n_delta <= %d and at most %d extracted orders (max_order <= %d at "
                  "stride 2, <= %d at stride 1); got n_q = %d, n_delta = %d, max_order = %d, stride = %d",
@@ -792,13 +847,21 @@ extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_ord
         c->err = msg;
         return MTIP_EINVAL;
     }
+    if (wide && (n_q > CX_MAX_NQ || n_delta > CX_MAX_ND || max_order > CX_WIDE_MAX_ORDER || n_m > CX_WIDE_MAX_M || n_delta < 2 * max_order)) {
+        snprintf(msg, sizeof msg,
+                 "cc_to_deg2_wide: built for n_q <= %d, 2 max_order <= n_delta <= %d, max_order <= %d and at most %d extracted orders; "
+                 "got n_q = %d, n_delta = %d, max_order = %d, stride = %d (%d extracted orders)",
+                 CX_MAX_NQ, CX_MAX_ND, CX_WIDE_MAX_ORDER, CX_WIDE_MAX_M, n_q, n_delta, max_order, s, n_m);
+        c->err = msg;
+        return MTIP_EINVAL;
+    }
     if (((flags & MTIP_CC_SUBTRACT_AVERAGE) && !average_intensity) || ((flags & MTIP_CC_PI_PERIODICITY) && !bad_angles) ||
         (dimensions == 3 && !legendre)) {
-        c->err = "cc_to_deg2: a table the flags / dimensions ask for is null (average_intensity, bad_angles, legendre)";
+        c->err = name + "a table the flags / dimensions ask for is null (average_intensity, bad_angles, legendre)";
         return MTIP_EINVAL;
     }
     if ((flags & MTIP_CC_PI_PERIODICITY) && (n_delta & 1)) {
-        c->err = "cc_to_deg2: pi_periodicity needs an even number of angles (fxs_invariant_tools.py:265)";
+        c->err = name + "pi_periodicity needs an even number of angles (fxs_invariant_tools.py:265)";
         return MTIP_EINVAL;
     }
     (void)hipSetDevice(c->device);
@@ -830,7 +893,7 @@ extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_ord
     DevView v_out(c, b_out, nqq * a.n_out * sizeof(double2), false, true);
     for (DevView* v : {&v_cc, &v_avg, &v_bad, &v_leg, &v_tw, &v_out})
         if (v->err != hipSuccess) {
-            c->err = std::string("cc_to_deg2: ") + hipGetErrorString(v->err);
+            c->err = name + hipGetErrorString(v->err);
             return v->err == hipErrorOutOfMemory ? MTIP_ENOMEM : MTIP_EHIP;
         }
     a.cc = (const double*)v_cc.dev;
@@ -841,16 +904,33 @@ extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_ord
     a.out = (double2*)v_out.dev;
     {
         ProfScope ps(c, "cc_deg2");
-        hipLaunchKernelGGL(k_cc_deg2, dim3((unsigned)div_up(n_q, CX_TP), (unsigned)n_q), dim3(CX_WAVES * 64), 0, c->stream, a);
+        static_assert(CX_WIDE_MAX_M <= CX_MAX_HM * CX_MAX_M, "the widest instantiation holds every order of the wide entry");
+        if (n_m <= CX_MAX_M) launch_cc_deg2<1>(c, a);                 // (the checks above leave the narrow entry nothing else)
+        else if (n_m <= 2 * CX_MAX_M) launch_cc_deg2<2>(c, a);
+        else launch_cc_deg2<3>(c, a);
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = v_out.finish();
     if (e != hipSuccess) {
-        c->err = std::string("cc_to_deg2: ") + hipGetErrorString(e);
+        c->err = name + hipGetErrorString(e);
         return MTIP_EHIP;
     }
     return MTIP_OK;
+}
+
+extern "C" int mtip_op_cc_to_deg2(mtip_ctx* c, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
+                                  const double* cc, const double* average_intensity, const uint8_t* bad_angles, const double* legendre,
+                                  mtip_cdouble* b_out) {
+    return cc_to_deg2_entry(c, false, n_q, n_delta, max_order, order_stride, dimensions, flags, cc, average_intensity, bad_angles, legendre,
+                            b_out);
+}
+
+extern "C" int mtip_op_cc_to_deg2_wide(mtip_ctx* c, int n_q, int n_delta, int max_order, int order_stride, int dimensions, uint32_t flags,
+                                       const double* cc, const double* average_intensity, const uint8_t* bad_angles,
+                                       const double* legendre, mtip_cdouble* b_out) {
+    return cc_to_deg2_entry(c, true, n_q, n_delta, max_order, order_stride, dimensions, flags, cc, average_intensity, bad_angles, legendre,
+                            b_out);
 }
 
 // ---- masked cross-correlation data: modify_cross_correlation with a mask, and B_l by least squares ----------------------

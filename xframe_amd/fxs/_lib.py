@@ -161,6 +161,7 @@ _SIGNATURES = {
     'mtip_op_hermitian_eig': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
     'mtip_op_symmetric_eig': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
     'mtip_op_cc_to_deg2': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, c_void, c_void, c_void, c_void, c_void]),
+    'mtip_op_cc_to_deg2_wide': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_cc_prepare_masked': (C.c_int, [c_void, C.c_int, C.c_int, C.c_uint32, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_cc_lstsq_deg2': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_deg2_to_cc': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void]),

@@ -353,9 +353,10 @@ class Engine(_lib.TensorOperands):
 
     # ------------------------------------------------------------------ extract: cross-correlation -> B_l (fxs_invariant_tools.py:578-645, 813-839)
     def cc_to_deg2(self, cc, max_order, order_stride=2, dimensions=3, legendre=None, average_intensity=None, bad_angles=None,
-                   q1q2_symmetric=False):
-        """mtip_op_cc_to_deg2: cc (Nq, Nq, n_delta) float64, a numpy array or a torch tensor on this engine's device (then B_l
-        comes back as a tensor on it).  Returns B_l (max_order + 1, Nq, Nq) complex128, the orders that are not multiples of
+                   q1q2_symmetric=False, wide=False):
+        """mtip_op_cc_to_deg2 (at most 64 extracted orders), with wide=True mtip_op_cc_to_deg2_wide (max_order <= 128, at most 129
+        extracted orders; the same kernel and the same bits up to 64): cc (Nq, Nq, n_delta) float64, a numpy array or a torch tensor
+        on this engine's device (then B_l comes back as a tensor on it).  Returns B_l (max_order + 1, Nq, Nq) complex128, the orders that are not multiples of
         order_stride as zeros.  legendre: (Nq, n_m (n_m + 1) / 2) table for dimensions 3 (``extract.legendre_table``);
         average_intensity (Nq): subtract_average_intensity; bad_angles (n_delta) bool: pi_periodicity."""
         on_device = not isinstance(cc, np.ndarray) and hasattr(cc, 'data_ptr')
@@ -393,8 +394,9 @@ class Engine(_lib.TensorOperands):
         else:
             out = np.empty(shape, complex)
             p_in, p_out = _lib.ptr(cc), _lib.ptr(out)
-        self._ck(self.lib.mtip_op_cc_to_deg2(self.ctx, nq, nd, int(max_order), int(order_stride), int(dimensions), flags, p_in,
-                                             _lib.ptr(avg), _lib.ptr(bad), _lib.ptr(leg), p_out))
+        entry = self.lib.mtip_op_cc_to_deg2_wide if wide else self.lib.mtip_op_cc_to_deg2
+        self._ck(entry(self.ctx, nq, nd, int(max_order), int(order_stride), int(dimensions), flags, p_in, _lib.ptr(avg), _lib.ptr(bad),
+                       _lib.ptr(leg), p_out))
         return out
 
     # ------------------------------------------------------------------ simulate_ccd: B_l -> cross-correlation (fxs_invariant_tools.py:934-1001)

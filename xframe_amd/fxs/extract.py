@@ -189,6 +189,13 @@ def legendre_table(radial_points, xray_wavelength, max_order, stride):
     return np.ascontiguousarray(sph_plm((li * stride)[None, :], (mi * stride)[None, :], x[:, None]))
 
 
+_NARROW_ENTRY_ORDERS = 64              # what mtip_op_cc_to_deg2 extracts; more go to mtip_op_cc_to_deg2_wide (up to 129, max_order <= 128)
+
+
+def _wants_wide_entry(max_order, stride):
+    return int(max_order) // int(stride) + 1 > _NARROW_ENTRY_ORDERS
+
+
 def _check_cc_options(metadata, dim):
     mask_type = (metadata.get('cc_mask') or {'type': 'none'}).get('type', 'none')
     if mask_type != 'none':
@@ -240,7 +247,8 @@ def cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
     stride = 2 if metadata['assume_zero_odd_orders'] else 1
     if dim == 3:
         kw['legendre'] = legendre_table(data_grid['qs'], metadata['xray_wavelength'], max_order, stride)
-    b = engine.cc_to_deg2(cc, max_order, order_stride=stride, dimensions=dim, q1q2_symmetric=bool(mod.get('q1q2_symmetric', False)), **kw)
+    b = engine.cc_to_deg2(cc, max_order, order_stride=stride, dimensions=dim, q1q2_symmetric=bool(mod.get('q1q2_symmetric', False)),
+                          wide=_wants_wide_entry(max_order, stride), **kw)
     if not isinstance(b, np.ndarray):
         b = b.cpu().numpy()
     return b, np.ones(b.shape[1:], dtype=bool)
@@ -399,7 +407,7 @@ def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
     stride = 2 if metadata['assume_zero_odd_orders'] else 1
     if mode == 'back_substitution':
         leg = legendre_table(qs, metadata['xray_wavelength'], max_order, stride)
-        b = engine.cc_to_deg2(cc2, max_order, order_stride=stride, dimensions=3, legendre=leg)
+        b = engine.cc_to_deg2(cc2, max_order, order_stride=stride, dimensions=3, legendre=leg, wide=_wants_wide_entry(max_order, stride))
         return np.asarray(b), np.asarray(mask2).all(-1)                                                  # 609
     extracted = np.arange(0, max_order + 1, stride)                                                      # orders[order_mask], 396-399
     thetas = np.arccos(qs * metadata['xray_wavelength'] / (4 * np.pi))                                   # 471, physicsLibrary.py:94-95
