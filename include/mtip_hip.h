@@ -388,7 +388,7 @@ int mtip_op_deg2_to_cc(mtip_ctx* ctx, int n_q, int max_order, int n_delta, int d
  * divides the image by it; factor (n_q, n_phi) or NULL: polarisation x solid-angle table (565-591) multiplied in afterwards.
  * shared_mask: the mask is the same for every pattern (ignored with a filter, which makes it per pattern): masks is then
  * (n_q, n_phi), the mask of the first batch is the handle's, and its pair counts M are computed once.
- * q1_pos (n_q1), q2_pos (n_q2): the selected rings.  n_phi: 16, 32, .. 1024 (a power of two).
+ * q1_pos (n_q1), q2_pos (n_q2): the selected rings.  n_phi: 16, 32, .. 1024 (a power of two; more through mtip_correlate_create_ex).
  * Per good pattern  sum += D / M, count += 1  where |M| >= 0.5, with D = irfft(conj F[q1] F[q2]), M = irfft(conj G[q1] G[q2]),
  * F = rfft(image), G = rfft(mask).  (The reference tests M != 0 on a rounded integer: the one deliberate deviation.)
  * Every buffer of add / get_partial / merge / finalize may be host memory or memory of the context's device. */
@@ -400,6 +400,15 @@ typedef struct {
 } mtip_correlate_cfg;
 mtip_correlate* mtip_correlate_create(mtip_ctx* ctx, const mtip_correlate_cfg* cfg, const int32_t* q1_pos, const int32_t* q2_pos,
                                       const double* factor);
+/* create with flags.  0: mtip_correlate_create.  MTIP_CORRELATE_GENERAL_NPHI: n_phi is any even length in 16 .. 2048 whose only prime
+ * factors are 2, 3 and 5 (1536, the reference's default, 1920, 2000, 2048 ..): mixed-radix transforms (radices 4, 2, 3, 5) by a plan
+ * made once per handle; a power of two up to 1024 runs the same kernels as without the flag and gives the same bits.  A refused
+ * length (odd, below 16, above 2048, a prime factor above 5) is a null return whose message states the rule and the nearest accepted
+ * lengths below and above; so is any other flag bit (the message names `flags`).  add, add_detector, get_partial, merge and finalize
+ * take either kind of handle. */
+#define MTIP_CORRELATE_GENERAL_NPHI 1u
+mtip_correlate* mtip_correlate_create_ex(mtip_ctx* ctx, const mtip_correlate_cfg* cfg, const int32_t* q1_pos, const int32_t* q2_pos,
+                                         const double* factor, uint32_t flags);
 void mtip_correlate_destroy(mtip_correlate* h);
 /* one batch: flags and waxs rows are decided on the device and kept by the handle; patterns are accumulated in pattern order, so
  * the same patterns give bit-identical sum and count however they are split into batches */

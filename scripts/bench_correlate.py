@@ -5,7 +5,11 @@ in a synchronise; five windows after a warm-up: median, min .. max), and inside 
 families corr_ring (k_corr_stats + k_corr_ring) and corr_pair (k_corr_pair).  Derived, with the counts stated where they are printed:
 the achieved FFT rate of k_corr_pair against the fp64 vector peak, and the accumulator bytes per pattern against HBM.
 The numpy restatement of the route (tests/correlate_cases.r_correlate) on this host with 1 and with 8 processes, as context.
-usage: python scripts/bench_correlate.py [--small]          (--small: the small shape only)"""
+usage: python scripts/bench_correlate.py [--small] [--n-phi N [--rings R]]
+  --small       the small shape only
+  --n-phi N     one shape only: R rings (default 256) x N angles.  A length the radix-2 kernels do not take (1536, the default settings'
+                length, 1920, 2000, 2048 ..) goes through a handle made with general_n_phi=True (k_corr_pair_g, csrc/k_correlate_mr.h);
+                the operation count 5 m log2 m is kept for it as the convention the rates are stated in."""
 import multiprocessing as mp
 import os
 import sys
@@ -75,18 +79,22 @@ def main():
     from xframe_amd.fxs.engine import Engine
     e = Engine({'grid': {'n_radial_points': 8, 'max_order': 2}}, None, n_batch=1, max_q=1.0)
     shapes = ((64, 256),) if '--small' in sys.argv else ((256, 1024), (64, 256))
+    if '--n-phi' in sys.argv:
+        rings = int(sys.argv[sys.argv.index('--rings') + 1]) if '--rings' in sys.argv else 256
+        shapes = ((rings, int(sys.argv[sys.argv.index('--n-phi') + 1])),)
     for n_q, n_phi in shapes:
         settings = settings_for(n_q, n_phi)
+        general = n_phi not in CR.SUPPORTED_N_PHI
         images, masks = patterns(n_q, n_phi, max(BATCHES))
         d_img = torch.from_numpy(images).cuda()
         d_mask = torch.from_numpy(masks).cuda()
         n_acc = n_q * n_q * n_phi
-        print('%d rings x %d angles, %d x %d pairs: accumulator %.1f MB (sum f64 + count int32), shared-mask table %.1f MB' %
-              (n_q, n_phi, n_q, n_q, 12e-6 * n_acc, 8e-6 * n_acc))
+        print('%d rings x %d angles%s, %d x %d pairs: accumulator %.1f MB (sum f64 + count int32), shared-mask table %.1f MB' %
+              (n_q, n_phi, ' (general_n_phi: mixed-radix kernels)' if general else '', n_q, n_q, 12e-6 * n_acc, 8e-6 * n_acc))
         for shared in (True, False):
             per_pattern = {}
             for B in BATCHES:
-                c = CR.Correlator(e, settings, shared_mask=shared)
+                c = CR.Correlator(e, settings, shared_mask=shared, general_n_phi=general)
                 m = d_mask[0] if shared else d_mask[:B]
                 t0 = time.perf_counter()
                 c.add(d_img[:B], m)                                    # warm-up (code objects, the shared mask's table)
@@ -124,7 +132,8 @@ def main():
             print('  %s mask: ms per pattern at batch 1 / 8 / 32 = %.3f / %.3f / %.3f  (batch 32 below batch 1: %s)' %
                   ('shared' if shared else 'per-pattern', per_pattern[1], per_pattern[8], per_pattern[32], per_pattern[32] < per_pattern[1]))
         del d_img, d_mask
-        cpu_context(n_q, n_phi, 1 if n_q >= 256 else 8)
+        if '--n-phi' not in sys.argv:                                  # (a single shape is asked for the device figures alone)
+            cpu_context(n_q, n_phi, 1 if n_q >= 256 else 8)
     e.close()
 
 

@@ -13,6 +13,14 @@
 //                  n_phi / 2 points (even samples in the real part, odd ones in the imaginary part) in a wave-private piece of
 //                  LDS: the lanes of one wave hand data to each other there, so no workgroup barrier is inside the loop.
 //   k_corr_final   ccf = sum / count (NaN where count = 0), symmetrize_ccf, fft(ccf)[..., :fc_n_max]
+// These take n_phi = 16, 32, .. 1024: their three transforms are radix 2.  A handle made by mtip_correlate_create_ex with
+// MTIP_CORRELATE_GENERAL_NPHI takes every even n_phi in 16 .. 2048 with no prime factor above 5 (1536, the reference's default, among
+// them): k_corr_ring_g / k_corr_pair_g / k_corr_final_g are the same kernel bodies with the mixed-radix transforms of k_correlate_mr.h
+// (radices 4, 2, 3, 5 by a plan made once per handle).  The pair kernel keeps its shape there: a wave per pair, sum and count in
+// registers across the chunk, the transform in a wave-private piece of LDS with no workgroup barrier in the pattern loop; rows of
+// 64 lanes may be partial (n_phi / 2 need not be a multiple of 64, nor even), its LDS is dynamic (49 n_phi bytes: 98 KB at 2048).
+// Such a handle with a power of two up to 1024 launches the radix-2 kernels.  Still refused: odd lengths, lengths below 16 or
+// above 2048, prime factors above 5.
 //
 // THE ONE DEVIATION from the reference: it tests M != 0 on a value that is an integer pair count plus FFT rounding, and so divides
 // noise by noise where the true count is 0 without a whole ring being masked.  Here the test is |M| >= 0.5: masks are 0 / 1, M is an
@@ -31,10 +39,15 @@
 #define COR_MODE_SHARED 1              // M read from the handle's table
 #define COR_MODE_MASK_ONLY 2           // fill that table
 
+#include "k_correlate_mr.h"
+
 struct mtip_correlate {
     mtip_ctx* c = nullptr;
     mtip_correlate_cfg cfg{};
     int m = 0, log2n = 0;              // n_phi / 2
+    bool general = false;              // the mixed-radix kernels (create_ex with MTIP_CORRELATE_GENERAL_NPHI, n_phi not 16, 32, .. 1024)
+    CorPlanArgs pl_n{}, pl_m{};        // their plans for n_phi and for n_phi / 2 points
+    DevBuf<uint16_t> d_perm;           // the two digit-reversal tables: n_phi entries, then n_phi / 2
     size_t n_acc = 0;                  // n_q1 n_q2 n_phi
     DevBuf<double> d_sum;
     DevBuf<int> d_cnt;
@@ -42,7 +55,7 @@ struct mtip_correlate {
     bool have_M = false;
     DevBuf<int> d_q1, d_q2;
     DevBuf<double> d_factor;           // (n_q, n_phi) polarisation x solid angle
-    DevBuf<double2> d_tw;              // exp(-2 pi i k / n_phi), k < n_phi / 2
+    DevBuf<double2> d_tw;              // exp(-2 pi i k / n_phi), k < n_phi / 2 (general: k < n_phi)
     DevBuf<double2> d_F, d_G;          // (COR_CHUNK, n_q, m + 1)
     DevBuf<uint8_t> d_mw;              // (COR_CHUNK, n_q, n_phi) filtered masks
     DevBuf<double> d_rc, d_rs;         // (COR_CHUNK, n_q) ring mask counts / masked ring sums
@@ -141,10 +154,21 @@ __global__ void __launch_bounds__(COR_RT) k_corr_stats(CorRingArgs a) {
     }
 }
 
+// where input point j of an n_phi-point transform is stored, and that transform: radix 2, or the handle's mixed-radix plan
+template <bool GEN>
+__device__ __forceinline__ int cor_store_pos(const CorPlanArgs* pl, int j, int log2n) {
+    if constexpr (GEN) return pl->perm[j];
+    else return cor_brev((unsigned)j, log2n);
+}
+template <bool GEN>
+__device__ __forceinline__ void cor_ring_fft(const CorPlanArgs* pl, double2* buf, int n, int log2n, const double2* tw, int tid) {
+    if constexpr (GEN) cor_block_fft_g(buf, pl->st, tw, tid, COR_RT);
+    else cor_block_fft(buf, n, log2n, tw, tid);
+}
+
 // correlate.py:416-450 for one ring of one pattern, then rfft of the image and of the mask along phi
-__global__ void __launch_bounds__(COR_RT) k_corr_ring(CorRingArgs a) {
-    __shared__ double2 s_buf[COR_MAX_NPHI];
-    __shared__ double s_red[COR_WAVES];
+template <bool GEN>
+__device__ __forceinline__ void cor_ring_body(const CorRingArgs a, const CorPlanArgs* pl, double2* s_buf, double* s_red) {
     const int tid = threadIdx.x, q = blockIdx.x, p = blockIdx.y, m = a.n_phi >> 1;
     const uint8_t* mrow = a.filter ? a.mw + ((size_t)p * a.n_q + q) * a.n_phi : a.mask + (size_t)p * a.mask_stride + (size_t)q * a.n_phi;
     if (a.img != nullptr) {
@@ -181,7 +205,7 @@ __global__ void __launch_bounds__(COR_RT) k_corr_ring(CorRingArgs a) {
             if (a.roi_norm) v = v / roi_mean;                           // 431-432
             if (frow) v *= frow[j];                                     // 434-438
             if (mrow[j]) ws += v;
-            s_buf[cor_brev((unsigned)j, a.log2n)] = make_double2(v, 0.0);
+            s_buf[cor_store_pos<GEN>(pl, j, a.log2n)] = make_double2(v, 0.0);
         }
         ws = cor_block_sum(ws, s_red, tid);
         if (tid == 0) {
@@ -189,17 +213,27 @@ __global__ void __launch_bounds__(COR_RT) k_corr_ring(CorRingArgs a) {
             if (q == 0) a.good[p] = good;
         }
         if (!good) return;                                              // the pair kernel skips the pattern
-        cor_block_fft(s_buf, a.n_phi, a.log2n, a.tw, tid);
+        cor_ring_fft<GEN>(pl, s_buf, a.n_phi, a.log2n, a.tw, tid);
         double2* F = a.F + ((size_t)p * a.n_q + q) * (m + 1);
         for (int k = tid; k <= m; k += COR_RT) F[k] = s_buf[k];
         __syncthreads();
     }
     if (a.do_G) {
-        for (int j = tid; j < a.n_phi; j += COR_RT) s_buf[cor_brev((unsigned)j, a.log2n)] = make_double2(mrow[j] ? 1.0 : 0.0, 0.0);
-        cor_block_fft(s_buf, a.n_phi, a.log2n, a.tw, tid);
+        for (int j = tid; j < a.n_phi; j += COR_RT) s_buf[cor_store_pos<GEN>(pl, j, a.log2n)] = make_double2(mrow[j] ? 1.0 : 0.0, 0.0);
+        cor_ring_fft<GEN>(pl, s_buf, a.n_phi, a.log2n, a.tw, tid);
         double2* G = a.G + ((size_t)p * a.n_q + q) * (m + 1);
         for (int k = tid; k <= m; k += COR_RT) G[k] = s_buf[k];
     }
+}
+__global__ void __launch_bounds__(COR_RT) k_corr_ring(CorRingArgs a) {
+    __shared__ double2 s_buf[COR_MAX_NPHI];
+    __shared__ double s_red[COR_WAVES];
+    cor_ring_body<false>(a, nullptr, s_buf, s_red);
+}
+__global__ void __launch_bounds__(COR_RT) k_corr_ring_g(CorRingArgs a, CorPlanArgs pl) {
+    __shared__ double2 s_buf[COR_G_MAX_NPHI];
+    __shared__ double s_red[COR_WAVES];
+    cor_ring_body<true>(a, &pl, s_buf, s_red);
 }
 
 struct CorPairArgs {
@@ -260,12 +294,20 @@ __device__ __forceinline__ void cor_wave_irfft(double2* buf, const double2* s_tw
     MTIP_WAVE_LDS_SYNC();
 }
 
-template <int NPL>
-__global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair(CorPairArgs a) {
-    __shared__ double2 s_fft[COR_WAVES * (COR_MAX_NPHI / 2)];
-    __shared__ double2 s_tw[COR_MAX_NPHI / 2];
+// NPL: rows of 64 lanes that hold the m points of a pair (the last one may be partial).  GEN: s_tw has n_phi entries, s_perm the
+// plan's digit reversal of m points
+template <int NPL, bool GEN>
+__device__ __forceinline__ void cor_pair_irfft(double2* buf, const double2* s_tw, const uint16_t* s_perm, const CorPlanArgs* pl,
+                                               const double2* a1, const double2* a2, int m, int log2m, int lane, double* out) {
+    if constexpr (GEN) cor_wave_irfft_g<NPL>(buf, s_tw, s_perm, pl->st, a1, a2, m, lane, out);
+    else cor_wave_irfft<NPL>(buf, s_tw, a1, a2, m, log2m, lane, out);
+}
+template <int NPL, bool GEN>
+__device__ __forceinline__ void cor_pair_body(const CorPairArgs a, const CorPlanArgs* pl, double2* s_fft, double2* s_tw, uint16_t* s_perm) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), m = a.m;
-    for (int k = tid; k < m; k += COR_WAVES * 64) s_tw[k] = a.tw[k];
+    for (int k = tid; k < (GEN ? 2 * m : m); k += COR_WAVES * 64) s_tw[k] = a.tw[k];
+    if constexpr (GEN)
+        for (int k = tid; k < m; k += COR_WAVES * 64) s_perm[k] = pl->perm[k];
     __syncthreads();
     double2* buf = s_fft + wave * m;
     const size_t row_len = (size_t)(m + 1), pat_len = (size_t)a.n_q * row_len;
@@ -280,7 +322,7 @@ __global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair(CorPairArgs a) {
         double sum[2 * NPL], d[2 * NPL], mm[2 * NPL];
         int cnt[2 * NPL];
         if (a.mode == COR_MODE_MASK_ONLY) {
-            cor_wave_irfft<NPL>(buf, s_tw, a.G + r1, a.G + r2, m, a.log2m, lane, mm);
+            cor_pair_irfft<NPL, GEN>(buf, s_tw, s_perm, pl, a.G + r1, a.G + r2, m, a.log2m, lane, mm);
 #pragma unroll
             for (int r = 0; r < NPL; ++r) {
                 const int j = lane + 64 * r;
@@ -307,10 +349,10 @@ __global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair(CorPairArgs a) {
         for (int p = 0; p < a.P; ++p) {
             if (!a.good[p]) continue;                                   // bad patterns contribute nothing (correlate.py:347)
             const double2* Fp = a.F + (size_t)p * pat_len;
-            cor_wave_irfft<NPL>(buf, s_tw, Fp + r1, Fp + r2, m, a.log2m, lane, d);
+            cor_pair_irfft<NPL, GEN>(buf, s_tw, s_perm, pl, Fp + r1, Fp + r2, m, a.log2m, lane, d);
             if (a.mode == COR_MODE_PATTERN) {
                 const double2* Gp = a.G + (size_t)p * pat_len;
-                cor_wave_irfft<NPL>(buf, s_tw, Gp + r1, Gp + r2, m, a.log2m, lane, mm);
+                cor_pair_irfft<NPL, GEN>(buf, s_tw, s_perm, pl, Gp + r1, Gp + r2, m, a.log2m, lane, mm);
 #pragma unroll
                 for (int e = 0; e < 2 * NPL; ++e) mm[e] *= a.inv_n;
             }
@@ -331,6 +373,20 @@ __global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair(CorPairArgs a) {
         }
     }
 }
+template <int NPL>
+__global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair(CorPairArgs a) {
+    __shared__ double2 s_fft[COR_WAVES * (COR_MAX_NPHI / 2)];
+    __shared__ double2 s_tw[COR_MAX_NPHI / 2];
+    cor_pair_body<NPL, false>(a, nullptr, s_fft, s_tw, nullptr);
+}
+// dynamic LDS: twiddles (n_phi), COR_WAVES wave-private transforms (m each), the digit reversal (m uint16): cor_pair_lds bytes.  Four
+// waves are one per SIMD, so the 16 rows of n_phi = 2048 (64 accumulator doubles and 32 counts per lane) have the whole register file.
+template <int NPL>
+__global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair_g(CorPairArgs a, CorPlanArgs pl) {
+    HIP_DYNAMIC_SHARED(double2, sm)
+    cor_pair_body<NPL, true>(a, &pl, sm + 2 * a.m, sm, (uint16_t*)(sm + (2 + COR_WAVES) * a.m));
+}
+static inline size_t cor_pair_lds(int m) { return (size_t)(2 + COR_WAVES) * m * sizeof(double2) + (((size_t)m * sizeof(uint16_t) + 15) & ~(size_t)15); }
 
 __global__ void k_corr_merge(double* sum, int* cnt, const double* sum_in, const int* cnt_in, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -349,8 +405,8 @@ struct CorFinalArgs {
 };
 
 // correlate.py:258-270: sum / count with NaN where nothing was counted, symmetrize_ccf (cross_correlation.py:67-78), fft[..., :fc_n]
-__global__ void __launch_bounds__(COR_RT) k_corr_final(CorFinalArgs a) {
-    __shared__ double2 s_buf[COR_MAX_NPHI];
+template <bool GEN>
+__device__ __forceinline__ void cor_final_body(const CorFinalArgs& a, const CorPlanArgs* pl, double2* s_buf) {
     const int tid = threadIdx.x;
     const size_t row = (size_t)blockIdx.x * a.n_phi;
     for (int j = tid; j < a.n_phi; j += COR_RT) {
@@ -362,11 +418,19 @@ __global__ void __launch_bounds__(COR_RT) k_corr_final(CorFinalArgs a) {
         const int n = a.cnt[row + src];
         const double v = n != 0 ? a.sum[row + src] / (double)n : __builtin_nan("");
         if (a.ccf) a.ccf[row + j] = v;
-        s_buf[cor_brev((unsigned)j, a.log2n)] = make_double2(v, 0.0);
+        s_buf[cor_store_pos<GEN>(pl, j, a.log2n)] = make_double2(v, 0.0);
     }
     if (a.fc == nullptr) return;
-    cor_block_fft(s_buf, a.n_phi, a.log2n, a.tw, tid);
+    cor_ring_fft<GEN>(pl, s_buf, a.n_phi, a.log2n, a.tw, tid);
     for (int k = tid; k < a.fc_n; k += COR_RT) a.fc[(size_t)blockIdx.x * a.fc_n + k] = s_buf[k];
+}
+__global__ void __launch_bounds__(COR_RT) k_corr_final(CorFinalArgs a) {
+    __shared__ double2 s_buf[COR_MAX_NPHI];
+    cor_final_body<false>(a, nullptr, s_buf);
+}
+__global__ void __launch_bounds__(COR_RT) k_corr_final_g(CorFinalArgs a, CorPlanArgs pl) {
+    __shared__ double2 s_buf[COR_G_MAX_NPHI];
+    cor_final_body<true>(a, &pl, s_buf);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
@@ -381,8 +445,8 @@ static inline hipError_t cor_host_copy(mtip_ctx* c, void* dst, const void* src, 
     return hipSuccess;
 }
 
-extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correlate_cfg* cfg, const int32_t* q1_pos, const int32_t* q2_pos,
-                                                 const double* factor) {
+extern "C" mtip_correlate* mtip_correlate_create_ex(mtip_ctx* c, const mtip_correlate_cfg* cfg, const int32_t* q1_pos,
+                                                    const int32_t* q2_pos, const double* factor, uint32_t flags) {
     if (!c) return nullptr;
     char msg[400];
     if (!cfg || !q1_pos || !q2_pos || cfg->n_q < 1 || cfg->n_q1 < 1 || cfg->n_q2 < 1 || cfg->n_q > 65535 || cfg->n_q1 > 65535 ||
@@ -390,9 +454,28 @@ extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correla
         c->err = "correlate_create: null argument or a ring count outside 1 .. 65535";
         return nullptr;
     }
+    if (flags & ~(uint32_t)MTIP_CORRELATE_GENERAL_NPHI) {
+        snprintf(msg, sizeof msg, "correlate_create_ex: flags = 0x%x: only MTIP_CORRELATE_GENERAL_NPHI (bit 0) is defined", (unsigned)flags);
+        c->err = msg;
+        return nullptr;
+    }
     const int n = cfg->n_phi;
-    if (n < COR_MIN_NPHI || n > COR_MAX_NPHI || (n & (n - 1))) {
+    const bool radix2 = n >= COR_MIN_NPHI && n <= COR_MAX_NPHI && !(n & (n - 1));
+    if (!(flags & MTIP_CORRELATE_GENERAL_NPHI) && !radix2) {
         snprintf(msg, sizeof msg, "correlate_create: n_phi = %d is not built; supported: 16, 32, 64, 128, 256, 512, 1024", n);
+        c->err = msg;
+        return nullptr;
+    }
+    if (!radix2 && !cor_general_ok(n)) {
+        int below, above;
+        char lo[16] = "none", hi[16] = "none";
+        cor_general_near(n, &below, &above);
+        if (below) snprintf(lo, sizeof lo, "%d", below);
+        if (above) snprintf(hi, sizeof hi, "%d", above);
+        snprintf(msg, sizeof msg,
+                 "correlate_create: n_phi = %d is not built; with MTIP_CORRELATE_GENERAL_NPHI: even lengths %d .. %d whose only prime "
+                 "factors are 2, 3 and 5; the nearest below: %s, above: %s",
+                 n, COR_MIN_NPHI, COR_G_MAX_NPHI, lo, hi);
         c->err = msg;
         return nullptr;
     }
@@ -418,7 +501,9 @@ extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correla
     h->cfg.shared_mask = shared ? 1 : 0;
     const size_t rows = (size_t)COR_CHUNK * cfg->n_q, n_spec = rows * (h->m + 1), spec = n_spec * sizeof(double2);
     const size_t acc = h->n_acc * 12, tab = shared ? h->n_acc * 8 : 0;
-    const size_t work = spec * (shared ? 1 : 2) + spec / COR_CHUNK + rows * n + rows * 16 + (factor ? (size_t)cfg->n_q * n * 8 : 0);
+    // (a mixed-radix handle's plan: twiddles of n_phi entries, digit reversals of n_phi and of n_phi / 2 points)
+    const size_t plan = radix2 ? 0 : (size_t)n * sizeof(double2) + ((size_t)n + h->m) * sizeof(uint16_t);
+    const size_t work = spec * (shared ? 1 : 2) + spec / COR_CHUNK + rows * n + rows * 16 + (factor ? (size_t)cfg->n_q * n * 8 : 0) + plan;
     const size_t fr = mtip_free_memory();
     if (acc + tab + work > fr) {
         snprintf(msg, sizeof msg,
@@ -430,12 +515,27 @@ extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correla
         delete h;
         return nullptr;
     }
-    std::vector<double2> tw((size_t)h->m);
-    for (int k = 0; k < h->m; ++k) {
+    h->general = !radix2;
+    std::vector<double2> tw((size_t)(h->general ? n : h->m));
+    for (int k = 0; k < (int)tw.size(); ++k) {
         const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
         tw[k] = make_double2((double)cosl(ang), (double)sinl(ang));
     }
+    std::vector<uint16_t> perm;
+    if (h->general) {                                                   // the plan: stages and digit reversals of n and of n / 2 points
+        h->pl_n.st = cor_make_stages(n, n);
+        h->pl_m.st = cor_make_stages(h->m, n);
+        perm.resize((size_t)n + h->m);
+        cor_make_perm(h->pl_n.st, n, perm.data());
+        cor_make_perm(h->pl_m.st, h->m, perm.data() + n);
+    }
     hipError_t e = h->d_sum.alloc(h->n_acc);
+    if (e == hipSuccess && h->general) e = h->d_perm.alloc(perm.size());
+    if (e == hipSuccess && h->general) e = mtip_copy(c, h->d_perm, perm.data(), perm.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && h->general) {
+        h->pl_n.perm = h->d_perm;
+        h->pl_m.perm = h->d_perm + n;
+    }
     if (e == hipSuccess) e = h->d_cnt.alloc(h->n_acc);
     if (e == hipSuccess && shared) e = h->d_M.alloc(h->n_acc);
     if (e == hipSuccess) e = h->d_q1.alloc((size_t)cfg->n_q1);
@@ -462,6 +562,11 @@ extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correla
     return h;
 }
 
+extern "C" mtip_correlate* mtip_correlate_create(mtip_ctx* c, const mtip_correlate_cfg* cfg, const int32_t* q1_pos, const int32_t* q2_pos,
+                                                 const double* factor) {
+    return mtip_correlate_create_ex(c, cfg, q1_pos, q2_pos, factor, 0);
+}
+
 extern "C" void mtip_correlate_destroy(mtip_correlate* h) {
     if (!h) return;
     (void)hipSetDevice(h->c->device);
@@ -469,10 +574,27 @@ extern "C" void mtip_correlate_destroy(mtip_correlate* h) {
     delete h;
 }
 
+static inline void cor_launch_ring(mtip_correlate* h, unsigned n_patterns, const CorRingArgs& r) {
+    const dim3 g((unsigned)h->cfg.n_q, n_patterns), b(COR_RT);
+    if (h->general) hipLaunchKernelGGL(k_corr_ring_g, g, b, 0, h->c->stream, r, h->pl_n);
+    else hipLaunchKernelGGL(k_corr_ring, g, b, 0, h->c->stream, r);
+}
+
 static inline void cor_launch_pair(mtip_correlate* h, const CorPairArgs& a) {
     mtip_ctx* c = h->c;
     const unsigned grid = (unsigned)std::min<long long>(div_up(a.npairs, COR_WAVES), (long long)c->n_cu * 8);
     const dim3 g(grid), b(COR_WAVES * 64);
+    if (h->general) {
+        const int rows = div_up(a.m, 64);
+        const size_t lds = cor_pair_lds(a.m);
+        if (rows <= 1) hipLaunchKernelGGL(k_corr_pair_g<1>, g, b, lds, c->stream, a, h->pl_m);
+        else if (rows <= 2) hipLaunchKernelGGL(k_corr_pair_g<2>, g, b, lds, c->stream, a, h->pl_m);
+        else if (rows <= 4) hipLaunchKernelGGL(k_corr_pair_g<4>, g, b, lds, c->stream, a, h->pl_m);
+        else if (rows <= 8) hipLaunchKernelGGL(k_corr_pair_g<8>, g, b, lds, c->stream, a, h->pl_m);
+        else if (rows <= 12) hipLaunchKernelGGL(k_corr_pair_g<12>, g, b, lds, c->stream, a, h->pl_m);
+        else hipLaunchKernelGGL(k_corr_pair_g<16>, g, b, lds, c->stream, a, h->pl_m);
+        return;
+    }
     const int npl = std::max(1, a.m / 64);
     if (npl == 1) hipLaunchKernelGGL(k_corr_pair<1>, g, b, 0, c->stream, a);
     else if (npl == 2) hipLaunchKernelGGL(k_corr_pair<2>, g, b, 0, c->stream, a);
@@ -541,7 +663,7 @@ extern "C" int mtip_correlate_add(mtip_correlate* h, int n_patterns, const doubl
         rm.mask_stride = 0;
         rm.filter = 0;
         rm.do_G = 1;
-        hipLaunchKernelGGL(k_corr_ring, dim3((unsigned)f.n_q, 1), dim3(COR_RT), 0, c->stream, rm);
+        cor_launch_ring(h, 1, rm);
         CorPairArgs am = a;
         am.mode = COR_MODE_MASK_ONLY;
         am.P = 1;
@@ -559,7 +681,7 @@ extern "C" int mtip_correlate_add(mtip_correlate* h, int n_patterns, const doubl
         {
             ProfScope ps(c, "corr_ring");
             hipLaunchKernelGGL(k_corr_stats, dim3((unsigned)f.n_q, (unsigned)pc), dim3(COR_RT), 0, c->stream, r);
-            hipLaunchKernelGGL(k_corr_ring, dim3((unsigned)f.n_q, (unsigned)pc), dim3(COR_RT), 0, c->stream, r);
+            cor_launch_ring(h, (unsigned)pc, r);
         }
         a.good = d_good + p0;
         a.P = pc;
@@ -670,7 +792,8 @@ extern "C" int mtip_correlate_finalize(mtip_correlate* h, int symmetrize, int po
         a.pos_3pi2 = pos_3pi2;
         a.fc_n = fc ? fc_n_max : 0;
         ProfScope ps(c, "corr_final");
-        hipLaunchKernelGGL(k_corr_final, dim3((unsigned)pairs), dim3(COR_RT), 0, c->stream, a);
+        if (h->general) hipLaunchKernelGGL(k_corr_final_g, dim3((unsigned)pairs), dim3(COR_RT), 0, c->stream, a, h->pl_n);
+        else hipLaunchKernelGGL(k_corr_final, dim3((unsigned)pairs), dim3(COR_RT), 0, c->stream, a);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

@@ -26,7 +26,8 @@ class MtipCfg(C.Structure):
                 ('n_batch', C.c_int32), ('hankel_trapz', C.c_int32), ('fused', C.c_int32), ('reserved', C.c_int32)]
 
 
-MTIP_CFG_LOOP_BIG_L = 1           # MtipCfg.reserved bit 0 (include/mtip_hip.h): the phasing loop and the projection beyond L = 63
+MTIP_CORRELATE_GENERAL_NPHI = 1   # mtip_correlate_create_ex flags bit 0: every even 5-smooth n_phi in 16 .. 2048
+MTIP_CFG_LOOP_BIG_L = 1          # MtipCfg.reserved bit 0 (include/mtip_hip.h): the phasing loop and the projection beyond L = 63
 
 
 class MtipCorrelateCfg(C.Structure):
@@ -166,6 +167,7 @@ _SIGNATURES = {
     'mtip_op_cc_lstsq_deg2': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_deg2_to_cc': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void]),
     'mtip_correlate_create': (c_void, [c_void, C.POINTER(MtipCorrelateCfg), c_void, c_void, c_void]),
+    'mtip_correlate_create_ex': (c_void, [c_void, C.POINTER(MtipCorrelateCfg), c_void, c_void, c_void, C.c_uint32]),
     'mtip_correlate_destroy': (None, [c_void]),
     'mtip_correlate_add': (C.c_int, [c_void, C.c_int, c_void, c_void]),
     'mtip_correlate_num_patterns': (C.c_int, [c_void]),

@@ -27,9 +27,30 @@ from . import _lib
 from .settings import resolve_correlate
 
 SUPPORTED_N_PHI = (16, 32, 64, 128, 256, 512, 1024)
+GENERAL_N_PHI_MIN, GENERAL_N_PHI_MAX = 16, 2048     # general_n_phi=True: even lengths in this range with prime factors 2, 3, 5 only
 SUPPORTED_ORDERS = (0, 1, 2, 3, 4, 5)
 FRAME_DIM_MIN, FRAME_DIM_MAX = 2, 4096
 BAD_MASK = 'correlate: mask values other than 0 / 1'
+
+
+def general_n_phi_ok(n):
+    """n_phi a ``Correlator`` made with general_n_phi=True takes"""
+    n = int(n)
+    if n < GENERAL_N_PHI_MIN or n > GENERAL_N_PHI_MAX or n % 2:
+        return False
+    for p in (2, 3, 5):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
+def general_n_phi_near(n):
+    """(below, above): the nearest lengths general_n_phi=True takes on either side of n (None: there is none), e.g. to pick the
+    n_phi of phi_range where its 'max' / 'min' mode would give the ring's pixel count"""
+    n = int(n)
+    below = next((k for k in range(min(n - 1, GENERAL_N_PHI_MAX), GENERAL_N_PHI_MIN - 1, -1) if general_n_phi_ok(k)), None)
+    above = next((k for k in range(max(n + 1, GENERAL_N_PHI_MIN), GENERAL_N_PHI_MAX + 1) if general_n_phi_ok(k)), None)
+    return below, above
 
 
 def analyse_dependencies(compute):
@@ -265,9 +286,13 @@ class Correlator:
     ``merge(partials)`` make the accumulation additive over ranks or GPUs that each take a share of the patterns.
 
     shared_mask=True: one mask for every pattern; its pair counts are computed once per handle.  An active radial pixel filter makes
-    masks per pattern, so the flag is ignored then."""
+    masks per pattern, so the flag is ignored then.
 
-    def __init__(self, engine, settings=None, shared_mask=False, binary_mask=None, background=None):
+    general_n_phi=True (None: settings['GPU']['general_n_phi'], default False): n_phi may be any even length in 16 .. 2048 whose only
+    prime factors are 2, 3 and 5 -- the default settings' 1536 among them -- through ``mtip_correlate_create_ex``; without it the
+    lengths are SUPPORTED_N_PHI.  ``general_n_phi_near`` names the nearest such lengths."""
+
+    def __init__(self, engine, settings=None, shared_mask=False, binary_mask=None, background=None, general_n_phi=None):
         self.engine = engine
         self._frame_arrays = (binary_mask, background)
         self.resampler = None
@@ -276,7 +301,16 @@ class Correlator:
         self.compute = analyse_dependencies(opt['compute'])
         self.geometry = g = polar_geometry(opt)
         self.n_q, self.n_phi = g['n_q'], g['n_phi']
-        if self.n_phi not in SUPPORTED_N_PHI:
+        if general_n_phi is None:
+            general_n_phi = (opt.get('GPU') or {}).get('general_n_phi', False)
+        self.general_n_phi = bool(general_n_phi)
+        if self.general_n_phi:
+            if not general_n_phi_ok(self.n_phi):
+                below, above = general_n_phi_near(self.n_phi)
+                raise NotImplementedError(f'correlate: n_phi = {self.n_phi} is not built; general_n_phi takes even lengths '
+                                          f'{GENERAL_N_PHI_MIN} .. {GENERAL_N_PHI_MAX} whose only prime factors are 2, 3 and 5; the '
+                                          f'nearest below: {below}, above: {above}')
+        elif self.n_phi not in SUPPORTED_N_PHI:
             raise NotImplementedError(f'correlate: n_phi = {self.n_phi} is not built; supported lengths: {SUPPORTED_N_PHI}')
         filt = opt['intensity_radial_pixel_filter']
         self.filter = bool(filt[0])
@@ -307,7 +341,11 @@ class Correlator:
         cfg = _lib.MtipCorrelateCfg(self.n_q, self.n_phi, self.n_q1, self.n_q2, 1 if self.filter else 0, roi_lo, roi_hi,
                                     1 if roi_f[0] else 0, 1 if roi_n[0] else 0, 1 if self.shared_mask else 0,
                                     float(filt[1][1]) if self.filter else 0.0, float(roi_f[1]), float(roi_f[2]))
-        self.handle = self.lib.mtip_correlate_create(engine.ctx, C.byref(cfg), _lib.ptr(self.q1), _lib.ptr(self.q2), _lib.ptr(self.factor))
+        tables = (engine.ctx, C.byref(cfg), _lib.ptr(self.q1), _lib.ptr(self.q2), _lib.ptr(self.factor))
+        if self.general_n_phi:
+            self.handle = self.lib.mtip_correlate_create_ex(*tables, _lib.MTIP_CORRELATE_GENERAL_NPHI)
+        else:
+            self.handle = self.lib.mtip_correlate_create(*tables)
         if not self.handle:
             msg = self.lib.mtip_last_error(engine.ctx).decode()
             if 'GB' in msg:

@@ -119,8 +119,10 @@ def correlate_default_settings():
     (``xframe/projects/fxs/settings/correlate/default_0.01.yaml``).  The Cartesian stage is part of it: intensity_pixel_threshold
     [on, lo, hi] masks pixels of the raw frame outside lo .. hi, use_binary_mask / subtract_background switch on the arrays handed to
     ``Resampler``, interpolation_order (0 .. 5) is the spline order of the polar resampling.  File lists and process splitting stay
-    with the caller (``read_raw_images`` reads the frames)."""
+    with the caller (``read_raw_images`` reads the frames).  GPU.general_n_phi (this project's key): ``Correlator`` takes every even
+    n_phi in 16 .. 2048 with prime factors 2, 3, 5 -- the default's 1536 among them -- instead of the powers of two up to 1024."""
     return {
+        'GPU': {'general_n_phi': False},
         'intensity_pixel_threshold': [False, 4.0, 1e4],
         'use_binary_mask': False,
         'subtract_background': False,
