@@ -37,137 +37,157 @@ void launch_coeff_diff(mtip_ctx* c, const double2* a, const double2* b, double2*
 // flattened into columns (B (4l+2) of them).  v_mfma_f64_16x16x4_f64: lane j holds A[i = j&15][kk = j>>4] = W_l[p0+kk][k0+i],
 // B[kk = j>>4][col = j&15] = X[p0+kk][col0+col], D reg r = D[(j>>4) + 4r][j&15].  The (-/+ i)^l * scale prefactor is applied in
 // the epilogue: multiplying by +-i swaps the re/im columns, i.e. neighbouring lanes (shfl_xor 1).
-// ---- workgroup-tiled variant ---------------------------------------------------------------------------------
-// (rounds 1-2 had one 16-column tile per WAVE, fragments straight from L2: the panel was re-read once per row group and W_l once per column tile, PMC 3.3 x the algorithmic
-// bytes), and what bounds these kernels is the rate at which a CU can pull bytes when every CU pulls (~11 B/clk,
-// L2 hits included).  Here a 512-thread workgroup owns 80 columns x all (<= 128) output shells of one order -- 231
-// workgroups at 8 restarts, L = 32: about one per CU, all resident, W_l read once per 80 columns and the panel once.  Per
-// chunk of 16 input shells W_l[16][Nq] and the panel [16][80] are staged in LDS with coalesced loads (operands of the
-// next two chunks in flight in registers); wave w multiplies row tile w with the five column tiles (one A and five B
-// fragments from LDS per k-step).  LDS row strides = 16 doubles mod 32, so the two input shells a half-wave reads
-// land on disjoint banks.
+// ---- one-pass workgroup tile -----------------------------------------------------------------------------------
+// A 512-thread workgroup owns 16 CT columns x 128 output shells of one order; wave w owns row tile w.  Per stage of
+// ST input shells (32; 64 at CT = 1) a wave requests its own 16 columns of W_l, ST / 4 doubles per lane, from the
+// fragment-ordered copy d_Wf (below) in 16-byte loads and keeps them in registers: W never enters LDS.  The
+// workgroup requests the stage's panel ST x 16 CT as 16-byte (re, im) pairs (SUB: the subtracted panel too; the
+// difference is taken at the deposit), deposits it once into one of two LDS buffers and meets at ONE barrier; behind
+// it the stage's k-steps run A from registers and B fragments from LDS, with no global access, no wait for one and no
+// barrier, while the next stage's operands are in flight in a second register set.  Every accumulator sees the k-steps
+// in ascending p, four shells each, and in SUB wave 0's masked row-0 MFMA directly behind the main one of its k-step:
+// the MFMA sequence of the chunked kernel this replaced, the same bits.  The LDS row stride is 16 doubles mod 32, so
+// the two input shells a half-wave reads land on disjoint banks.  (One stage of 128 shells with everything requested at
+// entry, and operands two stages ahead, were measured and are slower at CT >= 2: profiles/hankel_onepass_timing.txt.)
 #define HT_CT_MAX 5                 // 16-column MFMA tiles per workgroup: template parameter CT in {1, 2, 3, 5}
-#define HT_KC 16                    // input shells per chunk (4 MFMA k-steps)
 #define HT_ROWS 128                 // output shells per workgroup (8 row tiles = 8 waves)
-#define HT_WS (HT_ROWS + 16)        // LDS row strides (doubles)
 #define HT_THREADS 512
-#define HT_NW (HT_KC * HT_ROWS / HT_THREADS)                       // W doubles per thread and chunk (4)
+#define HT_PPAD 64                  // d_Wf pads the input shells of an order to a multiple of this: a whole number of stages
 
 struct HankelTile32 { int l, cflat0; };
+
+// d_Wf: W in MFMA-fragment order.  Block (l, row block rb, wave w, k-step pair j) is 64 lanes x 2 doubles: lane (i = lane & 15,
+// kk = lane >> 4) finds W_l[8j + kk][k] and W_l[8j + 4 + kk][k], k = 128 rb + 16 w + i, next to each other -- its A values
+// of k-steps 2j and 2j + 1; a wave load is 1 KiB contiguous.  Entries with p >= Np or k >= N are zero, so the kernel needs no
+// predicate on this side; j runs to hankel_wf_pairs(Np), a whole number of stages.
+static inline int hankel_wf_pairs(int Np) { return div_up(Np, HT_PPAD) * (HT_PPAD / 8); }
+
+size_t hankel_wf_doubles(const mtip_ctx* c) {
+    return (size_t)(c->L + 1) * div_up(c->N, HT_ROWS) * (HT_ROWS / 16) * hankel_wf_pairs(c->Np) * 128;
+}
+
+int upload_hankel_fragments(mtip_ctx* c, const double* w_raw) {
+    const int N = c->N, Np = c->Np, nrb = div_up(N, HT_ROWS), nj = hankel_wf_pairs(Np);
+    std::vector<double> wf(hankel_wf_doubles(c), 0.0);
+    size_t o = 0;
+    for (int l = 0; l <= c->L; ++l)
+        for (int rb = 0; rb < nrb; ++rb)
+            for (int w = 0; w < HT_ROWS / 16; ++w)
+                for (int j = 0; j < nj; ++j)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int h = 0; h < 2; ++h, ++o) {
+                            const int p = 8 * j + 4 * h + (lane >> 4), k = HT_ROWS * rb + 16 * w + (lane & 15);
+                            if (p < Np && k < N) wf[o] = w_raw[((size_t)l * Np + p) * N + k];
+                        }
+    return mtip_copy(c, c->d_Wf, wf.data(), wf.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess ? MTIP_OK : MTIP_EHIP;
+}
 
 // SUB: out = H(in - in_sub) on output shells > 0 and H(in) on shell 0 in ONE pass (the ft_stab step needs
 // IFT(F') - IFT(F) above shell 0 and IFT(F') on it, misk.py:326-329): the staged panel is the difference, and the wave
 // that owns output row 0 adds H(in_sub)[0] back with a second MFMA chain whose A fragment is W_l masked to row 0.
 template <int HT_CT, bool SUB>
 __global__ void __launch_bounds__(HT_THREADS) k_hankel_tile(const double* __restrict__ in, double* __restrict__ out,
-                                                            const double* __restrict__ W,
+                                                            const double* __restrict__ Wf,
                                                             const HankelTile32* __restrict__ tiles, int N, int Np, int L,
                                                             int B, int poffs, double scale, int sign,
                                                             const double* __restrict__ in_sub, const uint8_t* __restrict__ sub_mask) {
+    // input shells per stage: 32, and 64 at CT = 1, where 32 rows of 8 pairs would leave half the waves without a deposit
+    // (and so without the wait for their own W fragments in front of the barrier)
+    constexpr int HT_ST = HT_CT == 1 ? 64 : 32;
     constexpr int HT_COLS = 16 * HT_CT;
-    constexpr int HT_XS = HT_COLS + 16;
-    constexpr int HT_NX = (HT_KC * HT_COLS + HT_THREADS - 1) / HT_THREADS;    // panel doubles per thread and chunk
-    __shared__ double Ws[2][HT_KC][HT_WS];
-    __shared__ double Xs[2][HT_KC][HT_XS];
-    __shared__ double Ss[SUB ? 2 : 1][SUB ? HT_KC : 1][HT_XS];   // the subtracted panel itself (row-0 correction)
+    constexpr int HT_XS = (HT_CT & 1) ? HT_COLS : HT_COLS + 16; // 16, 48, 48, 80: 16 mod 32
+    constexpr int HT_PW = HT_COLS / 2;                          // (re, im) pairs per panel row
+    constexpr int HT_RP = HT_THREADS / HT_PW;                   // panel rows per pass of the workgroup
+    constexpr int HT_NX = (HT_ST + HT_RP - 1) / HT_RP;          // passes = pairs per thread and stage
+    constexpr int HT_NA = HT_ST / 8;                            // A pairs per lane and stage
+    static_assert(HT_PPAD % HT_ST == 0 && HT_ST % 8 == 0 && HT_XS % 32 == 16, "stage and stride rules");
+    __shared__ double Xs[2][HT_ST][HT_XS] __attribute__((aligned(16)));
+    __shared__ double Ss[SUB ? 2 : 1][SUB ? HT_ST : 1][HT_XS] __attribute__((aligned(16)));   // the subtracted panel itself (row-0 correction)
     const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const HankelTile32 tinfo = tiles[blockIdx.x];
     const int l = tinfo.l;
     const int k_base = blockIdx.y * HT_ROWS;                      // row block (Nq > 128)
     const int ncl = 4 * l + 2;                                    // doubles per (batch, shell) of this order
     const int nlm2 = 2 * (L + 1) * (L + 1);                       // doubles per (batch, shell)
-    const double* Wl = W + (size_t)l * Np * N;
-    // ---- staging roles: W chunk = 16 x 128 doubles (row tid / 32, 4 consecutive columns),
-    //      panel chunk = 16 x 80 doubles, element e = tid + j * 512 -> (row e / 80, column e % 80)
-    const int wrow = tid >> 5, wcol = (tid & 31) * 4;
-    int xrow[HT_NX], xc[HT_NX];
-    size_t xoff[HT_NX];
-    bool xok[HT_NX], xsub[HT_NX];        // xsub: this column's restart takes the subtraction (per-restart ft_stab; all without a mask)
-#pragma unroll
-    for (int j = 0; j < HT_NX; ++j) {
-        const int e = tid + j * HT_THREADS;
-        xrow[j] = e / HT_COLS;
-        xc[j] = e - xrow[j] * HT_COLS;
-        const int cflat = tinfo.cflat0 + xc[j];
-        xok[j] = xrow[j] < HT_KC && cflat < B * ncl;
-        const int b = xok[j] ? cflat / ncl : 0;
-        const int within = xok[j] ? cflat - b * ncl : 0;
-        xoff[j] = (size_t)b * N * nlm2 + 2 * (size_t)l * l + within;
-        xsub[j] = SUB && (sub_mask == nullptr || sub_mask[b] != 0);
-    }
-    // two register sets: the operands of the next TWO chunks are in flight while one is multiplied
-    double rw0[HT_NW], rx0[HT_NX], rw1[HT_NW], rx1[HT_NX];
-    double rs0[SUB ? HT_NX : 1], rs1[SUB ? HT_NX : 1];
-    auto request = [&](int p0, double (&rw)[HT_NW], double (&rx)[HT_NX], double (&rs)[SUB ? HT_NX : 1]) {
-        const int p = p0 + wrow;
-        const bool p_ok = p < Np;
-        const double* wr = Wl + (size_t)(p_ok ? p : 0) * N + k_base + wcol;
-#pragma unroll
-        for (int j = 0; j < HT_NW; ++j) rw[j] = (p_ok && k_base + wcol + j < N) ? wr[j] : 0.0;
-#pragma unroll
-        for (int j = 0; j < HT_NX; ++j) {
-            const bool ok = xok[j] && p0 + xrow[j] < Np;
-            const size_t o = xoff[j] + (size_t)(p0 + xrow[j] + poffs) * nlm2;
-            rx[j] = ok ? in[o] : 0.0;
-            if (SUB) {
-                rs[j] = (ok && xsub[j]) ? in_sub[o] : 0.0;
-                rx[j] -= rs[j];
-            }
-        }
-    };
-    auto deposit = [&](int buf, const double (&rw)[HT_NW], const double (&rx)[HT_NX], const double (&rs)[SUB ? HT_NX : 1]) {
-#pragma unroll
-        for (int j = 0; j < HT_NW; ++j) Ws[buf][wrow][wcol + j] = rw[j];
-#pragma unroll
-        for (int j = 0; j < HT_NX; ++j)
-            if (xrow[j] < HT_KC) {
-                Xs[buf][xrow[j]][xc[j]] = rx[j];
-                if (SUB) Ss[buf][xrow[j]][xc[j]] = rs[j];
-            }
-    };
+    const double2* Wa = reinterpret_cast<const double2*>(Wf) +
+                        (((size_t)l * gridDim.y + blockIdx.y) * (HT_ROWS / 16) + wave) * ((Np + HT_PPAD - 1) / HT_PPAD * (HT_PPAD / 8)) * 64 + lane;
+    // ---- staging role: pair tid % HT_PW of the panel rows tid / HT_PW + j HT_RP.  2 l^2, the column within the order and
+    //      cflat0 are even, so a pair is 16-byte aligned and never straddles two restarts
+    const int prow = tid / HT_PW, pc = tid - prow * HT_PW;
+    const int cflat_x = tinfo.cflat0 + 2 * pc;
+    const bool xok = prow < HT_RP && cflat_x < B * ncl;
+    const int xb = xok ? cflat_x / ncl : 0;
+    const size_t xoff = (size_t)xb * N * nlm2 + 2 * (size_t)l * l + (xok ? cflat_x - xb * ncl : 0);
+    const bool xsub = SUB && (sub_mask == nullptr || sub_mask[xb] != 0);   // this column's restart takes the subtraction (per-restart ft_stab; all without a mask)
     // ---- MFMA roles: wave = row tile, all HT_CT column tiles
     const int li = lane & 15, kk = lane >> 4;
     v4f64 acc[HT_CT];
 #pragma unroll
     for (int t = 0; t < HT_CT; ++t) acc[t] = v4f64{0.0, 0.0, 0.0, 0.0};
-    auto multiply = [&](int buf) {
+    // two register sets: the operands of the NEXT stage are in flight while this one is multiplied; the difference is taken at
+    // the deposit, so that nothing waits for a load before the stage that needs it
+    double2 a0[HT_NA], a1[HT_NA], rx0[HT_NX], rx1[HT_NX], rs0[SUB ? HT_NX : 1], rs1[SUB ? HT_NX : 1];
+    auto request = [&](int p0, double2 (&a)[HT_NA], double2 (&rx)[HT_NX], double2 (&rs)[SUB ? HT_NX : 1]) {
+        const double2* wa = Wa + (size_t)(p0 / 8) * 64;
 #pragma unroll
-        for (int s = 0; s < HT_KC / 4; ++s) {
-            const double af = Ws[buf][4 * s + kk][wave * 16 + li];
+        for (int j = 0; j < HT_NA; ++j) a[j] = wa[(size_t)j * 64];
+#pragma unroll
+        for (int j = 0; j < HT_NX; ++j) {
+            const int row = prow + j * HT_RP;
+            const bool ok = xok && ((j + 1) * HT_RP <= HT_ST || row < HT_ST) && p0 + row < Np;
+            const size_t o = xoff + (size_t)(p0 + row + poffs) * nlm2;
+            rx[j] = ok ? *reinterpret_cast<const double2*>(in + o) : make_double2(0.0, 0.0);
+            if (SUB) rs[j] = (ok && xsub) ? *reinterpret_cast<const double2*>(in_sub + o) : make_double2(0.0, 0.0);
+        }
+    };
+    auto deposit = [&](int buf, const double2 (&rx)[HT_NX], const double2 (&rs)[SUB ? HT_NX : 1]) {
+#pragma unroll
+        for (int j = 0; j < HT_NX; ++j) {
+            const int row = prow + j * HT_RP;
+            if ((HT_RP * HT_PW == HT_THREADS || prow < HT_RP) && ((j + 1) * HT_RP <= HT_ST || row < HT_ST)) {
+                double2 d = rx[j];
+                if (SUB) {
+                    d.x -= rs[j].x;
+                    d.y -= rs[j].y;
+                    *reinterpret_cast<double2*>(&Ss[buf][row][2 * pc]) = rs[j];
+                }
+                *reinterpret_cast<double2*>(&Xs[buf][row][2 * pc]) = d;
+            }
+        }
+    };
+    auto multiply = [&](int buf, const double2 (&a)[HT_NA]) {
+#pragma unroll
+        for (int s = 0; s < HT_ST / 4; ++s) {                      // k-steps past the last shell multiply zeros
+            const double af = (s & 1) ? a[s >> 1].y : a[s >> 1].x;
 #pragma unroll
             for (int t = 0; t < HT_CT; ++t) {
                 const double bf = Xs[buf][4 * s + kk][16 * t + li];
                 acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[t], 0, 0, 0);
             }
             if (SUB && wave == 0 && k_base == 0) {               // wave-uniform: output row 0 lives here
-                const double a0 = li == 0 ? af : 0.0;
+                const double a0m = li == 0 ? af : 0.0;
 #pragma unroll
                 for (int t = 0; t < HT_CT; ++t) {
                     const double sf = Ss[buf][4 * s + kk][16 * t + li];
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, sf, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0m, sf, acc[t], 0, 0, 0);
                 }
             }
         }
     };
-    const int n_chunks = (Np + HT_KC - 1) / HT_KC;
-    request(0, rw0, rx0, rs0);
-    deposit(0, rw0, rx0, rs0);
-    if (n_chunks > 1) request(HT_KC, rw1, rx1, rs1);
-    if (n_chunks > 2) request(2 * HT_KC, rw0, rx0, rs0);
-    __syncthreads();
-    for (int i = 0; i < n_chunks; i += 2) {
-        // chunk i from buffer 0; chunk i+1 (set 1) goes to buffer 1; then set 1 asks for chunk i+3
-        multiply(0);
-        if (i + 1 < n_chunks) deposit(1, rw1, rx1, rs1);
+    // a buffer is written again two stages after it was read: every wave has passed the barrier of the stage in between
+    request(0, a0, rx0, rs0);
+#pragma unroll 1
+    for (int p0 = 0; p0 < Np; p0 += 2 * HT_ST) {
+        deposit(0, rx0, rs0);
+        if (p0 + HT_ST < Np) request(p0 + HT_ST, a1, rx1, rs1);
         __syncthreads();
-        if (i + 3 < n_chunks) request((i + 3) * HT_KC, rw1, rx1, rs1);
-        if (i + 1 >= n_chunks) break;
-        // chunk i+1 from buffer 1; chunk i+2 (set 0) goes to buffer 0; then set 0 asks for chunk i+4
-        multiply(1);
-        if (i + 2 < n_chunks) deposit(0, rw0, rx0, rs0);
+        multiply(0, a0);
+        if (p0 + HT_ST >= Np) break;
+        deposit(1, rx1, rs1);
+        if (p0 + 2 * HT_ST < Np) request(p0 + 2 * HT_ST, a0, rx0, rs0);
         __syncthreads();
-        if (i + 4 < n_chunks) request((i + 4) * HT_KC, rw0, rx0, rs0);
+        multiply(1, a1);
     }
     // epilogue: * scale * (-/+ i)^l, store
     int r = l & 3;
@@ -204,7 +224,7 @@ void launch_hankel_mfma_sub(mtip_ctx* c, const double2* in, const double2* in_su
     const dim3 grid((unsigned)c->n_htiles32, (unsigned)hankel_row_blocks(c));
 #define HT_LAUNCH(CT, SUBF)                                                                                                  \
     hipLaunchKernelGGL((k_hankel_tile<CT, SUBF>), grid, dim3(HT_THREADS), 0, c->stream, reinterpret_cast<const double*>(in), \
-                       reinterpret_cast<double*>(out), (const double*)c->d_W, (const HankelTile32*)c->d_htiles32, c->N,      \
+                       reinterpret_cast<double*>(out), (const double*)c->d_Wf, (const HankelTile32*)c->d_htiles32, c->N,      \
                        c->Np, c->L, c->B, c->cfg.hankel_trapz ? 1 : 0, inverse ? c->inv_scale : c->fwd_scale,                \
                        inverse ? +1 : -1, reinterpret_cast<const double*>(in_sub), sub_mask)
     if (in_sub != nullptr) {

@@ -160,6 +160,7 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     A(dev_alloc(c, &c->d_r, N));
     A(dev_alloc(c, &c->d_q, N));
     A(dev_alloc(c, &c->d_W, (size_t)(L + 1) * c->Np * N));
+    A(dev_alloc(c, &c->d_Wf, hankel_wf_doubles(c)));
     // projection layout
     c->kl.assign(L + 1, 0);
     c->used.assign(L + 1, 0);
@@ -299,6 +300,7 @@ int mtip_set_hankel_weights(mtip_ctx* c, const double* w_raw, double fwd_scale, 
     if (!w_raw) FAIL(c, MTIP_EINVAL, "null weights");
     (void)hipSetDevice(c->device);
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_W, w_raw, (size_t)(c->L + 1) * c->Np * c->N * sizeof(double), hipMemcpyHostToDevice));
+    if (upload_hankel_fragments(c, w_raw) != MTIP_OK) FAIL(c, MTIP_EHIP, "upload of the fragment-ordered Hankel weights failed");
     c->fwd_scale = fwd_scale;
     c->inv_scale = inv_scale;
     c->have_weights = true;

@@ -322,6 +322,7 @@ struct mtip_ctx {
     DevBuf<double2> d_twN;                         // exp(-2 pi i j / n_phi), j < n_phi
     DevBuf<double2> d_tw;
     DevBuf<double> d_W;
+    DevBuf<double> d_Wf;                              // d_W again in MFMA-fragment order, zero padded (k_hankel.hip): what k_hankel_tile reads
     int n_cu = 256;                                   // compute units of the device (persistent-grid sizing)
     JacobiSchedule js;                                // resident-column pairing schedule
     // non-default reciprocal metrics (k_metrics.hip): flags 1 II_error | 2 ccd_diff | 4 fqc_error, their constant tables, history rows
@@ -440,6 +441,8 @@ void launch_hankel_mfma_sub(mtip_ctx* c, const double2* in, const double2* in_su
 int build_jacobi_schedule(mtip_ctx* c, int kmax);    // k_proj.hip: resident-column pairing schedule, verified on the host
 int jacobi_groups(int k);                            // pair-groups a round of that schedule keeps busy for k columns (<= js.ps: the table's row length)
 int build_hankel_tiles(mtip_ctx* c);
+size_t hankel_wf_doubles(const mtip_ctx* c);          // length of d_Wf
+int upload_hankel_fragments(mtip_ctx* c, const double* w_raw);   // d_Wf from the host table of mtip_set_hankel_weights
 int hankel_row_blocks(const mtip_ctx* c);            // row blocks (128 output shells each) of k_hankel_tile: the grid's y extent
 int launch_invariant_metrics(mtip_ctx* c, const double2* Ilm, long long step);
 int launch_reciprocal_l2_metric(mtip_ctx* c, const double2* F, const double2* Fp, long long step);
