@@ -87,6 +87,19 @@ void build_legendre_tables(mtip_ctx* c, const double* cos_theta) {
                 c->chain_chunks = t;
                 (void)mtip_copy(c, c->d_PTc, PTc.data(), PTc.size() * sizeof(double), hipMemcpyHostToDevice);
                 (void)mtip_copy(c, c->d_lmc, lmc.data(), lmc.size() * sizeof(int), hipMemcpyHostToDevice);
+                // and, for the L = 32 plan, by (wave, theta-pair couple, order, lane) with two neighbouring theta pairs to an entry:
+                // a thread of k_sht_chain fetches its 48 values with 24 loads of 16 bytes, a wave 1 KB in a row with each
+                if (c->d_PTw != nullptr && nth == 32) {
+                    std::vector<double2> PTw((size_t)8 * 8 * 3 * 64);
+                    for (int w = 0; w < 8; ++w)
+                        for (int cp = 0; cp < 8; ++cp)
+                            for (int u = 0; u < 3; ++u)
+                                for (int ln = 0; ln < 64; ++ln) {
+                                    const size_t th = (size_t)(w / 4) * 16 + 2 * cp, slot = (size_t)u * 256 + (w % 4) * 64 + ln;
+                                    PTw[(((size_t)w * 8 + cp) * 3 + u) * 64 + ln] = make_double2(PTc[th * 768 + slot], PTc[(th + 1) * 768 + slot]);
+                                }
+                    (void)mtip_copy(c, c->d_PTw, PTw.data(), PTw.size() * sizeof(double2), hipMemcpyHostToDevice);
+                }
             }
         }
     }

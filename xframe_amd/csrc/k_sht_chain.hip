@@ -33,6 +33,88 @@
         tprev = n_;                              \
     }
 
+// ---- Legendre sums of the L = 32 plan (n_theta = 64, two groups of 256 threads with 16 theta pairs each, three orders l of one
+// (m, parity) per thread: see the chunk layout in k_sht.hip).  The same 192 FMA in the same order as the general code in the
+// kernel, fed with less: the thread's 48 table values are 24 loads of 16 bytes from d_PTw (by wave, theta-pair couple, order,
+// lane: a wave reads 1 KB in a row with each) off three scalar bases and the lane's 32-bit offset; the panel reads of four theta
+// pairs are in flight while the four before them are consumed, and each such chunk waits once, by count, for its reads and its
+// six table loads (LDS and vector-memory operations of a wave complete in order).
+#ifdef __HIPCC__
+#define CHAIN_PIN_SGPR(x) asm volatile("" : "+s"(x))                        // a uniform value as a scalar register of its own
+// s_waitcnt vmcnt(VM) lgkmcnt(LGKM) as the instruction the compiler's own wait insertion sees (an asm statement it would not)
+#define CHAIN_WAITCNT(VM, LGKM) __builtin_amdgcn_s_waitcnt(((VM) & 0xf) | (0x7 << 4) | (((LGKM) & 0xf) << 8) | (((VM) >> 4) << 14))
+#define CHAIN_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)               // no instruction is scheduled across this point
+#else
+#define CHAIN_SCHED_FENCE()
+#define CHAIN_PIN_SGPR(x)
+#define CHAIN_WAITCNT(VM, LGKM)
+#endif
+
+__device__ __forceinline__ void chain_sums_l32(const double2* PTw, int wave, int lane, int lm0, const double2* Gs, double2 (&accp)[3],
+                                               double2 (&accm)[3]) {
+    constexpr int L = 32, nm = 2 * L + 1, THG = 16, NU = 3, NLD = NU * THG / 2;
+    // the wave's 24 KB: bases 8 KB apart, each in the middle of eight loads (offsets -4096 .. 3072 fit the instruction)
+    const char* tb[NLD / 8];
+#pragma unroll
+    for (int i = 0; i < NLD / 8; ++i) {
+        unsigned o = (unsigned)wave * (unsigned)(NLD * 64 * sizeof(double2)) + 4096u + 8192u * i;
+        CHAIN_PIN_SGPR(o);                                  // (left to itself the compiler adds the 8 KB steps per lane, in 64 bits)
+        tb[i] = reinterpret_cast<const char*>(PTw) + o;
+    }
+    const unsigned toff = (unsigned)lane * (unsigned)sizeof(double2);
+    double2 tab[NLD];                                       // entry 3 c + u: order u at theta pairs 2 c (.x) and 2 c + 1 (.y) of the group
+#pragma unroll
+    for (int k = 0; k < NLD; ++k) tab[k] = *reinterpret_cast<const double2*>(tb[k / 8] + ((k % 8) * 1024 - 4096) + toff);
+    const int lm = max(lm0, 0);                             // (the chunk's orders share m and the parity of l - m; -1: an idle thread)
+    const int l = lm & 0xff, m = lm >> 8;
+    // (the parity's row by a select, the group's by a scalar product: no vector multiply)
+    const double2* srcp = Gs + (wave >> 2) * (2 * THG * nm) + (((l + m) & 1) ? nm : 0) + L + m;
+    const double2* srcm = srcp - 2 * m;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        accp[u] = make_double2(0.0, 0.0);
+        accm[u] = make_double2(0.0, 0.0);
+    }
+    asm volatile("" ::: "memory");                          // every table load is requested in front of the first panel read
+    double2 vp[2][4], vm[2][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        vp[0][j] = srcp[2 * j * nm];
+        vm[0][j] = srcm[2 * j * nm];
+    }
+#pragma unroll
+    for (int c = 0; c < THG / 4; ++c) {
+        if (c + 1 < THG / 4) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                vp[(c + 1) & 1][j] = srcp[2 * (4 * (c + 1) + j) * nm];
+                vm[(c + 1) & 1][j] = srcm[2 * (4 * (c + 1) + j) * nm];
+            }
+        }
+        asm volatile("" ::: "memory");
+        // the 6 (c + 1) oldest table loads and the chunk's eight reads (eight younger ones may be in flight)
+        if (c == 0) CHAIN_WAITCNT(18, 8);
+        if (c == 1) CHAIN_WAITCNT(12, 8);
+        if (c == 2) CHAIN_WAITCNT(6, 8);
+        if (c == 3) CHAIN_WAITCNT(0, 0);
+        CHAIN_SCHED_FENCE();                               // (the products stay behind it: each would get a wait of its own in front of it)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int jj = 4 * c + j;
+            const double2 xp = vp[c & 1][j], xm = vm[c & 1][j];
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const double2 p2 = tab[(jj >> 1) * NU + u];
+                const double p = (jj & 1) ? p2.y : p2.x;
+                accp[u].x = fma(p, xp.x, accp[u].x);
+                accp[u].y = fma(p, xp.y, accp[u].y);
+                accm[u].x = fma(p, xm.x, accm[u].x);
+                accm[u].y = fma(p, xm.y, accm[u].y);
+            }
+        }
+    }
+}
+
 struct ChainArgs {
     // inverse half (as k_sht_inv_wide, one workgroup per shell)
     const double2* coeff;
@@ -52,6 +134,7 @@ struct ChainArgs {
     const int* lmtab;
     const double* PTc;                  // chunk layout of PT and lmtab (CHK instantiations)
     const int* lmc;
+    const double2* PTw;                 // PTc of the L = 32 plan by (wave, theta-pair couple, order, lane): 16-byte loads
     const double* gw;
     double norm;
     long long* dbg;                     // diagnostic: (shells, CHAIN_DBG_SLOTS) clock64 stamps of wave 0 at the phase boundaries, or null
@@ -77,7 +160,13 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
 #pragma unroll
         for (int i = 0; i < MTIP_CHAIN_DBG_SLOTS; ++i) stamp[i] = 0;
     }
-    const int L = LC > 0 ? LC : a.L, nt = a.nt, npairs = LC > 0 ? (LC + 1) * (LC + 2) / 2 : a.npairs, Nq = a.Nq, B = a.B;
+    // The L = 32 plan (SHT_CHAIN_L32) has ONE geometry -- n_theta = 64, 512 threads, two accumulation groups of 256 threads with 16
+    // theta pairs each (launch_chain_r checks it) -- so there all of it is a constant: the row guards of the passes fold (16 full
+    // groups of 4 rows, two per wave), the group of a thread is a shift, the closing reduction one add.
+    constexpr bool L32 = LC == 32;
+    static_assert(!L32 || (R1 == 8 && R2 == 16 && THG == 16 && MAXI == 3 && CHK), "the L = 32 plan");
+    constexpr int NT = L32 ? 64 : 0, GSZ = L32 ? 256 : 0;
+    const int L = LC > 0 ? LC : a.L, nt = L32 ? NT : a.nt, npairs = LC > 0 ? (LC + 1) * (LC + 2) / 2 : a.npairs, Nq = a.Nq, B = a.B;
     const int nm = 2 * L + 1;
     const int nlm = (L + 1) * (L + 1);
     double2* twN = sm;                              // N
@@ -89,7 +178,7 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     const long long shell = blockIdx.x;
     const int q = (int)(shell % Nq);
     const double2* csrc = a.coeff + (size_t)shell * nlm;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = blockDim.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = L32 ? SW_THREADS / 64 : (int)(blockDim.x >> 6);
     CHAIN_STAMP(0)
     // Everything the workgroup reads from global memory before its FFT passes is requested here, at once, and waited for once in
     // front of the staging barrier: the start values of the wave's Legendre items and cos(theta) of the lane (registers), then the
@@ -97,7 +186,6 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     // staging stores does not cover them -- the (l, m) of the closing sums and the epilogue operands of the wave's first group.
     // LQ items per wave are held; the L = 32 plan (n_theta = 64: one chunk of 32 theta pairs, 17 items on 8 waves) never refills.
     constexpr int LQ = 3;
-    constexpr bool L32 = LC == 32;
     static_assert(!L32 || ((LC + 2) / 2 + SW_THREADS / 64 - 1) / (SW_THREADS / 64) <= LQ, "start-value queue");
     // (the restart's byte of add_mask is a vector load the compiler wants in a scalar register at once: the oldest request, held
     // in its vector register until the staging has waited anyway, costs no wait of its own)
@@ -124,9 +212,9 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     // 2j+1 = odd part of theta pair j), and ONE Legendre-sum phase follows the last pass: accumulation group g owns theta pairs
     // [g thg, (g + 1) thg) of the shell, thread t of it the (l, m) pairs t + u gsz.  (Sums per pass were built first: table
     // rows and accumulators live across the 16-point FFTs spill.)
-    const int gsz = a.gsz;
+    const int gsz = L32 ? GSZ : a.gsz;
     const int thg = THG > 0 ? THG : a.thg;
-    const int grp = __builtin_amdgcn_readfirstlane(tid / gsz);      // wave-uniform (gsz >= 64): table rows through scalar bases
+    const int grp = L32 ? wave >> 2 : __builtin_amdgcn_readfirstlane(tid / gsz);      // wave-uniform (gsz >= 64): table rows through scalar bases
     const int tg = tid - grp * gsz;
     // ---- the FFT steps: WAVE-PRIVATE row groups.  A wave owns RW = 64 / R2 whole rows (theta pairs with their mirrors) through all
     // four FFT steps -- inverse R2-point FFTs over k2, transpose, inverse R1-point FFTs + epilogue + store, mirror fold, forward
@@ -158,7 +246,7 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     double pre_w = 0.0;                                     // theta weight of the error integral of this lane's row
     auto load_pre = [&](int g, auto first) {
         const int rr = first ? min(g * RW + r2l, nt - 1) : g * RW + r2l;
-        if (HAS_PRE && (first || (g < n_grp && rr < nt))) {
+        if (HAS_PRE && (first || (g < n_grp && (L32 || rr < nt)))) {
             const int th = rr >> 1;
             const int row = (rr & 1) ? (nt - 1 - th) : th;
 #pragma unroll
@@ -203,7 +291,7 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
         // ---- step 1: inverse R2-point FFTs over k2 of the zero padded spectrum, twiddle, transpose store
         {
             const int rr = g * RW + r1l;
-            if (role1 && rr < nt) {
+            if (L32 || (role1 && rr < nt)) {
                 const double2* gr = Gs + (size_t)rr * nm + L;
                 double2 uv[R2];
 #pragma unroll
@@ -241,7 +329,7 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
         CHAIN_SEG(4)
         // ---- step 2: inverse R1-point FFTs over k1, epilogue + coalesced store, the forward half's prologue
         const int rr2 = g * RW + r2l;
-        const bool act2 = rr2 < nt;
+        const bool act2 = L32 || rr2 < nt;
         double2 vv[R1];
 #pragma unroll
         for (int q1 = 0; q1 < R1; ++q1) vv[q1] = make_double2(0.0, 0.0);
@@ -261,7 +349,14 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
                     const double2 Fv = pre[n1];
                     const double I = cabs2(Fv);
                     const bool ok = (I >= 0.0) && (v.x >= 0.0);
-                    const double mult = ok ? sqrt(v.x / I) : 0.0;
+                    // (L = 32: the root of every lane, then the select -- `ok ? sqrt() : 0` is an EXEC region per point)
+                    double mult;
+                    if constexpr (L32) {
+                        const double root = sqrt(v.x / I);
+                        mult = ok ? root : 0.0;
+                    } else {
+                        mult = ok ? sqrt(v.x / I) : 0.0;
+                    }
                     v = cscale(Fv, mult);
                 } else if (EPI == EPI_REAL_UPDATE) {
                     const double2 pv = pre[n1];
@@ -300,7 +395,7 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
         //      were (consumed by step 1 of the same wave)
         {
             const int rr = g * RW + r1l;
-            if (role1 && rr < nt) {
+            if (L32 || (role1 && rr < nt)) {
                 double2 uv[R2];
                 const double2* ar = Bw + (size_t)(r1l * R1 + k1) * AS;
 #pragma unroll
@@ -313,8 +408,29 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
 #pragma unroll
                     for (int j = 0; j < R2 / 2; ++j) {
                         const int k = k1 + R1 * (2 * j + hf);
-                        if (k <= L) gr[k] = cscale(yv[j], sc);
-                        else if (k >= N - L) gr[k - N] = cscale(yv[j], sc);
+                        if constexpr (L32) {
+                            // no store under a lane's condition (each is two EXEC regions with their branches).  Output m2 = 2 j + hf
+                            // is k = k1 + R1 m2, k1 < R1: in the band for every lane (m2 <= 3: |m| <= L from below, m2 >= 12: from
+                            // above), for none (m2 = 5..11), or for some (m2 = 4: k1 = 0 alone).  The last kind goes through a
+                            // selected address: who is out of band writes to column R2 of its transpose-buffer row, padding that
+                            // nothing reads (the wave's reads of ar[] above are complete: LDS operations of a wave are in order).
+                            // (j is a constant once the loop is unrolled: these fold)
+                            const int ma = 2 * j, mb = 2 * j + 1;
+                            const bool lo_all = R1 * mb + R1 - 1 <= LC, lo_none = R1 * ma > LC;
+                            const bool hi_all = R1 * ma >= N - LC, hi_none = R1 * mb + R1 - 1 < N - LC;
+                            if (lo_all) {
+                                gr[k] = cscale(yv[j], sc);
+                            } else if (hi_all) {
+                                gr[k - N] = cscale(yv[j], sc);
+                            } else if (!(lo_none && hi_none)) {
+                                double2* dump = Bw + (size_t)(r1l * R1 + k1) * AS + R2;
+                                double2* dst = (k <= L) ? gr + k : (k >= N - L) ? gr + (k - N) : dump;
+                                *dst = cscale(yv[j], sc);
+                            }
+                        } else {
+                            if (k <= L) gr[k] = cscale(yv[j], sc);
+                            else if (k >= N - L) gr[k - N] = cscale(yv[j], sc);
+                        }
                     }
                 } else {
                     SmallFFT<R2, false>::run(uv);
@@ -347,7 +463,9 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     }
     // ---- Legendre sums over the whole panel: c_lm += P_lm(theta_j) E/O[j][m], table rows of the group requested together
     double2 accp[MAXI], accm[MAXI];
-    {
+    if constexpr (L32) {
+        chain_sums_l32(a.PTw, wave, lane, my_lm[0], Gs, accp, accm);
+    } else {
         // table rows of this thread's (l, m) pairs and theta pairs, requested together.  (Requested before the passes instead --
         // they fit beside them since the 16-point FFTs are split -- the sums get 4 k cycles shorter and step 1 of the passes 4 k
         // longer: measured, workgroup lifetime unchanged, profiles/r04_chain_phase_timers.txt.)
@@ -436,8 +554,9 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
     if (grp > 0) {
 #pragma unroll
         for (int u = 0; u < MAXI; ++u) {
-            racc[(size_t)(((grp - 1) * MAXI + u) * 2) * gsz + tg] = accp[u];
-            racc[(size_t)(((grp - 1) * MAXI + u) * 2 + 1) * gsz + tg] = accm[u];
+            const int gu = L32 ? u : (grp - 1) * MAXI + u;                  // (L = 32: group 1 is the only other one)
+            racc[(size_t)(gu * 2) * gsz + tg] = accp[u];
+            racc[(size_t)(gu * 2 + 1) * gsz + tg] = accm[u];
         }
     }
     __syncthreads();
@@ -457,11 +576,18 @@ __global__ void __launch_bounds__(SW_THREADS) k_sht_chain(ChainArgs a) {
 #pragma unroll
         for (int u = 0; u < MAXI; ++u) {
             double2 sp = accp[u], sq = accm[u];
-            for (int g = 1; g < ngrp; ++g) {
-                const double2 vp = racc[(size_t)(((g - 1) * MAXI + u) * 2) * gsz + tg];
-                const double2 vq = racc[(size_t)(((g - 1) * MAXI + u) * 2 + 1) * gsz + tg];
+            if constexpr (L32) {                                            // two groups: one add
+                const double2 vp = racc[(size_t)(u * 2) * GSZ + tg];
+                const double2 vq = racc[(size_t)(u * 2 + 1) * GSZ + tg];
                 sp.x += vp.x; sp.y += vp.y;
                 sq.x += vq.x; sq.y += vq.y;
+            } else {
+                for (int g = 1; g < ngrp; ++g) {
+                    const double2 vp = racc[(size_t)(((g - 1) * MAXI + u) * 2) * gsz + tg];
+                    const double2 vq = racc[(size_t)(((g - 1) * MAXI + u) * 2 + 1) * gsz + tg];
+                    sp.x += vp.x; sp.y += vp.y;
+                    sq.x += vq.x; sq.y += vq.y;
+                }
             }
             if (CHK ? my_lm[u] >= 0 : tg + u * gsz < npairs) {
                 const int l = my_lm[u] & 0xff, m = my_lm[u] >> 8;
@@ -486,11 +612,16 @@ static void launch_chain_r(mtip_ctx* c, const ChainArgs& a) {
     const ShtPlan& p = c->sht;
     const dim3 gr((unsigned)(c->B * c->N)), bl(SW_THREADS);
 #define CHAIN_GO(MAXI, THG, DBG, LC, CHK) hipLaunchKernelGGL((k_sht_chain<EPI, PRE, R1, R2, MAXI, THG, DBG, LC, CHK>), gr, bl, p.chain_lds, c->stream, a)
+    // the L = 32 instantiation has its geometry (n_theta 64, groups of 256 threads with 16 theta pairs, the table d_PTw) compiled in:
+    // a plan that says L32 with anything else gets the run-time geometry of REGTAB, never a kernel with the wrong constants
+    int chain = p.chain;
+    if (chain == SHT_CHAIN_L32 && !(c->nt == 64 && c->L == 32 && p.chain_gsz == 256 && p.chain_thg == 16 && p.chain_maxi == 3 && a.PTw != nullptr))
+        chain = SHT_CHAIN_REGTAB;
     if constexpr (R1 * R2 == 128) {
-        if (p.chain == SHT_CHAIN_L32 && a.dbg != nullptr) CHAIN_GO(3, 16, true, 32, true);     // phase stamps: this grid only
-        else if (p.chain == SHT_CHAIN_L32) CHAIN_GO(3, 16, false, 32, true);
-        else if (p.chain == SHT_CHAIN_REGTAB && p.chain_maxi == 3) CHAIN_GO(3, 16, false, 0, false);
-        else if (p.chain == SHT_CHAIN_REGTAB) CHAIN_GO(2, 16, false, 0, false);
+        if (chain == SHT_CHAIN_L32 && a.dbg != nullptr) CHAIN_GO(3, 16, true, 32, true);     // phase stamps: this grid only
+        else if (chain == SHT_CHAIN_L32) CHAIN_GO(3, 16, false, 32, true);
+        else if (chain == SHT_CHAIN_REGTAB && p.chain_maxi == 3) CHAIN_GO(3, 16, false, 0, false);
+        else if (chain == SHT_CHAIN_REGTAB) CHAIN_GO(2, 16, false, 0, false);
     }
     if (p.chain == SHT_CHAIN_RT && p.chain_maxi == 1) CHAIN_GO(1, 0, false, 0, false);
     else if (p.chain == SHT_CHAIN_RT) CHAIN_GO(3, 0, false, 0, false);
@@ -537,6 +668,7 @@ int launch_sht_chain(mtip_ctx* c, const double2* coeff, double2* grid, const Inv
     a.lmtab = c->d_lmtab;
     a.PTc = c->d_PTc;
     a.lmc = c->d_lmc;
+    a.PTw = c->d_PTw;
     a.gw = c->d_gw;
     a.norm = 2.0 * 3.14159265358979323846 / c->np;
     a.gsz = c->sht.chain_gsz;

@@ -149,6 +149,7 @@ mtip_ctx* mtip_create(const mtip_cfg* cfg, int device) {
     A(dev_alloc(c, &c->d_lmtab, c->npairs));
     A(dev_alloc(c, &c->d_PTc, (size_t)(c->nt / 2 + 1) * 768));
     A(dev_alloc(c, &c->d_lmc, 768));
+    if (L == 32 && c->nt == 64) A(dev_alloc(c, &c->d_PTw, (size_t)8 * 8 * 3 * 64));
     if (const char* e = std::getenv("MTIP_DEG2_SIMPLE")) c->deg2_simple = std::atoi(e) != 0;
     if (const char* e = std::getenv("MTIP_HANKEL_CT")) {
         const int v = std::atoi(e);

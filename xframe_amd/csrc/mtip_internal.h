@@ -312,6 +312,8 @@ struct mtip_ctx {
     DevBuf<double> d_PT;                           // (nt/2, npairs) theta-major Legendre table (fused SHT)
     DevBuf<double> d_PTc;                          // (nt/2, 768) the same table in the chunk layout of k_sht_chain's Legendre sums
     DevBuf<int> d_lmc;                             // (768) l | m << 8 of slot u * 256 + t, -1: none
+    DevBuf<double2> d_PTw;                         // (8, 8, 3, 64) d_PTc of the L = 32 plan (n_theta 64) by (wave, theta-pair couple, order u, lane): entry =
+                                                   // theta pairs 16 g + 2 c, 2 c + 1 of slot u * 256 + t, wave = 4 g + t / 64, lane = t % 64; null elsewhere
     DevBuf<uint8_t> d_ftmask;                      // (B) per-restart ft_stab of the next runs (mtip_set_ft_stab_mask)
     bool ftmask_mixed = false;                        // the mask has both values: steps with ft_stab take it per restart
     hipEvent_t turn_ev = nullptr;                     // mtip_run_group_async: end of this context's latest transform block
