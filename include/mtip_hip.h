@@ -606,6 +606,13 @@ int mtip_debug_chain_timing(mtip_ctx* ctx, int64_t* out);
  * workgroup (1, 2, 3 or 5: the instantiation that runs), n_tiles = column tiles (grid x), n_row_blocks = blocks of 128 output
  * shells (grid y).  Any of the three may be NULL. */
 int mtip_debug_hankel_tiles(mtip_ctx* ctx, int* ct, int* n_tiles, int* n_row_blocks);
+/* diagnostic: the SHT kernel choice of the context (ShtPlan, csrc/mtip_internal.h; made by mtip_set_angular_grid), host only,
+ * nothing is launched.  out (MTIP_SHT_PLAN_FIELDS) int32: [0] fwd (0 generic, 1 LDS, 2 register, 3 paired, 4 two-stage beyond
+ * L = 63), [1] inv (0 generic, 1 LDS, 2 register, 3 wide, 4 two-stage), [2] fwd_rp, [3] fwd_th, [4] fwd_maxi, [5] inv_rp,
+ * [6] inv_nsplit, [7] inv_jl, [8] real_update, [9] chain (0 off, 1 run-time tables, 2 tables in registers, 3 the L = 32
+ * form), [10] chain_gsz, [11] chain_thg, [12] chain_maxi */
+#define MTIP_SHT_PLAN_FIELDS 13
+int mtip_debug_sht_plan(mtip_ctx* ctx, int32_t* out);
 /* diagnostic: workgroups per restart of the real projection kernel (k_rproj: the host-packed slots of orders), 0 before the
  * first projection or when the general complex kernels are in use; negative = error code */
 int mtip_debug_projection_slots(mtip_ctx* ctx);

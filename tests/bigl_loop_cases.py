@@ -14,7 +14,10 @@ max(2, Nq / 2) of them inside, and every compared series is asserted to be non-z
 a problem is still positive everywhere inside the support (0.17 .. 0.47 after the first step in the oracle's runs), no constraint is
 violated there and the metric stays zero: those problems also get an upper value bound that cuts through that range.  Below four
 shells the cubic regridding of the invariants has too few nodes: those problems take the data grid itself (grid.max_q = the data's
-cut-off) and linear regridding, which is then the identity."""
+cut-off) and linear regridding, which is then the identity.
+
+problem() and check_loop_vs_oracle() also serve the default context below L = 64 (big_l = False: tests/sht_plan_cases.py, and the
+problems of parity_cases.check_split_shell_steps_vs_oracle and chain_latency_cases.check_fused_steps_ft_stab)."""
 import functools
 import os
 
@@ -59,8 +62,9 @@ MSG_FT_MASK = 'a per-restart ft_stab mask needs the fused one-pass step (cfg.fus
 
 # ------------------------------------------------------------------------------------------------------------------- problems
 @functools.lru_cache(maxsize=None)
-def problem(N, L, nt, nphi, n_used=None):
-    """(invariants, settings with GPU.big_l_loop) of one geometry; shared by the tests of a session and never modified"""
+def problem(N, L, nt, nphi, n_used=None, *, big_l=True):
+    """(invariants, settings) of one geometry, with GPU.big_l_loop unless big_l is False (the default context, for L <= 63:
+    tests/sht_plan_cases.py); shared by the tests of a session and never modified"""
     fpd = FourierPair(SHT(L, nt, nphi), N, S.data_cutoff(N), 2.0)
     q_d = S.midpoint_points(S.data_cutoff(N), N)
     small = N < 4
@@ -78,7 +82,7 @@ def problem(N, L, nt, nphi, n_used=None):
                                        'used_order_ids': np.arange(L + 1 if n_used is None else n_used)},
                         'real': {'projections': {'support': {'initial_support': {'max_radius': radius}},
                                                  'value_threshold': {'threshold': [0, VALUE_HI if N < 6 else False]}}}},
-        'GPU': {'big_l_loop': True}})
+        'GPU': {'big_l_loop': bool(big_l)}})
     return data, opt
 
 
@@ -96,9 +100,9 @@ def with_schedule(opt, schedule, order=None, methods=None):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_loop(shape4, schedule, seed, variant=None):
+def oracle_loop(shape4, schedule, seed, variant=None, big_l=True):
     """the oracle's phasing loop from its own seeded guess: computed once per session, shared, never modified"""
-    data, opt = problem(*shape4)
+    data, opt = problem(*shape4, big_l=big_l)
     opt = with_schedule(opt, schedule, *(NON_FXS if variant == 'non_fxs' else ()))
     om = OM.MTIP(opt, data)
     rho0 = om.density_guess(np.random.default_rng(seed))
@@ -116,27 +120,37 @@ def _n_steps(opt):
 
 
 # --------------------------------------------------------------------------------------------- cases 1, 2, 3, 7, 9: the loop
-def check_loop_vs_oracle(shape, schedule=SCHEDULE, lib_path=None, fused=True, seeds=(3, 4), variant=None, tag=''):
+def check_loop_vs_oracle(shape, schedule=SCHEDULE, lib_path=None, fused=True, seeds=(3, 4), variant=None, tag='', big_l=True,
+                         before_run=None, after_run=None, figures=None):
     """a short schedule from seeded guesses (a different one per restart), every restart against its own oracle run: the real error
     series the engine records (mtip_fetch_errors) against the oracle's at rtol 1e-8, the four densities at 1e-9 rel-L2, equal
-    supports; the compared series and the distance the density travelled are non-zero.  Returns the result dicts."""
+    supports; the compared series and the distance the density travelled are non-zero.  big_l = False: the default context (for
+    L <= 63).  before_run / after_run are called with the engine in front of and behind the loop; the dict `figures` receives the
+    largest deviations seen ('density', 'errors') before they are judged.  Returns the result dicts."""
     N, L, nt, nphi, B = shape
-    data, opt = problem(N, L, nt, nphi)
+    data, opt = problem(N, L, nt, nphi, big_l=big_l)
     opt = with_schedule(opt, schedule, *(NON_FXS if variant == 'non_fxs' else ()))
-    refs = [oracle_loop((N, L, nt, nphi), schedule, seeds[b], variant) for b in range(B)]
+    refs = [oracle_loop((N, L, nt, nphi), schedule, seeds[b], variant, big_l) for b in range(B)]
     R.MTIP.preinit(opt, data)
     m = R.MTIP(n_restarts=B, initial_densities=[r[0] for r in refs], lib_path=lib_path, fused=fused)
     m.generate_phasing_loop()
-    assert m.engine.big_l_loop and m.engine.L == L
+    assert m.engine.big_l_loop == big_l and m.engine.L == L
+    if before_run is not None:
+        before_run(m.engine)
     res = m.phasing_loop()
     n = _n_steps(opt)
     err = m.engine.fetch_errors(0, n)[0]
+    if after_run is not None:
+        after_run(m.engine)
     m.engine.close()
     for b in range(B):
         rho0, ref = refs[b]
         want = np.asarray(ref['error_dict']['real']['l2_projection_diff'])
         moved = rel_l2(res[b]['last_real_density'], rho0)
         dens = {k: rel_l2(res[b][k], ref[k]) for k in ('real_density', 'last_real_density', 'reciprocal_density', 'last_reciprocal_density')}
+        if figures is not None:
+            figures['density'] = max(figures.get('density', 0.0), max(dens.values()))
+            figures['errors'] = max(figures.get('errors', 0.0), float((np.abs(err[:, b] - want)[want > 0] / want[want > 0]).max()))
         print(f'{tag}{shape} fused={fused} restart {b}: errors {err[:, b]} oracle {want} max rel dev {np.abs(err[:, b] - want).max() / want.max():.2e}; '
               f'densities {dens}; moved {moved:.3f}; support differs at {(res[b]["last_support_mask"] != ref["last_support_mask"]).sum()}')
         assert want.shape == (n,) and (want > 0).any() and np.isfinite(want).all(), want       # not zeros against zeros

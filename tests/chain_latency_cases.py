@@ -9,15 +9,14 @@ L = 3..5, 6..10, 11..21, 22..42), 2 or 3 shells, 2 restarts.  L = 3 has two item
 import numpy as np
 
 import parity_cases as PC
-from helpers import rel_l2, golden_settings, OracleTransforms
-from oracle.fourier import FourierPair
-from oracle.sht import SHT
-from xframe_amd.fxs import synthetic as S
+from helpers import rel_l2
 from xframe_amd.fxs.engine import Engine
 
 # (N shells, L): all of them chain (n_phi <= 128 and a shell fits one CU)
 TRANSFORM_CASES = [(2, 3), (3, 4), (2, 5), (2, 9), (2, 10), (3, 15), (2, 16), (2, 31), (3, 32), (2, 33)]
-UNIT_L = [6, 7, 32, 33]             # unit coefficients: n_phi = 32 and 128, both parities
+# unit coefficients, both parities each: n_phi = 32 (6, 7); n_phi = 64 with accumulation groups of 128 (19, 20); n_phi = 128 with
+# tables in registers and 2 (l, m) pairs per thread (27, 28), 3 pairs (32, 33), groups of 512 and run-time tables (38, 39)
+UNIT_L = [6, 7, 19, 20, 27, 28, 32, 33, 38, 39]
 
 
 def check_transforms(N, L, lib_path):
@@ -73,13 +72,16 @@ def check_fused_steps_ft_stab(lib_path, N=4, L=32):
     against the reference-order step (separate transforms, k_sht_inv_wide with the coefficient difference) from the same state,
     at the bounds parity_cases.check_full_size_properties uses for fused against reference order"""
     import xframe_amd.fxs.hostsetup as hs
-    fpd = FourierPair(SHT(L), N, S.data_cutoff(N), 2.0)
-    data, _ = S.make_invariants(OracleTransforms(fpd), N, L)
-    opt = golden_settings(N, L)
+    import bigl_loop_cases as BL
+    # the problem of chain_diet_cases.steps_problem for this N x L (bigl_loop_cases.problem: particle, support and guess reach out to
+    # between shells 2 and 3, upper value bound inside the density's range): with the 250 A particle of the BASELINE configs one
+    # shell lies inside the support and the error sums of the three chained kernels are exactly zero in every step
+    data, opt = BL.problem(N, L, 0, 0, big_l=False)
+    radius = opt['particle_radius']
     out = {}
     for fused in (False, True):
         e = Engine(opt, data, n_batch=2, lib_path=lib_path, fused=fused)
-        rho0 = hs.bump_density(e.rs, e.shape, S.PARTICLE_RADIUS, 0.3, 2, np.random.default_rng(1000),
+        rho0 = hs.bump_density(e.rs, e.shape, radius, 0.3, 2, np.random.default_rng(1000),
                                e.rsetup.integrated_intensity, e.int_wr, e.int_wt)
         for b in range(2):
             e.set_density(b, rho0)
@@ -92,6 +94,8 @@ def check_fused_steps_ft_stab(lib_path, N=4, L=32):
     errs_b, rho_b, F_b = out[True]
     print('fused vs reference order, %d x L%d: density %.2e, F %.2e, first-step error ratio - 1 %.2e'
           % (N, L, rel_l2(rho_b, rho_a), rel_l2(F_b, F_a), np.abs(errs_b[0] / errs_a[0] - 1).max()))
+    print('error histories, reference order: %s fused: %s' % (errs_a[:, 0], errs_b[:, 0]))
     assert np.isfinite(errs_a).all() and np.isfinite(errs_b).all()
+    assert (errs_a > 0).all() and (errs_b > 0).all(), (errs_a, errs_b)                      # not zeros against zeros
     assert rel_l2(rho_b, rho_a) < 1e-7 and rel_l2(F_b, F_a) < 1e-7
     assert np.allclose(errs_b[0], errs_a[0], rtol=PC.TOL_STEP)

@@ -54,9 +54,16 @@ def launched_kernels(e, prefixes=('k_sht', 'k_fft', 'k_leg')):
 
 
 def check_transforms(N, L, lib_path, seed=0, mode='midpoint', expect_chain=None, n_theta=0, n_phi=0, n_batch=2,
-                     expect_kernels=None):
+                     expect_kernels=None, figures=None):
     """operators against the oracle at one geometry; expect_kernels = (forward, inverse, inverse -> forward): the SHT kernel names
-    one call of each launches (checked where the library logs its launches: the CPU emulator)"""
+    one call of each launches (checked where the library logs its launches: the CPU emulator); the dict `figures` receives the
+    largest rel-L2 deviation seen ('transforms'), before it is judged"""
+    def dev(a, b):
+        d = rel_l2(a, b)
+        if figures is not None:
+            figures['transforms'] = max(figures.get('transforms', 0.0), float(d))
+        return d
+
     e, fp = transforms_engine(N, L, lib_path, n_batch=n_batch, mode=mode, n_theta=n_theta, n_phi=n_phi)
     sht = fp.sht
     assert (e.n_theta, e.n_phi) == (sht.n_theta, sht.n_phi)
@@ -65,12 +72,12 @@ def check_transforms(N, L, lib_path, seed=0, mode='midpoint', expect_chain=None,
     co = cplx(rng, (n_batch, N, e.nlm))
     launched = []
     launched_kernels(e)
-    assert rel_l2(e.sht_forward(g), sht.forward_d(g)) < TOL_SHT
+    assert dev(e.sht_forward(g), sht.forward_d(g)) < TOL_SHT
     launched.append(launched_kernels(e))
-    assert rel_l2(e.sht_forward(g, 1), sht.forward_d(g * g.conj())) < TOL_SHT
-    assert rel_l2(e.sht_forward(g, 2), sht.forward_d(np.abs(g))) < TOL_SHT
+    assert dev(e.sht_forward(g, 1), sht.forward_d(g * g.conj())) < TOL_SHT
+    assert dev(e.sht_forward(g, 2), sht.forward_d(np.abs(g))) < TOL_SHT
     launched_kernels(e)
-    assert rel_l2(e.sht_inverse(co), sht.inverse_d(co)) < TOL_SHT
+    assert dev(e.sht_inverse(co), sht.inverse_d(co)) < TOL_SHT
     launched.append(launched_kernels(e))
     # the chained inverse -> forward kernel: the grid is that of the inverse transform, the coefficients those of the oracle's
     # two transforms one after the other
@@ -80,23 +87,23 @@ def check_transforms(N, L, lib_path, seed=0, mode='midpoint', expect_chain=None,
         if pro == 0:
             launched.append(launched_kernels(e))
         ref_g = sht.inverse_d(co)
-        assert rel_l2(gi, ref_g) < TOL_SHT
-        assert rel_l2(ci, sht.forward_d(ref_g * ref_g.conj() if pro else ref_g)) < TOL_SHT
+        assert dev(gi, ref_g) < TOL_SHT
+        assert dev(ci, sht.forward_d(ref_g * ref_g.conj() if pro else ref_g)) < TOL_SHT
     if expect_chain is not None:
         assert (e.profile_get('sht_chain')[1] > 0) == expect_chain, e.profile_get('sht_chain')
     e.profile(False)
     if expect_kernels is not None and launched[0] is not None:
         assert tuple(launched) == tuple(tuple(k) for k in expect_kernels), launched
-    assert rel_l2(e.hankel(co), fp.hankel(co)) < TOL_OP
-    assert rel_l2(e.hankel(co, True), fp.ihankel(co)) < TOL_OP
-    assert rel_l2(e.fourier_transform(g), fp.ft(g)) < TOL_SHT
-    assert rel_l2(e.fourier_transform(g, True), fp.ift(g)) < TOL_SHT
+    assert dev(e.hankel(co), fp.hankel(co)) < TOL_OP
+    assert dev(e.hankel(co, True), fp.ihankel(co)) < TOL_OP
+    assert dev(e.fourier_transform(g), fp.ft(g)) < TOL_SHT
+    assert dev(e.fourier_transform(g, True), fp.ift(g)) < TOL_SHT
     # size-independent properties: SHT round trip on band-limited data, linearity, Friedel symmetry of FT(real)
     band = e.sht_inverse(co)
-    assert rel_l2(e.sht_forward(band), co) < TOL_SHT
+    assert dev(e.sht_forward(band), co) < TOL_SHT
     a, b = 0.3 - 1.1j, -2.0 + 0.5j
     lin = e.fourier_transform(a * g + b * g[::-1])
-    assert rel_l2(lin, a * e.fourier_transform(g) + b * e.fourier_transform(g[::-1])) < TOL_SHT
+    assert dev(lin, a * e.fourier_transform(g) + b * e.fourier_transform(g[::-1])) < TOL_SHT
     e.close()
 
 
@@ -516,20 +523,22 @@ def check_group_run_identical_synthetic(cfg, lib_path=None, sizes=(2, 1, 1), n_h
 def check_split_shell_steps_vs_oracle(lib_path, N=6, L=44, fused=True):
     """Angular size of config 5 (128 x 256, L > 40) with few shells: the inverse SHT shares a shell between two
     workgroups there (two error partial sums per shell in the fused real-space epilogue).  2 HIO + SW + 1 ER against
-    the oracle from a seeded bump guess."""
-    fpd = FourierPair(SHT(L), N, S.data_cutoff(N), 2.0)
-    data, _ = S.make_invariants(OracleTransforms(fpd), N, L)
-    opt = golden_settings(N, L)
-    main = opt['main_loop']['sub_loops']['main']
-    main['methods']['HIO']['iterations'] = 2
-    main['methods']['ER']['iterations'] = 1
-    main['iterations'] = 1
+    the oracle from a seeded bump guess.  The problem is that of bigl_loop_cases.problem (particle, support and guess reach
+    out to between two shells): with the 250 A particle of the BASELINE configs and six shells one shell lies inside the
+    support and the error series, the target of this check, is exactly zero in every step."""
+    import bigl_loop_cases as BL
+    data, opt = BL.problem(N, L, 0, 0, big_l=False)
+    opt = BL.with_schedule(opt, (2, True, 1))
     om = OM.MTIP(opt, data)
     rho0 = om.density_guess(np.random.default_rng(3))
     ref = om.phasing_loop(rho0=rho0)
+    want = np.asarray(ref['error_dict']['main'])
+    print('split shells %d x L%d: oracle errors %s' % (N, L, want))
+    assert want.shape == (3,) and np.isfinite(want).all() and (want > 0).any(), want          # not zeros against zeros
     R.MTIP.preinit(opt, data)
     m = R.MTIP(n_restarts=2, initial_densities=[rho0] * 2, lib_path=lib_path, fused=fused)
     m.generate_phasing_loop()
+    assert m.engine.sht_plan()['inv_nsplit'] == 2
     res = m.phasing_loop()
     for b in range(2):
         r = res[b]

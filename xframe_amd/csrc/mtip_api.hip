@@ -1316,6 +1316,16 @@ int mtip_debug_hankel_tiles(mtip_ctx* c, int* ct, int* n_tiles, int* n_row_block
     return MTIP_OK;
 }
 
+int mtip_debug_sht_plan(mtip_ctx* c, int32_t* out) {
+    CTX_CHECK(c);
+    if (!out) return MTIP_EINVAL;
+    const ShtPlan& p = c->sht;
+    const int v[MTIP_SHT_PLAN_FIELDS] = {p.fwd, p.inv, p.fwd_rp, p.fwd_th, p.fwd_maxi, p.inv_rp, p.inv_nsplit, p.inv_jl,
+                                         p.real_update ? 1 : 0, p.chain, p.chain_gsz, p.chain_thg, p.chain_maxi};
+    for (int i = 0; i < MTIP_SHT_PLAN_FIELDS; ++i) out[i] = v[i];
+    return MTIP_OK;
+}
+
 int mtip_debug_projection_slots(mtip_ctx* c) {
     CTX_CHECK(c);
     return c->vr == VR_REAL ? c->pp.rp_n_slots : 0;

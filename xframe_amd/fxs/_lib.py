@@ -183,6 +183,7 @@ _SIGNATURES = {
     'mtip_profile_reset': (C.c_int, [c_void]),
     'mtip_debug_jacobi_sweeps': (C.c_int, [c_void, c_void]),
     'mtip_debug_projection_slots': (C.c_int, [c_void]),
+    'mtip_debug_sht_plan': (C.c_int, [c_void, c_void]),
     'mtip_debug_hankel_tiles': (C.c_int, [c_void, c_void, c_void, c_void]),
     'mtip_debug_chain_timing': (C.c_int, [c_void, c_void]),
     'mtip_debug_check_jacobi_schedule': (C.c_int, [c_void, C.c_int]),

@@ -871,6 +871,22 @@ class Engine(_lib.TensorOperands):
         self._ck(self.lib.mtip_debug_hankel_tiles(self.ctx, C.byref(ct), C.byref(nt), C.byref(nr)))
         return ct.value, nt.value, nr.value
 
+    SHT_PLAN_FIELDS = ('fwd', 'inv', 'fwd_rp', 'fwd_th', 'fwd_maxi', 'inv_rp', 'inv_nsplit', 'inv_jl', 'real_update',
+                       'chain', 'chain_gsz', 'chain_thg', 'chain_maxi')
+    SHT_FWD_KINDS = ('generic', 'lds', 'reg', 'pair', 'big')
+    SHT_INV_KINDS = ('generic', 'lds', 'reg', 'wide', 'big')
+    SHT_CHAIN_KINDS = ('off', 'rt', 'regtab', 'l32')
+
+    def sht_plan(self):
+        """the SHT kernel choice of this context (ShtPlan, csrc/mtip_internal.h) as a dict: the kinds as names, real_update as a
+        bool, the rest as ints; host only, nothing is launched"""
+        out = np.zeros(len(self.SHT_PLAN_FIELDS), np.int32)
+        self._ck(self.lib.mtip_debug_sht_plan(self.ctx, _lib.ptr(out)))
+        p = {k: int(v) for k, v in zip(self.SHT_PLAN_FIELDS, out)}
+        p['fwd'], p['inv'], p['chain'] = self.SHT_FWD_KINDS[p['fwd']], self.SHT_INV_KINDS[p['inv']], self.SHT_CHAIN_KINDS[p['chain']]
+        p['real_update'] = bool(p['real_update'])
+        return p
+
     def projection_slots(self):
         """workgroups per restart of the real projection kernel in the last call (0: general complex kernels)"""
         n = self.lib.mtip_debug_projection_slots(self.ctx)
