@@ -383,7 +383,9 @@ int mtip_op_deg2_to_cc(mtip_ctx* ctx, int n_q, int max_order, int n_delta, int d
  * (n_patterns, n_q, n_phi) uint8 with values 0 / 1 are what process_image holds at line 398.  A handle owns the accumulators
  * sum (n_q1, n_q2, n_phi) float64 and count (same shape) int32 on the context's device; its size is checked against the free
  * device memory at create (a null return; the message in mtip_last_error names the size).
- * cfg: filter_kind 1 = intensity_radial_pixel_filter 'average_sigma' with filter_k sigmas (0: none); the ROI mean runs over the
+ * cfg: filter_kind 1 = intensity_radial_pixel_filter 'average_sigma' with filter_k sigmas, 2 = 'median_mad' with filter_k median
+ * absolute deviations (correlate.py:405-406, 471-474; exact order statistics, csrc/k_ringfilter.h), 0: none; any other value is a
+ * null return whose message names the three.  The ROI mean runs over the
  * rings [roi_lo, roi_hi) where mask == 1: roi_filter rejects a pattern whose mean is outside [roi_min, roi_max], roi_normalize
  * divides the image by it; factor (n_q, n_phi) or NULL: polarisation x solid-angle table (565-591) multiplied in afterwards.
  * shared_mask: the mask is the same for every pattern (ignored with a filter, which makes it per pattern): masks is then
@@ -424,6 +426,16 @@ int mtip_correlate_merge(mtip_correlate* h, const double* sum, const int32_t* co
  * fc = fft(ccf)[..., :fc_n_max] (n_q1, n_q2, fc_n_max); a NULL output is skipped */
 int mtip_correlate_finalize(mtip_correlate* h, int symmetrize, int pos_pi2, int pos_pi, int pos_3pi2, int fc_n_max, double* ccf,
                             mtip_cdouble* fc);
+
+/* The median_mad statistics and filter alone (csrc/k_ringfilter.h; correlate.py:471-474 i_median_and_mad, 412 the filter), row by
+ * row: images (n_rows, n_phi) float64, masks (n_rows, n_phi) uint8.  Over a row's valid samples (mask != 0, value not NaN; n of them),
+ * v sorted: median = v[n / 2] for odd n, (v[n / 2 - 1] + v[n / 2]) / 2 for even n, mad the same rule on |x - median|, NaN for n = 0:
+ * np.nanmedian and scipy.stats.median_abs_deviation(nan_policy='omit') bit for bit.  masks_out = mask && !(|x - median| > k mad).
+ * median, mad (n_rows) and masks_out (n_rows, n_phi): a NULL output is skipped.  1 <= n_phi <= 2048 (any length: there is no
+ * transform) and n_rows >= 1, else MTIP_EINVAL with the limits in the message.  Valid samples are finite or NaN with |x| < 1e300;
+ * infinities are out of contract.  Host or device buffers. */
+int mtip_op_ring_median_mad(mtip_ctx* ctx, int n_rows, int n_phi, const double* images, const uint8_t* masks, double k, double* median,
+                            double* mad, uint8_t* masks_out);
 
 /* ---- correlate, the Cartesian stage: detector frames -> polar patterns (csrc/k_resample.h) ------------------------------------
  * process_image 377-398 of xframe/projects/fxs/correlate.py per pattern: mask = 0 where image < threshold_lo or image >

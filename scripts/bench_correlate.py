@@ -5,8 +5,13 @@ in a synchronise; five windows after a warm-up: median, min .. max), and inside 
 families corr_ring (k_corr_stats + k_corr_ring) and corr_pair (k_corr_pair).  Derived, with the counts stated where they are printed:
 the achieved FFT rate of k_corr_pair against the fp64 vector peak, and the accumulator bytes per pattern against HBM.
 The numpy restatement of the route (tests/correlate_cases.r_correlate) on this host with 1 and with 8 processes, as context.
-usage: python scripts/bench_correlate.py [--small] [--n-phi N [--rings R]]
+usage: python scripts/bench_correlate.py [--small] [--n-phi N [--rings R]] [--filter KIND] [--batch B]
   --small       the small shape only
+  --filter KIND the radial pixel filter: none (default), average_sigma (k_corr_stats) or median_mad (k_corr_stats_mad,
+                csrc/k_ringfilter.h; Correlator(..., median_mad=True)), each at 3 sigmas / MADs.  With a filter 4 % of the samples are
+                outliers, the masks are per pattern (a filter makes them so) and the statistics kernel's own event bracket (family
+                corr_stats, one launch per chunk of 32 patterns) is printed per launch.
+  --batch B     that batch size only
   --n-phi N     one shape only: R rings (default 256) x N angles.  A length the radix-2 kernels do not take (1536, the default settings'
                 length, 1920, 2000, 2048 ..) goes through a handle made with general_n_phi=True (k_corr_pair_g, csrc/k_correlate_mr.h);
                 the operation count 5 m log2 m is kept for it as the convention the rates are stated in."""
@@ -27,15 +32,23 @@ FP64_VECTOR_PEAK = 78e12
 BATCHES = (1, 8, 32)
 
 
-def settings_for(n_q, n_phi):
+FILTERS = ('none', 'average_sigma', 'median_mad')
+
+
+def settings_for(n_q, n_phi, filt='none'):
     import correlate_cases as CO
-    return CO.make_settings(n_q, n_phi, q_step=2.0 ** -10, q_min=2.0 ** -10)
+    s = CO.make_settings(n_q, n_phi, q_step=2.0 ** -10, q_min=2.0 ** -10)
+    if filt != 'none':
+        s['intensity_radial_pixel_filter'] = [True, [filt, 3]]
+    return s
 
 
-def patterns(n_q, n_phi, P, seed=0):
+def patterns(n_q, n_phi, P, seed=0, outliers=False):
     rng = np.random.default_rng(seed)
     masks = (rng.random((P, n_q, n_phi)) < 0.85).astype(np.uint8)
     images = (200.0 * (1.0 + 0.4 * rng.random((P, n_q, n_phi)))) * masks
+    if outliers:
+        images[rng.random(images.shape) < 0.04] *= 2.5
     return images, masks
 
 
@@ -79,22 +92,28 @@ def main():
     from xframe_amd.fxs.engine import Engine
     e = Engine({'grid': {'n_radial_points': 8, 'max_order': 2}}, None, n_batch=1, max_q=1.0)
     shapes = ((64, 256),) if '--small' in sys.argv else ((256, 1024), (64, 256))
+    filt = sys.argv[sys.argv.index('--filter') + 1] if '--filter' in sys.argv else 'none'
+    if filt not in FILTERS:
+        raise SystemExit('--filter takes one of ' + ', '.join(FILTERS))
+    batches = (int(sys.argv[sys.argv.index('--batch') + 1]),) if '--batch' in sys.argv else BATCHES
     if '--n-phi' in sys.argv:
         rings = int(sys.argv[sys.argv.index('--rings') + 1]) if '--rings' in sys.argv else 256
         shapes = ((rings, int(sys.argv[sys.argv.index('--n-phi') + 1])),)
     for n_q, n_phi in shapes:
-        settings = settings_for(n_q, n_phi)
+        settings = settings_for(n_q, n_phi, filt)
         general = n_phi not in CR.SUPPORTED_N_PHI
-        images, masks = patterns(n_q, n_phi, max(BATCHES))
+        images, masks = patterns(n_q, n_phi, max(batches), outliers=filt != 'none')
         d_img = torch.from_numpy(images).cuda()
         d_mask = torch.from_numpy(masks).cuda()
         n_acc = n_q * n_q * n_phi
         print('%d rings x %d angles%s, %d x %d pairs: accumulator %.1f MB (sum f64 + count int32), shared-mask table %.1f MB' %
               (n_q, n_phi, ' (general_n_phi: mixed-radix kernels)' if general else '', n_q, n_q, 12e-6 * n_acc, 8e-6 * n_acc))
-        for shared in (True, False):
+        if filt != 'none':
+            print('  intensity_radial_pixel_filter: %s, 3' % filt)
+        for shared in ((True, False) if filt == 'none' else (False,)):
             per_pattern = {}
-            for B in BATCHES:
-                c = CR.Correlator(e, settings, shared_mask=shared, general_n_phi=general)
+            for B in batches:
+                c = CR.Correlator(e, settings, shared_mask=shared, general_n_phi=general, median_mad=filt == 'median_mad')
                 m = d_mask[0] if shared else d_mask[:B]
                 t0 = time.perf_counter()
                 c.add(d_img[:B], m)                                    # warm-up (code objects, the shared mask's table)
@@ -102,7 +121,7 @@ def main():
                 torch.cuda.synchronize()
                 one = (time.perf_counter() - t0) / 2
                 reps = int(min(64, max(2, round(0.4 / max(one, 1e-4)))))
-                wall, ring, pair = [], [], []
+                wall, ring, pair, stat = [], [], [], []
                 for _ in range(5):
                     e.profile(True)
                     torch.cuda.synchronize()
@@ -116,6 +135,8 @@ def main():
                     assert n == reps, (n, reps)
                     ring.append(r_ms / (reps * B))
                     pair.append(p_ms / (reps * B))
+                    s_ms, s_n = e.profile_get('corr_stats')
+                    stat.append(s_ms / max(s_n, 1))
                     e.profile(False)
                 c.close()
                 per_pattern[B] = float(np.median(wall))
@@ -125,14 +146,19 @@ def main():
                 print('  %s mask, batch %2d (%2d calls per window): add %s per pattern' % ('shared     ' if shared else 'per-pattern', B, reps,
                                                                                          stats(wall)))
                 print('      k_corr_pair %s | k_corr_stats + k_corr_ring %s per pattern' % (stats(pair), stats(ring)))
+                if filt != 'none':
+                    print('      %s alone: %s per launch of %d patterns x %d rings' %
+                          ('k_corr_stats_mad' if filt == 'median_mad' else 'k_corr_stats', stats(stat), min(B, 32), n_q))
                 print('      k_corr_pair: %.2f GFLOP of FFT per pattern -> %.2f TFLOP/s = %.1f %% of the fp64 vector peak (78 TFLOP/s); '
                       'accumulator traffic %.1f MB per pattern = %.3f ms at 8 TB/s (%.1f %% of the kernel time)' %
                       (1e-9 * fl, 1e-12 * fl / k, 100 * fl / k / FP64_VECTOR_PEAK, 1e-6 * acc_bytes, 1e3 * acc_bytes / HBM_PEAK,
                        100 * acc_bytes / HBM_PEAK / k))
-            print('  %s mask: ms per pattern at batch 1 / 8 / 32 = %.3f / %.3f / %.3f  (batch 32 below batch 1: %s)' %
-                  ('shared' if shared else 'per-pattern', per_pattern[1], per_pattern[8], per_pattern[32], per_pattern[32] < per_pattern[1]))
+            if batches == BATCHES:
+                print('  %s mask: ms per pattern at batch 1 / 8 / 32 = %.3f / %.3f / %.3f  (batch 32 below batch 1: %s)' %
+                      ('shared' if shared else 'per-pattern', per_pattern[1], per_pattern[8], per_pattern[32],
+                       per_pattern[32] < per_pattern[1]))
         del d_img, d_mask
-        if '--n-phi' not in sys.argv:                                  # (a single shape is asked for the device figures alone)
+        if '--n-phi' not in sys.argv and filt == 'none' and batches == BATCHES:   # (else the device figures alone are asked for)
             cpu_context(n_q, n_phi, 1 if n_q >= 256 else 8)
     e.close()
 

@@ -5,6 +5,8 @@
 //   xframe/projects/fxs/projectLibrary/cross_correlation.py        ccf_analysis
 // Included by k_extract.hip (its entry points stand beside mtip_op_cc_to_deg2).  Per batch of patterns, in chunks of COR_CHUNK:
 //   k_corr_stats   one workgroup per (pattern, ring): the average_sigma pixel filter and the ring sums the pattern-wide decisions need
+//                  (a handle made with filter_kind = 2 launches k_corr_stats_mad of k_ringfilter.h in its place: the median_mad filter,
+//                  exact order statistics by a radix select, the same three output arrays)
 //   k_corr_ring    one workgroup per (pattern, ring): fully-masked / ROI decisions, ROI normalisation, the correction factor table,
 //                  waxs, and the forward real FFTs F = rfft(image), G = rfft(mask); flags and waxs stay on the device
 //   k_corr_pair    a wave owns one pair (q1, q2) with its whole Delta axis: sum (f64) and count (int32) sit in its registers while it
@@ -153,6 +155,8 @@ __global__ void __launch_bounds__(COR_RT) k_corr_stats(CorRingArgs a) {
         a.rs[(size_t)p * a.n_q + q] = sum;
     }
 }
+
+#include "k_ringfilter.h"
 
 // where input point j of an n_phi-point transform is stored, and that transform: radix 2, or the handle's mixed-radix plan
 template <bool GEN>
@@ -479,8 +483,10 @@ extern "C" mtip_correlate* mtip_correlate_create_ex(mtip_ctx* c, const mtip_corr
         c->err = msg;
         return nullptr;
     }
-    if (cfg->filter_kind != 0 && cfg->filter_kind != 1) {
-        c->err = "correlate_create: filter_kind must be 0 (none) or 1 (average_sigma); median_mad (correlate.py:405-406) is not built";
+    if (cfg->filter_kind < 0 || cfg->filter_kind > 2) {
+        snprintf(msg, sizeof msg, "correlate_create: filter_kind = %d: it must be 0 (none), 1 (average_sigma) or 2 (median_mad)",
+                 (int)cfg->filter_kind);
+        c->err = msg;
         return nullptr;
     }
     for (int i = 0; i < cfg->n_q1 + cfg->n_q2; ++i) {
@@ -680,7 +686,12 @@ extern "C" int mtip_correlate_add(mtip_correlate* h, int n_patterns, const doubl
         r.do_G = shared ? 0 : 1;
         {
             ProfScope ps(c, "corr_ring");
-            hipLaunchKernelGGL(k_corr_stats, dim3((unsigned)f.n_q, (unsigned)pc), dim3(COR_RT), 0, c->stream, r);
+            {
+                ProfScope pt(c, "corr_stats");
+                const dim3 g((unsigned)f.n_q, (unsigned)pc), b(COR_RT);
+                if (f.filter_kind == 2) hipLaunchKernelGGL(k_corr_stats_mad, g, b, 0, c->stream, r, (double*)nullptr, (double*)nullptr);
+                else hipLaunchKernelGGL(k_corr_stats, g, b, 0, c->stream, r);
+            }
             cor_launch_ring(h, (unsigned)pc, r);
         }
         a.good = d_good + p0;

@@ -174,6 +174,7 @@ _SIGNATURES = {
     'mtip_correlate_get_partial': (C.c_int, [c_void, c_void, c_void, c_void, c_void]),
     'mtip_correlate_merge': (C.c_int, [c_void, c_void, c_void, C.c_int, c_void, c_void]),
     'mtip_correlate_finalize': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void]),
+    'mtip_op_ring_median_mad': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, C.c_double, c_void, c_void, c_void]),
     'mtip_resample_create': (c_void, [c_void, C.POINTER(MtipResampleCfg), c_void, c_void, c_void, c_void]),
     'mtip_resample_destroy': (None, [c_void]),
     'mtip_resample_run': (C.c_int, [c_void, C.c_int, c_void, C.c_int, c_void, c_void, c_void, C.POINTER(C.c_int64)]),

@@ -154,6 +154,32 @@ def _frames(a, H, W, what, on_device):
     return a.contiguous() if on_device else np.ascontiguousarray(a)
 
 
+def ring_median_mad(engine, images, masks, k):
+    """``i_median_and_mad`` (correlate.py:471-474) and the filter of line 412 on rows: images (n_rows, n_phi) float64, masks of the same
+    shape (non-zero: valid), n_phi = 1 .. 2048.  Returns (median (n_rows), mad (n_rows), masks_out (n_rows, n_phi) uint8) with
+    masks_out = mask & ~(|x - median| > k mad); numpy arrays in and out, or torch tensors on the engine's device in and out."""
+    on_device = not isinstance(images, np.ndarray) and hasattr(images, 'data_ptr')
+    if on_device:
+        import torch
+        images = images.to(torch.float64).contiguous()
+        masks = (torch.as_tensor(masks, device=images.device) != 0).to(torch.uint8).contiguous()
+    else:
+        images, masks = _lib.as_f64(images), _lib.as_u8(np.asarray(masks) != 0)
+    if images.ndim != 2 or tuple(masks.shape) != tuple(images.shape):
+        raise ValueError(f'correlate: ring_median_mad takes images and masks of one shape (n_rows, n_phi), got {tuple(images.shape)} '
+                         f'and {tuple(masks.shape)}')
+    n_rows, n_phi = int(images.shape[0]), int(images.shape[1])
+    if on_device:
+        med = torch.empty(n_rows, dtype=torch.float64, device=images.device)
+        mad, out = torch.empty_like(med), torch.empty_like(masks)
+        ptrs = [engine._tp(t) for t in (images, masks, med, mad, out)]
+    else:
+        med, mad, out = np.empty(n_rows), np.empty(n_rows), np.empty((n_rows, n_phi), np.uint8)
+        ptrs = [_lib.ptr(t) for t in (images, masks, med, mad, out)]
+    engine._ck(engine.lib.mtip_op_ring_median_mad(engine.ctx, n_rows, n_phi, ptrs[0], ptrs[1], float(k), ptrs[2], ptrs[3], ptrs[4]))
+    return med, mad, out
+
+
 class Resampler:
     """The Cartesian stage of ``process_image`` (382-398) on the engine's device: ``run(images, masks=None)`` takes detector frames
     (P, H, W) float32 / float64 and optional initial masks (P, H, W) or (H, W) of 0 / 1 (default: ones) to
@@ -290,9 +316,12 @@ class Correlator:
 
     general_n_phi=True (None: settings['GPU']['general_n_phi'], default False): n_phi may be any even length in 16 .. 2048 whose only
     prime factors are 2, 3 and 5 -- the default settings' 1536 among them -- through ``mtip_correlate_create_ex``; without it the
-    lengths are SUPPORTED_N_PHI.  ``general_n_phi_near`` names the nearest such lengths."""
+    lengths are SUPPORTED_N_PHI.  ``general_n_phi_near`` names the nearest such lengths.
 
-    def __init__(self, engine, settings=None, shared_mask=False, binary_mask=None, background=None, general_n_phi=None):
+    median_mad=True (None: settings['GPU']['median_mad'], default False): intensity_radial_pixel_filter [True, ['median_mad', k]] runs
+    on the device (``csrc/k_ringfilter.h``: exact medians, numpy's and scipy's bit for bit); without it that setting raises."""
+
+    def __init__(self, engine, settings=None, shared_mask=False, binary_mask=None, background=None, general_n_phi=None, median_mad=None):
         self.engine = engine
         self._frame_arrays = (binary_mask, background)
         self.resampler = None
@@ -314,11 +343,16 @@ class Correlator:
             raise NotImplementedError(f'correlate: n_phi = {self.n_phi} is not built; supported lengths: {SUPPORTED_N_PHI}')
         filt = opt['intensity_radial_pixel_filter']
         self.filter = bool(filt[0])
-        if self.filter and filt[1][0] == 'median_mad':
+        if median_mad is None:
+            median_mad = (opt.get('GPU') or {}).get('median_mad', False)
+        self.median_mad = bool(median_mad)
+        if self.filter and filt[1][0] == 'median_mad' and not self.median_mad:
             raise NotImplementedError("correlate: intensity_radial_pixel_filter 'median_mad' (correlate.py:405-406, i_median_and_mad "
-                                      '471-474) is not built; average_sigma is')
-        if self.filter and filt[1][0] != 'average_sigma':
+                                      "471-474) is opt-in: Correlator(..., median_mad=True) or settings['GPU']['median_mad'] = True; "
+                                      'average_sigma needs no flag')
+        if self.filter and filt[1][0] not in ('average_sigma', 'median_mad'):
             raise ValueError(f'correlate: unknown intensity_radial_pixel_filter {filt[1][0]!r} (correlate.py:408)')
+        filter_kind = 0 if not self.filter else (2 if filt[1][0] == 'median_mad' else 1)
         roi_n, roi_f = opt['ROI_normalization'], opt['ROI_mean_filter']
         qvals = g['qvals']
         roi_lo = roi_hi = 0
@@ -338,7 +372,7 @@ class Correlator:
         self.n_q1, self.n_q2 = len(self.q1), len(self.q2)
         self.shared_mask = bool(shared_mask) and not self.filter
         self._mask0 = None
-        cfg = _lib.MtipCorrelateCfg(self.n_q, self.n_phi, self.n_q1, self.n_q2, 1 if self.filter else 0, roi_lo, roi_hi,
+        cfg = _lib.MtipCorrelateCfg(self.n_q, self.n_phi, self.n_q1, self.n_q2, filter_kind, roi_lo, roi_hi,
                                     1 if roi_f[0] else 0, 1 if roi_n[0] else 0, 1 if self.shared_mask else 0,
                                     float(filt[1][1]) if self.filter else 0.0, float(roi_f[1]), float(roi_f[2]))
         tables = (engine.ctx, C.byref(cfg), _lib.ptr(self.q1), _lib.ptr(self.q2), _lib.ptr(self.factor))
