@@ -357,6 +357,40 @@ int mtip_op_cc_prepare_masked(mtip_ctx* ctx, int n_q, int n_delta, uint32_t flag
 int mtip_op_cc_lstsq_deg2(mtip_ctx* ctx, int n_q, int n_delta, int n_orders, const int32_t* orders, const double* cc,
                           const uint8_t* cc_mask, const double* cos_sin_theta, const double* cos_delta, mtip_cdouble* b_out, int32_t* n_valid,
                           double* rcond);
+/* mtip_op_cc_lstsq_deg2_minnorm: the same fit with LAPACK's answer for rank-deficient pairs (numpy.linalg.lstsq with rcond = None,
+ * fxs_invariant_tools.py:513).  The kernel of mtip_op_cc_lstsq_deg2 runs first and unchanged: a pair it solves at full rank
+ * (n_valid >= n_orders and rcond >= 1e-12) keeps the same bits and gets rank = n_orders.  The pairs it leaves, 0 < n_valid <
+ * n_orders or rcond < 1e-12, are compacted into a list for a second kernel: the same Householder reduction, then a one-sided
+ * Jacobi on the rows of the triangle (a trapezoid when n_valid < n_orders) with the right-hand side riding along, and
+ *   x = sum_{sigma_i > cut} v_i (u_i^T c) / sigma_i,  cut = eps max(n_valid, n_orders) sigma_max;
+ * rank (n_q, n_q) int32 counts the kept singular values there; a pair without a valid sample gets zeros and rank 0.  n_valid and
+ * rcond come back as from mtip_op_cc_lstsq_deg2.  Known limit, unchanged: a pair whose unpivoted triangle estimate is >= 1e-12
+ * while sigma_min / sigma_max lies below the cut counts as full rank.  Limits, buffers and errors as for mtip_op_cc_lstsq_deg2. */
+int mtip_op_cc_lstsq_deg2_minnorm(mtip_ctx* ctx, int n_q, int n_delta, int n_orders, const int32_t* orders, const double* cc,
+                                  const uint8_t* cc_mask, const double* cos_sin_theta, const double* cos_delta, mtip_cdouble* b_out,
+                                  int32_t* n_valid, double* rcond, int32_t* rank);
+/* The stages of modify_cross_correlation (235-289) around those of mtip_op_cc_prepare_masked (csrc/k_extract_cond.h), whole-array
+ * passes over cc (n_q, n_q, n_delta) float64.  Shared: n_q <= 4096, n_delta <= 4096, else MTIP_EINVAL with a message and untouched
+ * outputs; an output must not alias its input; every buffer may be host memory or memory of the context's device;
+ * average_intensity (n_q) may be null, otherwise I(q1) I(q2) is subtracted while cc is read (245-247: the subtraction comes before
+ * anything else, so the first stage that runs takes it).  None of the three reads or changes a mask, except the binned mean.
+ * mtip_op_cc_lowpass_q: low_pass_order_in_q (248-252): scipy.signal.sosfilt of ONE second-order section, zero initial state,
+ *   along axis 0 and then along axis 1.  sos: the six numbers b0 b1 b2 a0 a1 a2 with a0 = 1, as
+ *   scipy.signal.butter(1, value, 'lp', fs = n_q, output = 'sos')[0] gives them.
+ * mtip_op_cc_harmonic_filter: enforce_max_order / enforce_zero_odd_harmonics (253-263): per pair irfft(Z rfft(row) / n, n) n, Z
+ *   zeroing the harmonics above max_order (max_order < 0: no such cut) and, with zero_odd != 0, the odd ones; at least one of the
+ *   two must be asked for; n_delta >= 2, even or odd.
+ * mtip_op_cc_binned_mean: apply_binned_mean (281-283, binned_mean 308-332).  The row is rolled by n_roll (numpy.roll) and cut
+ *   into n_bins runs, bin b holding the rolled samples bin_start[b] .. bin_start[b + 1] - 1; bin_start (n_bins + 1) int32 must rise
+ *   strictly from 0 to n_delta, and 0 <= n_roll < n_delta: the caller forms both with the reference's expressions (312-323), the
+ *   kernel never recomputes a bin edge.  cc_out (n_q, n_q, n_bins): the mean of the valid samples of the bin; mask_out the same
+ *   shape, uint8: 1 where the bin has a valid sample; a bin without one gets the value 0 and mask 0 (329). */
+int mtip_op_cc_lowpass_q(mtip_ctx* ctx, int n_q, int n_delta, const double* sos, const double* cc, const double* average_intensity,
+                         double* cc_out);
+int mtip_op_cc_harmonic_filter(mtip_ctx* ctx, int n_q, int n_delta, int max_order, int zero_odd, const double* cc,
+                               const double* average_intensity, double* cc_out);
+int mtip_op_cc_binned_mean(mtip_ctx* ctx, int n_q, int n_delta, int n_bins, const int32_t* bin_start, int n_roll, const double* cc,
+                           const uint8_t* cc_mask, const double* average_intensity, double* cc_out, uint8_t* mask_out);
 /* degree-2 invariants -> cross-correlation, the inverse of mtip_op_cc_to_deg2 and the back half of the worker `simulate_ccd`
  * (csrc/k_simulate.h; fxs_invariant_tools.py:941-990 deg2_invariant_to_cc_3d, 934-939 deg2_invariant_to_cc_2d).
  * bl (max_order + 1, n_q, n_q) complex128.

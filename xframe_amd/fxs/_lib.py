@@ -165,6 +165,11 @@ _SIGNATURES = {
     'mtip_op_cc_to_deg2_wide': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_cc_prepare_masked': (C.c_int, [c_void, C.c_int, C.c_int, C.c_uint32, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_cc_lstsq_deg2': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    'mtip_op_cc_lstsq_deg2_minnorm': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
+                                                 c_void]),
+    'mtip_op_cc_lowpass_q': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void]),
+    'mtip_op_cc_harmonic_filter': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
+    'mtip_op_cc_binned_mean': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_deg2_to_cc': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void]),
     'mtip_correlate_create': (c_void, [c_void, C.POINTER(MtipCorrelateCfg), c_void, c_void, c_void]),
     'mtip_correlate_create_ex': (c_void, [c_void, C.POINTER(MtipCorrelateCfg), c_void, c_void, c_void, C.c_uint32]),

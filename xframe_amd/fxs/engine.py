@@ -538,6 +538,126 @@ class Engine(_lib.TensorOperands):
                                                 _lib.ptr(phis), ptrs[2], ptrs[3], ptrs[4]))
         return out, nv, rc
 
+    def cc_lstsq_deg2_minnorm(self, cc, cc_mask, orders, thetas, phis):
+        """mtip_op_cc_lstsq_deg2_minnorm: ``cc_lstsq_deg2`` with LAPACK's truncated minimum-norm solution (numpy.linalg.lstsq,
+        rcond=None) for the pairs that are rank deficient -- 0 < n_valid < n_orders, or rcond < 1e-12; every other pair keeps the
+        bits of ``cc_lstsq_deg2``.  Same arguments; returns (B, n_valid, rcond, rank (Nq, Nq) int32: n_orders for a pair solved
+        at full rank, the number of singular values kept for a deficient one, 0 for a pair without a valid sample)."""
+        on_device, cc, cc_mask = self._cc_pair('cc_lstsq_deg2_minnorm', cc, cc_mask)
+        nq, nd = int(cc.shape[0]), int(cc.shape[2])
+        orders = np.ascontiguousarray(orders, dtype=np.int32)
+        thetas, phis = np.asarray(thetas, dtype=float), np.asarray(phis, dtype=float)
+        if orders.ndim != 1 or orders.size < 1 or thetas.shape != (nq,) or phis.shape != (nd,):
+            raise ValueError('cc_lstsq_deg2_minnorm: orders (n_orders >= 1), thetas (Nq) and phis (n_delta) do not fit cc %r'
+                             % (tuple(cc.shape),))
+        cth, phis = _lib.as_f64(np.stack([np.cos(thetas), np.sin(thetas)])), _lib.as_f64(np.cos(phis))
+        shape = (int(max(orders.max(), 0)) + 1, nq, nq)
+        if on_device:
+            import torch
+            out = torch.empty(shape, dtype=torch.complex128, device=cc.device)
+            nv = torch.empty((nq, nq), dtype=torch.int32, device=cc.device)
+            rc = torch.empty((nq, nq), dtype=torch.float64, device=cc.device)
+            rank = torch.empty((nq, nq), dtype=torch.int32, device=cc.device)
+            ptrs = tuple(self._tp(t) for t in (cc, cc_mask, out, nv, rc, rank))
+        else:
+            out, nv, rc, rank = np.empty(shape, complex), np.empty((nq, nq), np.int32), np.empty((nq, nq)), np.empty((nq, nq), np.int32)
+            ptrs = tuple(_lib.ptr(t) for t in (cc, cc_mask, out, nv, rc, rank))
+        self._ck(self.lib.mtip_op_cc_lstsq_deg2_minnorm(self.ctx, nq, nd, int(orders.size), _lib.ptr(orders), ptrs[0], ptrs[1],
+                                                        _lib.ptr(cth), _lib.ptr(phis), ptrs[2], ptrs[3], ptrs[4], ptrs[5]))
+        return out, nv, rc, rank
+
+    # ------------------------------------------------------------------ extract: the rest of modify_cross_correlation (fxs_invariant_tools.py:248-263, 281-283, 308-332)
+    def _cc_array(self, name, cc):
+        """cc float64 (Nq, Nq, n_delta): a numpy array, or a tensor on this engine's device"""
+        on_device = not isinstance(cc, np.ndarray) and hasattr(cc, 'data_ptr')
+        if on_device:
+            import torch
+            if cc.dtype != torch.float64 or not cc.is_cuda:
+                raise TypeError('%s: a tensor must be float64 on the GPU' % name)
+            cc = cc.contiguous()
+        else:
+            cc = np.asarray(cc)
+            cc = _lib.as_f64(cc.real if np.iscomplexobj(cc) else cc)
+        if cc.ndim != 3 or cc.shape[0] != cc.shape[1]:
+            raise ValueError('%s: cc must have shape (Nq, Nq, n_delta), got %r' % (name, tuple(cc.shape)))
+        return on_device, cc
+
+    def _cc_average(self, average_intensity, nq):
+        if average_intensity is None:
+            return None
+        avg = _lib.as_f64(average_intensity)
+        assert avg.shape == (nq,), avg.shape
+        return avg
+
+    def cc_lowpass_q(self, cc, sos, average_intensity=None):
+        """mtip_op_cc_lowpass_q: scipy.signal.sosfilt(sos, ., axis=0) then axis=1 for one second-order section with zero initial
+        state (low_pass_order_in_q).  cc (Nq, Nq, n_delta) float64, numpy or a tensor on this engine's device (the result then
+        stays on it); sos: (1, 6) or (6,) with a0 = 1; average_intensity (Nq): I(q1) I(q2) is subtracted first."""
+        on_device, cc = self._cc_array('cc_lowpass_q', cc)
+        nq, nd = int(cc.shape[0]), int(cc.shape[2])
+        sos = _lib.as_f64(sos).reshape(-1)
+        if sos.shape != (6,):
+            raise ValueError('cc_lowpass_q: one second-order section (six coefficients) is built, got %d numbers' % sos.size)
+        avg = self._cc_average(average_intensity, nq)
+        if on_device:
+            import torch
+            out = torch.empty_like(cc)
+            p_in, p_out = self._tp(cc), self._tp(out)
+        else:
+            out = np.empty_like(cc)
+            p_in, p_out = _lib.ptr(cc), _lib.ptr(out)
+        self._ck(self.lib.mtip_op_cc_lowpass_q(self.ctx, nq, nd, _lib.ptr(sos), p_in, _lib.ptr(avg), p_out))
+        return out
+
+    def cc_harmonic_filter(self, cc, max_order=None, zero_odd=False, average_intensity=None):
+        """mtip_op_cc_harmonic_filter: per pair irfft(Z rfft(row)), Z zeroing the harmonics above max_order (None: no cut) and, with
+        zero_odd, the odd ones (enforce_max_order, enforce_zero_odd_harmonics).  cc and average_intensity as for
+        ``cc_lowpass_q``."""
+        on_device, cc = self._cc_array('cc_harmonic_filter', cc)
+        nq, nd = int(cc.shape[0]), int(cc.shape[2])
+        if max_order is None and not zero_odd:
+            raise ValueError('cc_harmonic_filter: neither max_order nor zero_odd is set')
+        if max_order is not None and int(max_order) < 0:
+            raise ValueError('cc_harmonic_filter: max_order %r is negative' % (max_order,))
+        avg = self._cc_average(average_intensity, nq)
+        if on_device:
+            import torch
+            out = torch.empty_like(cc)
+            p_in, p_out = self._tp(cc), self._tp(out)
+        else:
+            out = np.empty_like(cc)
+            p_in, p_out = _lib.ptr(cc), _lib.ptr(out)
+        self._ck(self.lib.mtip_op_cc_harmonic_filter(self.ctx, nq, nd, -1 if max_order is None else int(max_order), 1 if zero_odd else 0,
+                                                     p_in, _lib.ptr(avg), p_out))
+        return out
+
+    def cc_binned_mean(self, cc, cc_mask, bin_start, n_roll, average_intensity=None):
+        """mtip_op_cc_binned_mean: the masked mean over runs of the row rolled by n_roll (apply_binned_mean); bin_start
+        (n_bins + 1) and n_roll as ``extract.binned_mean_tables`` forms them with the reference's expressions.  cc and cc_mask as
+        for ``cc_prepare_masked``.  Returns (cc' (Nq, Nq, n_bins), mask' bool: False where a bin has no valid sample, its value
+        then 0)."""
+        on_device, cc, cc_mask = self._cc_pair('cc_binned_mean', cc, cc_mask)
+        nq, nd = int(cc.shape[0]), int(cc.shape[2])
+        bin_start = np.ascontiguousarray(bin_start, dtype=np.int32)
+        if bin_start.ndim != 1 or bin_start.size < 2:
+            raise ValueError('cc_binned_mean: bin_start must hold n_bins + 1 >= 2 offsets')
+        n_bins = int(bin_start.size) - 1
+        avg = self._cc_average(average_intensity, nq)
+        fits = nq <= 4096 and nd <= 4096                                # (beyond the limits the call writes nothing: no large output)
+        shape = (nq, nq, n_bins) if fits else (1,)
+        if on_device:
+            import torch
+            out = torch.empty(shape, dtype=torch.float64, device=cc.device)
+            mout = torch.empty(shape, dtype=torch.uint8, device=cc.device)
+            ptrs = (self._tp(cc), self._tp(cc_mask), self._tp(out), self._tp(mout))
+        else:
+            out, mout = np.empty(shape), np.empty(shape, np.uint8)
+            ptrs = (_lib.ptr(cc), _lib.ptr(cc_mask), _lib.ptr(out), _lib.ptr(mout))
+        self._ck(self.lib.mtip_op_cc_binned_mean(self.ctx, nq, nd, n_bins, _lib.ptr(bin_start), int(n_roll), ptrs[0], ptrs[1],
+                                                 _lib.ptr(avg), ptrs[2], ptrs[3]))
+        mout = mout.view(torch.bool) if on_device else mout.view(bool)
+        return out, mout
+
     # ------------------------------------------------------------------ rotational alignment (average.py:920-960)
     def _so3_setup(self):
         if not getattr(self, '_so3_ready', False):

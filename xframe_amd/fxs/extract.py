@@ -350,7 +350,108 @@ def _pair_name(flat, nq):
     return '(q1, q2) = (%d, %d)' % (flat // nq, flat % nq)
 
 
-def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
+_CONDITIONING_KEYS = ('low_pass_order_in_q', 'enforce_max_order', 'enforce_zero_odd_harmonics', 'apply_binned_mean')
+_RANK_DEFICIENT = ('raise', 'minimum_norm')
+
+
+def _is_off(value):
+    return isinstance(value, (bool, np.bool_)) and not value
+
+
+def binned_mean_tables(phis, max_order):
+    """the host tables of ``Engine.cc_binned_mean`` in the reference's own expressions (binned_mean, fxs_invariant_tools.py:310-323):
+    returns (bin_start (n_bins + 1) int32: the runs of the rolled bin ids that numpy.add.reduceat sums, n_roll, new_phis (330)).
+    Raises ValueError where the runs are not the bins 0 .. n_bins - 1 in order -- a grid that leaves a bin without a sample (reduceat
+    then returns fewer bins than new_phis has entries) or that is not sorted."""
+    phis = np.asarray(phis, dtype=float)
+    max_order = int(max_order)
+    if max_order < 1:
+        raise ValueError('apply_binned_mean needs max_order >= 1 (step pi / max_order, fxs_invariant_tools.py:310)')
+    step_size = np.pi / max_order                                                                        # 310
+    n_bins = 2 * max_order
+    ids = (phis + step_size / 2) // step_size                                                            # 312: numpy's floor division
+    n_roll = int(np.sum(ids == n_bins))
+    ids[ids == n_bins] = 0
+    idr = np.roll(ids, n_roll)                                                                           # 319
+    split_ids = np.where(np.roll(idr, 1) != idr)[0]                                                      # 323
+    if len(split_ids) != n_bins or not np.array_equal(idr[split_ids], np.arange(n_bins)):
+        raise ValueError('apply_binned_mean: the %d angles do not put a sample into every one of the 2 max_order = %d bins in '
+                         'rising order (%d runs of bin ids; fxs_invariant_tools.py:323-324 would return that many bins for %d new '
+                         'angles)' % (len(phis), n_bins, len(split_ids), n_bins))
+    bin_start = np.concatenate([split_ids, [len(phis)]]).astype(np.int32)
+    return bin_start, n_roll, np.arange(n_bins) * 2 * np.pi / n_bins                                     # 330
+
+
+def lowpass_sos(value, nq):
+    """the second-order section of low_pass_order_in_q (fxs_invariant_tools.py:250): scipy.signal.butter(1, value, 'lp', fs=Nq,
+    output='sos'); a cutoff outside (0, Nq / 2) raises ValueError, as scipy does"""
+    if isinstance(value, (bool, np.bool_)) or not np.isscalar(value) or not np.isfinite(value) or not 0 < value < nq / 2:
+        raise ValueError('low_pass_order_in_q = %r: scipy.signal.butter(1, value, \'lp\', fs=%d) needs 0 < value < fs / 2 = %g'
+                         % (value, nq, nq / 2))
+    from scipy.signal import butter
+    sos = np.asarray(butter(1, value, 'lp', fs=nq, output='sos'), dtype=float)
+    assert sos.shape == (1, 6) and sos[0, 3] == 1.0, sos
+    return sos
+
+
+def modify_masked_cross_correlation(engine, cc, cc_mask, phis, max_order, average_intensity=False, **modify_cc):
+    """modify_cross_correlation (fxs_invariant_tools.py:235-289) with a mask, every stage on the device, in the reference's order:
+    subtract_average_intensity, low_pass_order_in_q (``Engine.cc_lowpass_q``), enforce_max_order / enforce_zero_odd_harmonics
+    (``Engine.cc_harmonic_filter``), pi_periodicity, q1q2_symmetric, apply_binned_mean (``Engine.cc_binned_mean``),
+    interpolate_masked.  The first stage that runs subtracts the average intensity.  With none of low_pass_order_in_q,
+    enforce_max_order, enforce_zero_odd_harmonics, apply_binned_mean it is ONE ``Engine.cc_prepare_masked`` call.  Returns
+    (cc', mask', phis'): after a binned mean the 2 max_order new angles, which the interpolation already uses.  Raises ValueError
+    for a cutoff outside (0, Nq / 2), for a grid that leaves a bin without an angle, and where scipy's interp1d would raise."""
+    mod = modify_cc
+    phis = np.asarray(phis, dtype=float)
+    nq, n_delta = int(cc.shape[0]), int(cc.shape[-1])
+    max_order = int(max_order)
+    avg = average_intensity
+    avg = np.asarray(getattr(avg, 'data', avg))
+    kw = {}
+    if mod.get('subtract_average_intensity', False) and avg.ndim == 1:                                    # 245
+        kw['average_intensity'] = avg
+    if mod.get('pi_periodicity', False):
+        assert n_delta % 2 == 0, 'for odd number of phi symmetry enforcing is not possible since phi+pi is not an existing grid point.'
+        assert n_delta == len(phis), 'Cross correlation has {} angular datapoints but only {} angle values are given.'.format(n_delta, len(phis))
+        kw['bad_angles'] = (phis < np.pi / 2) | (phis >= 3 * np.pi / 2)                                  # 267
+    interpolate = bool(mod.get('interpolate_masked', False))
+    symmetric = bool(mod.get('q1q2_symmetric', False))
+    low_pass = mod.get('low_pass_order_in_q', False)
+    sos = None if isinstance(low_pass, (bool, np.bool_)) else lowpass_sos(low_pass, nq)                  # 248: anything but a bool
+    cut_orders, zero_odd = bool(mod.get('enforce_max_order', False)), bool(mod.get('enforce_zero_odd_harmonics', False))
+    binned = bool(mod.get('apply_binned_mean', False))
+    if binned:
+        assert n_delta == len(phis), 'Cross correlation has {} angular datapoints but only {} angle values are given.'.format(n_delta, len(phis))
+        bin_start, n_roll, new_phis = binned_mean_tables(phis, max_order)
+    # the first stage that runs subtracts the average intensity (245-247); every stage up to the bins works on the old angles
+    pending = {'average_intensity': kw.pop('average_intensity')} if 'average_intensity' in kw else {}
+    if sos is not None:
+        cc = engine.cc_lowpass_q(cc, sos, **pending)
+        pending = {}
+    if cut_orders or zero_odd:
+        cc = engine.cc_harmonic_filter(cc, max_order=max_order if cut_orders else None, zero_odd=zero_odd, **pending)
+        pending = {}
+    if binned:
+        if symmetric or 'bad_angles' in kw:
+            cc, cc_mask, _ = engine.cc_prepare_masked(cc, cc_mask, q1q2_symmetric=symmetric, **pending, **kw)
+            pending = {}
+        cc2, mask2 = engine.cc_binned_mean(cc, cc_mask, bin_start, n_roll, **pending)
+        phis = new_phis
+        status = (0, 0)
+        if interpolate:
+            cc2, mask2, status = engine.cc_prepare_masked(cc2, mask2, interpolate_phis=phis)
+    else:
+        if interpolate:
+            kw['interpolate_phis'] = phis
+        cc2, mask2, status = engine.cc_prepare_masked(cc, cc_mask, q1q2_symmetric=symmetric, **pending, **kw)
+    if status[0]:
+        raise ValueError('interpolate_masked: %d rows have a masked sample outside the range of their valid ones, the first at %s; scipy\'s '
+                         'interp1d raises there (fxs_invariant_tools.py:348) and nothing is extrapolated' % (status[0], _pair_name(status[1], nq)))
+    return cc2, mask2, phis
+
+
+def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, rank_deficient='raise', **metadata):
     """fxs_invariant_tools.py:374-422 for data with a cc_mask, for mode 'lstsq' and for modify_cc.interpolate_masked, three dimensions,
     arithmetic on the device.  metadata as for ``cross_correlation_to_deg2_invariant``; modes: 'back_substitution' (578-645: the masked
     samples are interpolated first, 605-608; qq_mask = mask'.all(-1)) and 'lstsq' (452-517: a fit over the unmasked samples of every
@@ -362,15 +463,25 @@ def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
     are fine.  Nothing is extrapolated.
     Raises NotImplementedError for rank-deficient least-squares problems (0 < n_valid < number of orders, or a reciprocal condition
     estimate min |r_kk| / max |r_kk| of the triangle below 1e-12): LAPACK's gelsd returns the truncated minimum-norm solution there,
-    which this route does not build."""
+    which this route builds as an opt-in: rank_deficient='minimum_norm' (``Engine.cc_lstsq_deg2_minnorm``; the flow reads
+    settings['GPU']['lstsq_minimum_norm']) solves those pairs as numpy.linalg.lstsq(..., rcond=None) does and leaves the bits of
+    every other pair alone.
+
+    modify_cc runs in the reference's order (235-289): subtract_average_intensity, low_pass_order_in_q (``Engine.cc_lowpass_q``),
+    enforce_max_order / enforce_zero_odd_harmonics (``Engine.cc_harmonic_filter``), pi_periodicity, q1q2_symmetric,
+    apply_binned_mean (``Engine.cc_binned_mean``), interpolate_masked.  With none of the four conditioning keys it is the one
+    ``Engine.cc_prepare_masked`` call.  After a binned mean the interpolation, the fit and data_grid['phis'] use the 2 max_order
+    new angles, as upstream (395)."""
+    if rank_deficient not in _RANK_DEFICIENT:
+        raise ValueError('rank_deficient %r: one of %s' % (rank_deficient, ', '.join(_RANK_DEFICIENT)))
     if dim == 2:
         raise NotImplementedError('masked cross-correlation data with dimensions = 2 (fxs_invariant_tools.py:813-839 drops masked pairs)')
     if dim != 3:
         raise ValueError('dim must be 2 or 3')
     mod = dict(metadata.get('modify_cc') or {})
-    built = _BUILT_MODIFY_CC + ('interpolate_masked',)
+    built = _BUILT_MODIFY_CC + ('interpolate_masked',) + _CONDITIONING_KEYS
     for key, value in mod.items():
-        if key not in built and not (isinstance(value, (bool, np.bool_)) and not value):
+        if key not in built and not _is_off(value):
             raise NotImplementedError('modify_cc.%s (fxs_invariant_tools.py:235-289): built are %s' % (key, ', '.join(built)))
     mode = metadata.get('mode', False)
     if mode not in _MASKED_MODES:
@@ -388,22 +499,12 @@ def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
     cc_mask = np.asarray(cross_correlation_mask(data_grid, metadata), dtype=bool)
     if cc_mask.shape != tuple(cc.shape):
         raise ValueError('cc_mask has shape %r, the cross-correlation %r' % (cc_mask.shape, tuple(cc.shape)))
-    avg = metadata.get('average_intensity', False)
-    avg = np.asarray(getattr(avg, 'data', avg))
-    kw = {}
-    if mod.get('subtract_average_intensity', False) and avg.ndim == 1:                                    # 245
-        kw['average_intensity'] = avg
-    if mod.get('pi_periodicity', False):
-        assert n_delta % 2 == 0, 'for odd number of phi symmetry enforcing is not possible since phi+pi is not an existing grid point.'
-        assert n_delta == len(phis), 'Cross correlation has {} angular datapoints but only {} angle values are given.'.format(n_delta, len(phis))
-        kw['bad_angles'] = (phis < np.pi / 2) | (phis >= 3 * np.pi / 2)                                  # 267
     # interpolation: the setting, or implied by back_substitution (605-608; a no-op on a mask that is all true)
-    if mod.get('interpolate_masked', False) or mode == 'back_substitution':
-        kw['interpolate_phis'] = phis
-    cc2, mask2, status = engine.cc_prepare_masked(cc, cc_mask, q1q2_symmetric=bool(mod.get('q1q2_symmetric', False)), **kw)
-    if status[0]:
-        raise ValueError('interpolate_masked: %d rows have a masked sample outside the range of their valid ones, the first at %s; scipy\'s '
-                         'interp1d raises there (fxs_invariant_tools.py:348) and nothing is extrapolated' % (status[0], _pair_name(status[1], nq)))
+    mod['interpolate_masked'] = bool(mod.get('interpolate_masked', False)) or mode == 'back_substitution'
+    cc2, mask2, phis = modify_masked_cross_correlation(engine, cc, cc_mask, phis, max_order,
+                                                       average_intensity=metadata.get('average_intensity', False), **mod)
+    if mod.get('apply_binned_mean', False):
+        data_grid['phis'] = phis                                                                         # 395
     stride = 2 if metadata['assume_zero_odd_orders'] else 1
     if mode == 'back_substitution':
         leg = legendre_table(qs, metadata['xray_wavelength'], max_order, stride)
@@ -413,14 +514,18 @@ def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
     thetas = np.arccos(qs * metadata['xray_wavelength'] / (4 * np.pi))                                   # 471, physicsLibrary.py:94-95
     if not np.isfinite(thetas).all():
         raise ValueError('q * wavelength / (4 pi) > 1: the radial points do not lie on the Ewald sphere of this wavelength')
-    b, n_valid, rcond = engine.cc_lstsq_deg2(cc2, mask2, extracted, thetas, phis)
+    if rank_deficient == 'minimum_norm':
+        b, n_valid, rcond, _ = engine.cc_lstsq_deg2_minnorm(cc2, mask2, extracted, thetas, phis)
+    else:
+        b, n_valid, rcond = engine.cc_lstsq_deg2(cc2, mask2, extracted, thetas, phis)
     b, n_valid, rcond = np.asarray(b), np.asarray(n_valid), np.asarray(rcond)
     deficient = (n_valid > 0) & ((n_valid < len(extracted)) | (rcond < _LSTSQ_RCOND_MIN))
-    if deficient.any():
+    if deficient.any() and rank_deficient == 'raise':
         first = int(np.flatnonzero(deficient)[0])
         raise NotImplementedError('lstsq: %d of %d pairs are rank deficient (fewer valid samples than the %d orders, or a reciprocal '
                                   'condition estimate below %g), the first at %s with %d valid samples, estimate %.1e; LAPACK returns the '
-                                  'truncated minimum-norm solution there (fxs_invariant_tools.py:513), which is not built'
+                                  'truncated minimum-norm solution there (fxs_invariant_tools.py:513), which is opt-in: '
+                                  "rank_deficient='minimum_norm', or settings['GPU']['lstsq_minimum_norm'] = True in the flow"
                                   % (int(deficient.sum()), deficient.size, len(extracted), _LSTSQ_RCOND_MIN, _pair_name(first, nq),
                                      int(n_valid.flat[first]), float(rcond.flat[first])))
     if b.shape[0] < max_order + 1:                                                                       # (odd max_order at stride 2)
@@ -430,8 +535,9 @@ def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
 
 def _wants_masked_route(dopt):
     mask_type = (dopt.get('cc_mask') or {'type': 'none'}).get('type', 'none')
-    return (mask_type != 'none' or dopt.get('bl_extraction_method') == 'lstsq'
-            or bool((dopt.get('modify_cc') or {}).get('interpolate_masked', False)))
+    mod = dopt.get('modify_cc') or {}
+    return (mask_type != 'none' or dopt.get('bl_extraction_method') == 'lstsq' or bool(mod.get('interpolate_masked', False))
+            or any(not _is_off(mod.get(key, False)) for key in _CONDITIONING_KEYS))
 
 
 def calc_deg_2_invariant_line_mask(radial_points, max_order, line_specifier, invert=False):
@@ -545,7 +651,9 @@ def extract_from_cross_correlation(engine, ccd, settings):
     meta = {**{k: v for k, v in ccd.items() if k != 'cross_correlation'}, **dopt, 'orders': np.arange(max_order + 1),
             'mode': dopt['bl_extraction_method'], 'average_intensity': avg}                              # 134
     if _wants_masked_route(dopt):
-        b_coeff, q_mask = masked_cross_correlation_to_deg2_invariant(engine, cc_arrays['I1I1'], dim, **meta)
+        minimum_norm = bool((opt.get('GPU') or {}).get('lstsq_minimum_norm', False))
+        b_coeff, q_mask = masked_cross_correlation_to_deg2_invariant(engine, cc_arrays['I1I1'], dim,
+                                                                     rank_deficient='minimum_norm' if minimum_norm else 'raise', **meta)
     else:
         b_coeff, q_mask = cross_correlation_to_deg2_invariant(engine, cc_arrays['I1I1'], dim, **meta)
     mask, q_id_limits = calc_deg_2_invariant_masks(dopt, b_coeff.shape, q_mask, qs, max_order)
