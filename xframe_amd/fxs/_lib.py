@@ -246,6 +246,20 @@ def as_u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
+def ft_stab_flag(engine, ft_stab):
+    """the `ft_stab` of an engine's `run` (a bool, or a bool per restart) as the flag of the C call: restarts that disagree go to the
+    context as a mask (`engine.set_ft_stab_mask`) under the flag True; a mask left from an earlier run is cleared"""
+    if isinstance(ft_stab, np.ndarray):
+        flags = np.asarray(ft_stab, dtype=bool).reshape(engine.B)
+        if flags.any() and not flags.all():
+            engine.set_ft_stab_mask(flags)
+            return True
+        ft_stab = bool(flags.all())
+    if getattr(engine, '_ft_mask_set', False):
+        engine.set_ft_stab_mask(None)                                # a plain flag again: every restart
+    return ft_stab
+
+
 class TensorOperands:
     """What the engines share for operators that work in place on torch tensors (the averaging keeps its batch in HBM and hands
     ``tensor.data_ptr()`` across the ABI).  Needs ``self.lib`` and ``self.device_index``.

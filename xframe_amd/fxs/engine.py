@@ -869,17 +869,7 @@ class Engine(_lib.TensorOperands):
         enforce decision per reconstruction process: restarts of a batch may disagree)"""
         betas = _lib.as_f64(np.atleast_1d(betas))
         n = len(betas)
-        mixed = None
-        if isinstance(ft_stab, np.ndarray):
-            flags = np.asarray(ft_stab, dtype=bool).reshape(self.B)
-            if flags.all() or not flags.any():
-                ft_stab = bool(flags.all())
-            else:
-                mixed, ft_stab = flags, True
-        if mixed is not None:
-            self.set_ft_stab_mask(mixed)
-        elif getattr(self, '_ft_mask_set', False):
-            self.set_ft_stab_mask(None)                              # a plain flag again: every restart
+        ft_stab = _lib.ft_stab_flag(self, ft_stab)
         if self.group is not None:
             # side by side with other engines of this GPU: the group enqueues everybody's steps in turn order (EngineGroup); a
             # per-restart ft_stab mask is state of this engine's context, the call itself says ft_stab = 1

@@ -284,17 +284,7 @@ class Engine2D(_lib.TensorOperands):
         real errors (n, B) of these steps come back, else nothing crosses the host"""
         betas = _lib.as_f64(np.atleast_1d(betas))
         n = len(betas)
-        mixed = None
-        if isinstance(ft_stab, np.ndarray):
-            flags = np.asarray(ft_stab, dtype=bool).reshape(self.B)
-            if flags.all() or not flags.any():
-                ft_stab = bool(flags.all())
-            else:
-                mixed, ft_stab = flags, True
-        if mixed is not None:
-            self.set_ft_stab_mask(mixed)
-        elif getattr(self, '_ft_mask_set', False):
-            self.set_ft_stab_mask(None)
+        ft_stab = _lib.ft_stab_flag(self, ft_stab)
         mid = self.METHOD_ID[method]
         if not fetch:
             self._ck(self.lib.mtip2d_run_async(self.ctx, mid, int(bool(ft_stab)), n, _lib.ptr(betas)))

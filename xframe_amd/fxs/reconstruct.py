@@ -11,7 +11,7 @@ Same call shape as the reference::
 What differs by design: the reference forks one OS process per restart and round-trips every Hankel
 transform through a GPU daemon (reconstruct.py:141-157, Multiprocessing.py:1033-1117); here all restarts of a
 rank are one batch resident on one GPU and the whole loop runs on the device; the Python side only walks the
-schedule (sub-loops, SW steps, ramps) and collects results.  Restarts are sharded over ranks / GPUs by
+schedule (sub-loops, SW steps, ramps: ``schedule.walk``, shared with the 2-D loops) and collects results.  Restarts are sharded over ranks / GPUs by
 ``parallel.shard_restarts``; there is no collective on the data path.
 """
 import time
@@ -19,9 +19,42 @@ import time
 import numpy as np
 
 from . import hostsetup as hs
+from . import schedule
 from .engine import Engine
 from .operators import RecipeFactory, build_operators
 from .settings import DictNamespace, resolve
+
+
+class _EngineState:
+    """what `schedule.walk` drives in the 3-D loop: the resident `Engine`, whose state is all on the device.  Every call looks its
+    method up on the engine when it is made (tests shadow them on the instance)."""
+
+    def __init__(self, engine):
+        self.e = engine
+
+    def check_method(self, key):
+        pass                                                # an unknown key is METHOD_ID's KeyError at its run
+
+    def begin_sub_loop(self):
+        self.e.begin_sub_loop()
+
+    def shrinkwrap(self, sigma, threshold, limit):
+        return self.e.shrinkwrap(sigma, threshold, limit)
+
+    def before_sw_center(self, limit):
+        return None                                         # the first support update's decision is the one (no read, no raise)
+
+    def refresh_reciprocal_density(self):
+        self.e.refresh_reciprocal_density()
+
+    def run(self, key, ft_stab, betas):
+        self.e.run(key, ft_stab, betas, fetch=False)
+
+    def main_errors(self, first, n):
+        return self.e.fetch_main_errors(first, n)
+
+    def select_best(self, where):
+        self.e.select_best(where)
 
 
 class MTIP:
@@ -102,35 +135,6 @@ class MTIP:
         self.process_factory.addOperators(build_operators(self.engine))
         self.phasing_loop = self._main_loop
 
-    # ------------------------------------------------------------------ ramps (reference 1212-1258)
-    def _sw_ramps(self):
-        e = self.engine
-        sw_opt = self.opt['projections']['real']['shrink_wrap']
-        if sw_opt.get('mode', 'threshold') != 'threshold':
-            raise NotImplementedError("shrink_wrap.mode = %r: only 'threshold' is on the accelerated path "
-                                      '(fixed_volume: fxs_Projections.py:260-291)' % (sw_opt.get('mode'),))
-        order = self.opt['main_loop']['sub_loops']['order']
-        sig, thr = [], []
-        for lid in range(len(order)):
-            s = sw_opt['sigmas'][lid] if len(sw_opt['sigmas']) - 1 >= lid else False
-            s = s if isinstance(s, (list, tuple)) else [s]
-            sig.append(hs.LinearRamp(*s, default_start=e.default_sigma, default_stop=e.default_sigma))
-            t = sw_opt['thresholds'][lid] if len(sw_opt['thresholds']) - 1 >= lid else 0.1
-            t = t if isinstance(t, (list, tuple)) else [t]
-            thr.append(hs.LinearRamp(*t))
-        return sig, thr
-
-    def _update_shrink_wrap(self, iteration, loop_number):
-        r = self._sig_ramps[loop_number]
-        if not r.undefined:
-            v = r(iteration)
-            ok = np.issubdtype(np.array(v).dtype, np.number) and not isinstance(v, bool) and v > 0
-            self.sw_sigma = v if ok else self.engine.default_sigma           # fxs_Projections.py:233-243
-        t = self._thr_ramps[loop_number]
-        if not t.undefined:
-            v = t(iteration)
-            self.sw_threshold = 0 if v < 0 else (1 if v >= 1 else v)          # 218-227
-
     # ------------------------------------------------------------------ initial densities (1115-1174, 957-979)
     def _initial_densities(self):
         """guesses of all restarts of this batch; the seed-independent autocorrelation is transformed once"""
@@ -167,24 +171,6 @@ class MTIP:
         return hs.bump_density(e.rs, e.shape, radius, dg['bump']['slope'], dg['random']['SNR'], rng,
                                e.rsetup.integrated_intensity, e.int_wr, e.int_wt)
 
-    @staticmethod
-    def _change_to_ft_stab(popt, name, eis_list):
-        """reconstruct.py:836-850: the reference decides per reconstruction process -- a bool when the restarts agree, else one per restart."""
-        if name[-8:] == '_ft_stab' or 'ft_stab' not in popt:
-            return False
-        v = popt['ft_stab']
-        if isinstance(v, bool):
-            return v
-        if v == 'link_to_enforce_initial_support':
-            delay = max(int(popt['link_to_enforce_initial_support']['delay']), 1)
-            if len(eis_list) >= delay:
-                recent = np.array(eis_list[-delay:])            # (delay, B)
-                flags = ~(recent == True).any(axis=0)          # noqa: E712
-                if flags.all() != flags.any():
-                    return flags                                # the restarts disagree: a flag per restart (Engine.run takes it)
-                return bool(flags.all())
-        return False
-
     # ------------------------------------------------------------------ the loop (854-951, 1023-1035)
     def _main_loop(self, *args, **kwargs):
         e = self.engine
@@ -199,78 +185,14 @@ class MTIP:
         e.init_state()
         initial_density = [e.density(b) for b in range(B)]
         initial_mask = e.initial_support.copy()
-        self._sig_ramps, self._thr_ramps = self._sw_ramps()
-        self.sw_sigma, self.sw_threshold = e.default_sigma, 0.06
-        hio_opt = opt['projections']['real']['HIO']
-        eis_opt = opt['projections']['real']['projections']['support']['enforce_initial_support']
-        limit = eis_opt['if_error_bigger_than'] if eis_opt['apply'] else np.inf
-        loops = opt['main_loop']['sub_loops']
-        eis_list = []
-        iterations = []
+        sw_opt = opt['projections']['real']['shrink_wrap']
+        if sw_opt.get('mode', 'threshold') != 'threshold':
+            raise NotImplementedError("shrink_wrap.mode = %r: only 'threshold' is on the accelerated path "
+                                      '(fixed_volume: fxs_Projections.py:260-291)' % (sw_opt.get('mode'),))
+        ramps = schedule.ShrinkWrapRamps(opt, e.default_sigma)
         e.synchronize()
         t0 = time.perf_counter()
-        n_steps = 0
-        # best_error / best_iteration per restart (reconstruct.py:934-938), only followed on the host when some loop
-        # reselects the best density at its end (945-949)
-        track_best = any(np.isfinite(loops[name].get('best_density_not_in_first_n_iterations', np.inf))
-                         for name in loops['order'])
-        best_err_h = np.full(B, np.inf)
-        best_iter_h = np.zeros(B, int)
-        for loop_number, loop_name in enumerate(loops['order']):
-            lo = loops[loop_name]
-            e.begin_sub_loop()
-            loop_first_step = n_steps
-            step_iteration = []
-            methods = {}
-            for key in lo['order']:
-                mo = lo['methods'][key]
-                methods[key] = ({'iterations': mo.get('iterations', 0), 'options': mo} if isinstance(mo, dict)
-                                else {'iterations': mo, 'options': {}})
-            beta_cfg = hio_opt['beta'][loop_number] if len(hio_opt['beta']) - 1 >= loop_number else [0.5, 0.5, -1 / 700, 1600]
-            ramp = hs.ExponentialRamp(*beta_cfg)
-            if 'SW' in methods:
-                self._update_shrink_wrap(0, loop_number)
-            step = 0
-            sw_step = 0
-            iteration = 0
-            for iteration in range(1, lo['iterations'] + 1):
-                for key in lo['order']:
-                    if key == 'SW':
-                        enforced = e.shrinkwrap(self.sw_sigma, self.sw_threshold, limit)
-                        eis_list.append(enforced)
-                        sw_step += 1
-                        self._update_shrink_wrap(sw_step, loop_number)
-                        continue
-                    if key == 'SW_center':
-                        # reconstruct.py:886-897: one enforce decision, then `iterations` support updates, each replacing
-                        # the last pair (the sketch, 606-613, shifts nothing and hands its outputs back in swapped order)
-                        for i in range(methods[key]['iterations']):
-                            enforced = e.shrinkwrap(self.sw_sigma, self.sw_threshold, limit)
-                            if i == 0:
-                                eis_list.append(enforced)
-                            e.refresh_reciprocal_density()
-                            sw_step += 1
-                            self._update_shrink_wrap(sw_step, loop_number)
-                        continue
-                    repeats = methods[key]['iterations']
-                    ft_stab = self._change_to_ft_stab(methods[key]['options'], key, eis_list)
-                    betas = np.array([ramp.eval(step + i) for i in range(repeats)], dtype=float)
-                    e.run(key, ft_stab, betas, fetch=False)
-                    step += repeats
-                    n_steps += repeats
-                    step_iteration += [iteration] * repeats
-            if track_best and n_steps > loop_first_step:
-                errs = e.fetch_main_errors(loop_first_step, n_steps - loop_first_step)
-                for i, it in enumerate(step_iteration):
-                    better = best_err_h > errs[i]
-                    best_err_h = np.where(better, errs[i], best_err_h)
-                    best_iter_h = np.where(better, it, best_iter_h)
-            n_first = lo.get('best_density_not_in_first_n_iterations', np.inf)
-            if np.isfinite(n_first):
-                reselect = best_iter_h > n_first
-                if reselect.any():
-                    e.select_best(reselect)
-            iterations.append(iteration)
+        iterations, n_steps = schedule.walk(opt, _EngineState(e), ramps, B)
         e.synchronize()
         t1 = time.perf_counter()
         out = self._generate_output(iterations, initial_density, initial_mask, n_steps)

@@ -16,10 +16,16 @@ the reference's own functions).  Not built for 2-D: the other reciprocal metrics
 
 With `resident=True` (the worker's `GPU.resident_2d`, default off) the same sub-loops run on the resident engine instead
 (`Engine2D.run` = `mtip2d_run`: the batch stays in HBM, a step is five fused kernels, consecutive steps of one method are one call,
-errors / metrics / best tracking on the device): `_loop_resident`, after the 3-D host loop; the result dicts are the same."""
+errors / metrics / best tracking on the device); the result dicts are the same.
+
+Both flavours are walked by `schedule.walk`, the one mirror of the sub-loop state machine (the 3-D loop's too): `_loop_operators` and
+`_loop_resident` are set-up, the walk on a state, and the hand-over to `_generate_output`.  `_OperatorState` is the loop state upstream
+keeps per process, for the batch and on the host (history, stale history, non-FXS intensity, support, best pair, error lists);
+`_ResidentState` forwards to the engine that holds all of that in HBM."""
 import numpy as np
 
 from . import hostsetup as hs
+from . import schedule
 from .polar2d import Engine2D
 from .settings import reciprocity_coefficient, resolve
 
@@ -121,6 +127,124 @@ class ReciprocalSetup2D:
         self.radial_high_pass = so.get('radial_high_pass', 0.2)
         # generate_approximate_unknowns, 744-750: the unknown of the strongest even order is 1 in every step
         self.so_position = int(so_order_ranking(proj, keys, self.qs, self.radial_high_pass)[0][0]) if self.use_SO_freedom else None
+
+
+class _State2D:
+    """what the two 2-D states of `schedule.walk` share: the keys they refuse, and the enforce decision `SW_center` starts from.
+    Both reach the engine and `MTIP2D._step` through `self.e` / `self.m` when the call is made (tests shadow them on the instance)."""
+
+    def check_method(self, key):
+        if key not in ('HIO', 'ER', 'SW', 'SW_center', 'HIO_non_FXS', 'ER_non_FXS'):
+            raise NotImplementedError('2-D loop method %r' % (key,))
+        if key.endswith('_non_FXS') and self.m.reciprocal_metrics:
+            # (upstream the *_non_FXS start sketch hands the reciprocal metrics a grid instead of I_m and raises)
+            raise NotImplementedError('2-D %s with reciprocal metrics enabled: the reference raises' % key)
+
+    def before_sw_center(self, limit):
+        if not self.n_steps:
+            raise IndexError("SW_center before any phasing step: error_dict['main'][-1] of an empty list (reconstruct.py:887)")
+        return self.main_errors(self.n_steps - 1, 1)[0] > limit
+
+
+class _ResidentState(_State2D):
+    """the resident engine (`Engine2D.run`): the state is the device's"""
+
+    def __init__(self, m, ragged):
+        self.m, self.e, self.ragged = m, m.engine, ragged
+        self.n_steps = self.fxs_steps = 0                             # fxs_steps: whether there are unknowns to fetch
+
+    def begin_sub_loop(self):
+        self.e.begin_sub_loop()                                       # stale = hist, latest_intensity = None (reconstruct.py:859, 866)
+
+    def shrinkwrap(self, sigma, threshold, limit):
+        return self.e.shrinkwrap_state(sigma, threshold, limit)
+
+    def refresh_reciprocal_density(self):
+        self.e.refresh_reciprocal_density()
+
+    def run(self, key, ft_stab, betas):
+        if self.ragged and len(betas):
+            raise ValueError('main error over metrics of different shapes (inhomogeneous array upstream, fxs_IO_methods.py:758)')
+        self.e.run(key, ft_stab, betas, fetch=False)                  # (a block of no steps still takes / drops the non-FXS intensity)
+        self.n_steps += len(betas)
+        if not key.endswith('_non_FXS'):
+            self.fxs_steps += len(betas)
+
+    def main_errors(self, first, n):
+        return self.e.fetch_main_errors(first, n)
+
+    def select_best(self, where):
+        self.e.select_best(where)
+
+
+class _OperatorState(_State2D):
+    """the loop state of reconstruct.py:854-951 for the batch, on the host; a step is one `MTIP2D._step`"""
+
+    def __init__(self, m, F0, rho0):
+        self.m = m
+        hl = m.opt['main_loop'].get('history_length', 3)
+        self.hist = [(F0.copy(), rho0.copy())] * hl                   # per entry: (F (B, ...), rho (B, ...))
+        # reconstruct.py:859: `hist` is a local that is re-read from the state only at the top of every phasing step (913); SW_center
+        # (893) and the *_non_FXS intensity (901) read it as it was left there -- the history BEFORE the most recent step
+        self.stale, self.latest_intensity = self.hist, None
+        self.init_sup = np.broadcast_to(m.initial_support, (m.B,) + m.shape).copy()
+        self.support = self.init_sup.copy()                           # effective support (what RealProjection's mask holds)
+        self.best = {'pair': (F0.copy(), rho0.copy()), 'err': np.full(m.B, np.inf), 'mask': self.init_sup.copy()}
+        self.err_real, self.err_main, self.unknowns = [], [], None
+        self.err_recip = {n: [] for n in m.reciprocal_metrics}
+
+    n_steps = property(lambda self: len(self.err_main))
+
+    def begin_sub_loop(self):
+        self.stale, self.latest_intensity = self.hist, None
+
+    def shrinkwrap(self, sigma, threshold, limit):
+        new_sup = self.m.engine.shrinkwrap(self.hist[-1][1], sigma, threshold)
+        # (`error_dict['main'][-1:] > limit` of an empty list is empty: falsy)
+        enforce = np.asarray(self.err_main[-1]) > limit if self.err_main else np.zeros(self.m.B, bool)
+        self.support = np.where(enforce[:, None, None], new_sup & self.init_sup, new_sup)      # support setter, fxs_Projections.py:53-58
+        return enforce
+
+    def refresh_reciprocal_density(self):
+        # reconstruct.py:606-613: the sketch shifts nothing and hands its outputs back in swapped order -- the pair appended to the
+        # (stale) history is (rho, FT(rho))
+        rho = self.hist[-1][1]
+        self.hist = self.stale[1:] + [(rho.copy(), self.m.engine.fourier_transform(rho))]
+
+    def run(self, key, ft_stab, betas):
+        m, best = self.m, self.best
+        if not key.endswith('_non_FXS'):
+            self.latest_intensity = None
+        elif self.latest_intensity is None:
+            self.latest_intensity = np.abs(self.stale[-1][0])         # |F| of the stale pair, used as the intensity (899-902)
+        want = bool(m.reciprocal_metrics)
+        for beta in betas:
+            self.stale = self.hist
+            res = m._step(key, ft_stab, beta, self.hist[-1][1], self.support, self.latest_intensity, want)
+            F_new, rho_new, err, unk = res[:4]
+            if unk is not None:
+                self.unknowns = unk
+            self.hist = self.hist[1:] + [(F_new, rho_new)]
+            self.err_real.append(err)
+            recip = m._reciprocal_errors(res[4], F_new, res[5]) if want else {}
+            for n_, v_ in recip.items():
+                self.err_recip[n_].append(v_)
+            main_err = m._main_error(err, recip)
+            self.err_main.append(main_err)
+            better = best['err'] > main_err
+            if better.any():
+                sel = better[:, None, None]
+                best['pair'] = (np.where(sel, F_new, best['pair'][0]), np.where(sel, rho_new, best['pair'][1]))
+                best['mask'] = np.where(sel, self.support, best['mask'])
+                best['err'] = np.where(better, main_err, best['err'])
+
+    def main_errors(self, first, n):
+        return np.array(self.err_main[first:first + n])
+
+    def select_best(self, where):                                     # 945-949
+        sel, (F, rho) = where[:, None, None], self.hist[-1]
+        self.hist = self.hist[1:] + [(np.where(sel, self.best['pair'][0], F), np.where(sel, self.best['pair'][1], rho))]
+        self.support = np.where(sel, self.best['mask'], self.support)
 
 
 class MTIP2D:
@@ -291,45 +415,6 @@ class MTIP2D:
             phases[b] = np.exp(1j * (q * np.cos(pq) * rad * np.cos(phi_c) + q * np.sin(pq) * rad * np.sin(phi_c)))
         return F * phases, e.fourier_transform(ft * phases, True), centers
 
-    def _sw_ramps(self):
-        sw_opt = self.opt['projections']['real']['shrink_wrap']
-        order = self.opt['main_loop']['sub_loops']['order']
-        sig, thr = [], []
-        for lid in range(len(order)):
-            s = sw_opt['sigmas'][lid] if len(sw_opt['sigmas']) - 1 >= lid else False
-            sig.append(hs.LinearRamp(*(s if isinstance(s, (list, tuple)) else [s]), default_start=self.default_sigma, default_stop=self.default_sigma))
-            t = sw_opt['thresholds'][lid] if len(sw_opt['thresholds']) - 1 >= lid else 0.1
-            thr.append(hs.LinearRamp(*(t if isinstance(t, (list, tuple)) else [t])))
-        return sig, thr
-
-    def _update_shrink_wrap(self, iteration, loop_number):
-        r = self._sig_ramps[loop_number]
-        if not r.undefined:
-            v = r(iteration)
-            ok = np.issubdtype(np.array(v).dtype, np.number) and not isinstance(v, bool) and v > 0
-            self.sw_sigma = v if ok else self.default_sigma             # fxs_Projections.py:233-243
-        t = self._thr_ramps[loop_number]
-        if not t.undefined:
-            v = t(iteration)
-            self.sw_threshold = 0 if v < 0 else (1 if v >= 1 else v)    # 218-227
-
-    @staticmethod
-    def _change_to_ft_stab(popt, name, eis_list):
-        """reconstruct.py:836-850: one decision per restart; a bool when they agree"""
-        if name[-8:] == '_ft_stab' or 'ft_stab' not in popt:
-            return False
-        v = popt['ft_stab']
-        if isinstance(v, bool):
-            return v
-        if v == 'link_to_enforce_initial_support':
-            delay = max(int(popt['link_to_enforce_initial_support']['delay']), 1)
-            if len(eis_list) >= delay:
-                flags = ~(np.array(eis_list[-delay:]) == True).any(axis=0)          # noqa: E712
-                if flags.all() != flags.any():
-                    return flags                                    # restarts of one batch disagree: per restart (see _step)
-                return bool(flags.all())
-        return False
-
     def _step(self, key, ft_stab, beta, rho, support, fixed, want):
         """Engine2D.step for the batch; when the restarts disagree on ft_stab (the reference decides per reconstruction process) the
         step runs once with and once without the add-back and every restart takes its own"""
@@ -351,114 +436,24 @@ class MTIP2D:
         """create_initial_state + the sub-loops + generate_output (reconstruct.py:957-1035) for the batch: list of result dicts"""
         return self._generate_output(*(self._loop_resident() if self.resident else self._loop_operators()))
 
+    def _walk(self, state):
+        return schedule.walk(self.opt, state, schedule.ShrinkWrapRamps(self.opt, self.default_sigma), self.B)
+
     def _loop_operators(self):
         """the sub-loops, one operator-level call per step (`Engine2D.step`), histories and best tracking on the host"""
-        e, B, opt = self.engine, self.B, self.opt
-        rho0 = np.stack([self._initial_density(b) for b in range(B)])
+        e = self.engine
+        rho0 = np.stack([self._initial_density(b) for b in range(self.B)])
         F0 = e.fourier_transform(rho0)
         rho0 = e.fourier_transform(F0, True)                          # 962-963: the state starts from IFT(FT(guess))
-        hl = opt['main_loop'].get('history_length', 3)
-        hist = [(F0.copy(), rho0.copy())] * hl                        # per entry: (F (B, ...), rho (B, ...))
-        init_sup = np.broadcast_to(self.initial_support, (B,) + self.shape).copy()
-        support = init_sup.copy()                                     # effective support (what RealProjection's mask holds)
-        best = {'pair': (F0.copy(), rho0.copy()), 'err': np.full(B, np.inf), 'iter': np.zeros(B, int), 'mask': init_sup.copy()}
-        err_real, err_main, unknowns = [], [], None
-        err_recip = {n: [] for n in self.reciprocal_metrics}
-        self._sig_ramps, self._thr_ramps = self._sw_ramps()
-        self.sw_sigma, self.sw_threshold = self.default_sigma, 0.06
-        hio_opt = opt['projections']['real']['HIO']
-        eis_opt = opt['projections']['real']['projections']['support']['enforce_initial_support']
-        limit = eis_opt['if_error_bigger_than'] if eis_opt['apply'] else np.inf
-        loops = opt['main_loop']['sub_loops']
-        eis_list, iterations = [], []
-        want = bool(self.reciprocal_metrics)
-        for loop_number, loop_name in enumerate(loops['order']):
-            lo = loops[loop_name]
-            methods = {}
-            for key in lo['order']:
-                mo = lo['methods'][key]
-                methods[key] = ({'iterations': mo.get('iterations', 0), 'options': mo} if isinstance(mo, dict) else {'iterations': mo, 'options': {}})
-                if key not in ('HIO', 'ER', 'SW', 'SW_center', 'HIO_non_FXS', 'ER_non_FXS'):
-                    raise NotImplementedError('2-D loop method %r' % (key,))
-                if key.endswith('_non_FXS') and self.reciprocal_metrics:
-                    # (upstream the *_non_FXS start sketch hands the reciprocal metrics a grid instead of I_m and raises)
-                    raise NotImplementedError('2-D %s with reciprocal metrics enabled: the reference raises' % key)
-            beta_cfg = hio_opt['beta'][loop_number] if len(hio_opt['beta']) - 1 >= loop_number else [0.5, 0.5, -1 / 700, 1600]
-            ramp = hs.ExponentialRamp(*beta_cfg)
-            if 'SW' in methods:
-                self._update_shrink_wrap(0, loop_number)
-            step = sw_step = iteration = 0
-            # reconstruct.py:859: `hist` is a local that is re-read from the state only at the top of every phasing step (913); SW_center
-            # (893) and the *_non_FXS intensity (901) read it as it was left there -- the history BEFORE the most recent step
-            stale = hist
-            latest_intensity = None
-            for iteration in range(1, lo['iterations'] + 1):
-                for key in lo['order']:
-                    if key == 'SW':                                   # 877-885
-                        new_sup = e.shrinkwrap(hist[-1][1], self.sw_sigma, self.sw_threshold)
-                        last = np.asarray(err_main[-1]) if err_main else np.full(B, np.nan)
-                        enforce = last > limit if err_main else np.zeros(B, bool)      # (`error_dict['main'][-1:] > limit` of an empty list is empty: falsy)
-                        eis_list.append(enforce)
-                        support = np.where(enforce[:, None, None], new_sup & init_sup, new_sup)    # support setter, fxs_Projections.py:53-58
-                        sw_step += 1
-                        self._update_shrink_wrap(sw_step, loop_number)
-                        continue
-                    if key == 'SW_center':
-                        # reconstruct.py:606-613, 886-897: one enforce decision, then `iterations` support updates; the sketch shifts
-                        # nothing and hands its outputs back in swapped order -- the pair appended to the (stale) history is (rho, FT(rho))
-                        if not err_main:
-                            raise IndexError("SW_center before any phasing step: error_dict['main'][-1] of an empty list (reconstruct.py:887)")
-                        enforce = np.asarray(err_main[-1]) > limit
-                        eis_list.append(enforce)
-                        for _ in range(methods[key]['iterations']):
-                            rho = hist[-1][1]
-                            new_sup = e.shrinkwrap(rho, self.sw_sigma, self.sw_threshold)
-                            support = np.where(enforce[:, None, None], new_sup & init_sup, new_sup)
-                            hist = stale[1:] + [(rho.copy(), e.fourier_transform(rho))]
-                            sw_step += 1
-                            self._update_shrink_wrap(sw_step, loop_number)
-                        continue
-                    if key.endswith('_non_FXS'):
-                        if latest_intensity is None:
-                            latest_intensity = np.abs(stale[-1][0])       # |F| of the stale pair, used as the intensity (899-902)
-                    else:
-                        latest_intensity = None
-                    ft_stab = self._change_to_ft_stab(methods[key]['options'], key, eis_list)
-                    for _ in range(methods[key]['iterations']):
-                        stale = hist
-                        res = self._step(key, ft_stab, ramp.eval(step), hist[-1][1], support, latest_intensity, want)
-                        F_new, rho_new, err, unk = res[:4]
-                        if unk is not None:
-                            unknowns = unk
-                        hist = hist[1:] + [(F_new, rho_new)]
-                        err_real.append(err)
-                        recip = self._reciprocal_errors(res[4], F_new, res[5]) if want else {}
-                        for n_, v_ in recip.items():
-                            err_recip[n_].append(v_)
-                        main_err = self._main_error(err, recip)
-                        err_main.append(main_err)
-                        better = best['err'] > main_err
-                        if better.any():
-                            sel = better[:, None, None]
-                            best['pair'] = (np.where(sel, F_new, best['pair'][0]), np.where(sel, rho_new, best['pair'][1]))
-                            best['mask'] = np.where(sel, support, best['mask'])
-                            best['err'] = np.where(better, main_err, best['err'])
-                            best['iter'] = np.where(better, iteration, best['iter'])
-                        step += 1
-            n_first = lo.get('best_density_not_in_first_n_iterations', np.inf)
-            res = best['iter'] > n_first                              # 945-949
-            if np.any(res):
-                sel = res[:, None, None]
-                hist = hist[1:] + [(np.where(sel, best['pair'][0], hist[-1][0]), np.where(sel, best['pair'][1], hist[-1][1]))]
-                support = np.where(sel, best['mask'], support)
-            iterations.append(iteration)
-        return rho0, best['pair'], hist[-1], best['err'], best['mask'], support, err_real, err_main, err_recip, unknowns, iterations
+        s = _OperatorState(self, F0, rho0)
+        iterations, _ = self._walk(s)
+        return (rho0, s.best['pair'], s.hist[-1], s.best['err'], s.best['mask'], s.support, s.err_real, s.err_main, s.err_recip, s.unknowns,
+                iterations)
 
     def _loop_resident(self):
-        """the same sub-loops on the resident engine, after the 3-D host loop (reconstruct.py:216-269): consecutive steps of one
-        method are ONE `run`, errors, metrics and best tracking stay on the device; the host keeps what upstream decides on the host
-        (ramps, the ft_stab link from the enforce flags, iteration counts)"""
-        e, B, opt = self.engine, self.B, self.opt
+        """the same sub-loops on the resident engine: consecutive steps of one method are ONE `run`, errors, metrics and best tracking
+        stay on the device; the host keeps what upstream decides on the host (`schedule.walk`)"""
+        e, B = self.engine, self.B
         for b in range(B):
             e.set_density(b, self._initial_density(b))
         e.set_initial_support(self.initial_support)
@@ -478,73 +473,11 @@ class MTIP2D:
             e.set_main_error(self.main_type, items)
         e.init_state()
         rho0 = e.density()
-        self._sig_ramps, self._thr_ramps = self._sw_ramps()
-        self.sw_sigma, self.sw_threshold = self.default_sigma, 0.06
-        hio_opt = opt['projections']['real']['HIO']
-        eis_opt = opt['projections']['real']['projections']['support']['enforce_initial_support']
-        limit = eis_opt['if_error_bigger_than'] if eis_opt['apply'] else np.inf
-        loops = opt['main_loop']['sub_loops']
-        eis_list, iterations = [], []
-        n_steps, fxs_steps = 0, 0
-        best_err_h, best_iter_h = np.full(B, np.inf), np.zeros(B, int)
-        for loop_number, loop_name in enumerate(loops['order']):
-            lo = loops[loop_name]
-            methods = {}
-            for key in lo['order']:
-                mo = lo['methods'][key]
-                methods[key] = ({'iterations': mo.get('iterations', 0), 'options': mo} if isinstance(mo, dict) else {'iterations': mo, 'options': {}})
-                if key not in ('HIO', 'ER', 'SW', 'SW_center', 'HIO_non_FXS', 'ER_non_FXS'):
-                    raise NotImplementedError('2-D loop method %r' % (key,))
-                if key.endswith('_non_FXS') and self.reciprocal_metrics:
-                    raise NotImplementedError('2-D %s with reciprocal metrics enabled: the reference raises' % key)
-            beta_cfg = hio_opt['beta'][loop_number] if len(hio_opt['beta']) - 1 >= loop_number else [0.5, 0.5, -1 / 700, 1600]
-            ramp = hs.ExponentialRamp(*beta_cfg)
-            if 'SW' in methods:
-                self._update_shrink_wrap(0, loop_number)
-            e.begin_sub_loop()                                        # stale = hist, latest_intensity = None (reconstruct.py:859, 866)
-            loop_first_step, step_iteration = n_steps, []
-            step = sw_step = iteration = 0
-            for iteration in range(1, lo['iterations'] + 1):
-                for key in lo['order']:
-                    if key == 'SW':
-                        eis_list.append(e.shrinkwrap_state(self.sw_sigma, self.sw_threshold, limit))
-                        sw_step += 1
-                        self._update_shrink_wrap(sw_step, loop_number)
-                        continue
-                    if key == 'SW_center':
-                        if n_steps == 0:
-                            raise IndexError("SW_center before any phasing step: error_dict['main'][-1] of an empty list (reconstruct.py:887)")
-                        eis_list.append(e.fetch_main_errors(n_steps - 1, 1)[0] > limit)
-                        for _ in range(methods[key]['iterations']):
-                            e.shrinkwrap_state(self.sw_sigma, self.sw_threshold, limit)     # (the same decision: no step in between)
-                            e.refresh_reciprocal_density()
-                            sw_step += 1
-                            self._update_shrink_wrap(sw_step, loop_number)
-                        continue
-                    repeats = methods[key]['iterations']
-                    ft_stab = self._change_to_ft_stab(methods[key]['options'], key, eis_list)
-                    if ragged and repeats:
-                        raise ValueError('main error over metrics of different shapes (inhomogeneous array upstream, fxs_IO_methods.py:758)')
-                    betas = np.array([ramp.eval(step + i) for i in range(repeats)], dtype=float)
-                    e.run(key, ft_stab, betas, fetch=False)           # (a block of no steps still takes / drops the non-FXS intensity)
-                    step += repeats
-                    n_steps += repeats
-                    step_iteration += [iteration] * repeats
-                    if not key.endswith('_non_FXS'):
-                        fxs_steps += repeats
-            if n_steps > loop_first_step:                             # the best ITERATION is followed on the host (reconstruct.py:934-938)
-                errs = e.fetch_main_errors(loop_first_step, n_steps - loop_first_step)
-                for i, it in enumerate(step_iteration):
-                    better = best_err_h > errs[i]
-                    best_err_h = np.where(better, errs[i], best_err_h)
-                    best_iter_h = np.where(better, it, best_iter_h)
-            reselect = best_iter_h > lo.get('best_density_not_in_first_n_iterations', np.inf)      # 945-949
-            if np.any(reselect):
-                e.select_best(reselect)
-            iterations.append(iteration)
+        s = _ResidentState(self, ragged)
+        iterations, n_steps = self._walk(s)
         err_real, err_main = e.fetch_errors(0, n_steps), e.fetch_main_errors(0, n_steps)
         err_recip = e.fetch_reciprocal_metrics(0, n_steps) if self.reciprocal_metrics else {}
-        unknowns = e.unknowns() if fxs_steps else None
+        unknowns = e.unknowns() if s.fxs_steps else None
         return (rho0, (e.reciprocal_density(True), e.density(True)), (e.reciprocal_density(), e.density()), e.best_error()[0], e.support(True),
                 e.support(), err_real, err_main, err_recip, unknowns, iterations)
 
