@@ -2,7 +2,8 @@
 emulator suite (tests/test_emul_resident2d.py, lib_path = the emulation build) and the MI355X suite (tests/test_gpu_resident2d.py,
 lib_path = None).  The yardsticks are the ones the operator-level 2-D loop is held to: the reference's own 2-D runs (fixtures G20,
 G22), oracle/mtip2d.py, and the operator-level calls themselves (`Engine2D.step`, `.shrinkwrap`), which this engine leaves as they
-are."""
+are; section 8 adds a longdouble restatement of one step (tests/resident2d_reference.py) at the shapes where the geometry of the fused
+kernels changes."""
 import numpy as np
 
 import parity_cases as PC
@@ -519,3 +520,352 @@ def check_launch_budget(g, lib_path):
         assert 'error -5' in str(ex) and 'mtip2d_set_projection' in str(ex), ex
     assert launch_log(e) == ()
     e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 8. the step kernels' geometry
+# One resident step against the longdouble restatement (tests/resident2d_reference.py) at the shapes where the geometry of the k2d_rs_*
+# kernels changes: (shells N, max order M, restarts) -> what the shape reaches.  Rows have 2 M + 1 values.
+REFERENCE_SHAPES = {
+    (5, 6, 9): 'second restart group with one restart; Hankel slices of 2, 2, 1, 0 shells; finish wave 0 takes restarts 0, 4, 8',
+    (13, 6, 17): 'three groups, a full middle one; last Hankel slice of one shell',
+    (6, 64, 3): '129 values: one left-over column on the wave-per-output path',
+    (6, 65, 2): '131 values: the first row length back on the two-round path',
+    (6, 86, 9): '173 values: the largest row the LDS limit admits, two groups',
+    (7, 1, 2): '3 values, 2 coefficient outputs: the wave path with no full round',
+}
+# Distance of oracle/mtip2d.py's step (complex128, numpy FFT, pairwise sums) from the restatement, measured on the CPU with
+# `oracle_distance` below from the very states of these cases, worst restart and method; per quantity the largest deviation of a row
+# relative to the restart's largest value (F', rho'), relative for the scalars:
+#            shape          F'       rho'     unknowns  real err  l2       deg2      main
+ORACLE_DISTANCE = {
+    (5, 6, 9):     (1.5e-15, 9.6e-16, 1.4e-14, 6.6e-16, 4.2e-16, 1.1e-14, 6.6e-16),
+    (13, 6, 17):   (1.1e-15, 1.0e-15, 8.8e-15, 2.6e-15, 6.1e-16, 3.9e-14, 2.6e-15),
+    (6, 64, 3):    (7.8e-15, 1.9e-15, 3.1e-14, 2.3e-16, 7.5e-16, 2.6e-14, 2.3e-16),
+    (6, 65, 2):    (5.9e-15, 2.3e-15, 2.8e-14, 4.8e-16, 4.5e-16, 1.4e-14, 4.8e-16),
+    (6, 86, 9):    (4.3e-14, 3.9e-15, 4.4e-14, 8.4e-16, 8.9e-16, 4.6e-14, 8.4e-16),
+    (7, 1, 2):     (4.8e-16, 4.8e-16, 1.1e-16, 2.1e-15, 3.4e-16, 1.1e-15, 2.1e-15),
+}                                                                     # largest: 4.6e-14 -> BOUND_STEP = 2.3e-12
+# The bound of the comparison is 50 x the largest of these figures: a sequential sum of n terms (the device, up to 173 per row) against
+# numpy's pairwise one loses up to n / log2(n) ~ 23 times more, with a factor 2 on top.  It never comes from what the resident engine
+# gives, and it has to stay below the project's single-step bound.  (For comparison only, the resident engine against the
+# restatement on the MI355X, same quantities: (5, 6, 9) 1.0e-13 (deg2), (13, 6, 17) 3.1e-14 (unknowns), (6, 64, 3) 3.9e-14 (deg2),
+# (6, 65, 2) 9.1e-14 (deg2), (6, 86, 9) 1.6e-13 (deg2; F' 1.4e-13), (7, 1, 2) 1.0e-15; every column in profiles/resident2d_coverage.txt.)
+BOUND_STEP = 50 * max([max(v) for v in ORACLE_DISTANCE.values()] or [0.0])
+assert BOUND_STEP <= TOL_STEP
+STEP_RUNS = (('HIO', 'mask'), ('ER', False), ('HIO_non_FXS', True), ('ER_non_FXS', False))
+QUANTITIES = ('F', 'rho', 'unknowns', 'err', 'l2', 'deg2', 'main')
+_SEEDS = {(5, 6, 9): 101, (13, 6, 17): 102, (6, 64, 3): 103, (6, 65, 2): 104, (6, 86, 9): 105, (7, 1, 2): 106}
+
+
+class _RecordedTables:
+    """wraps the engine's setters while an MTIP2D is built: what the host hands to the context is what the restatement gets"""
+    NAMES = ('set_projection', 'set_so_freedom', 'set_real_constraints', 'set_error_weights')
+
+    def __enter__(self):
+        from xframe_amd.fxs import polar2d as P2D
+        self.P2D, self.rec = P2D, {}
+        self.saved = {k: getattr(P2D.Engine2D, k) for k in self.NAMES}
+        self.saved_w = P2D.assemble_weights_2d
+
+        def wrap(name):
+            def call(eng, *a):
+                self.rec[name] = a
+                return self.saved[name](eng, *a)
+            return call
+
+        def weights(*a):
+            self.rec['weights'] = self.saved_w(*a)
+            return self.rec['weights']
+        for k in self.NAMES:
+            setattr(P2D.Engine2D, k, wrap(k))
+        P2D.assemble_weights_2d = weights
+        return self
+
+    def __exit__(self, *exc):
+        for k in self.NAMES:
+            setattr(self.P2D.Engine2D, k, self.saved[k])
+        self.P2D.assemble_weights_2d = self.saved_w
+
+    def tables(self, e, deg2_ref=None, deg2_norms=None, l2_weights=None):
+        import resident2d_reference as RR
+        r = self.rec
+        vectors, used, rmask, n_particles = r['set_projection'] if 'set_projection' in r else (np.zeros((0, e.N)), {}, np.zeros((0, e.N)), 1.0)
+        ids = np.array(list(used.values()), dtype=int)
+        return RR.make_tables(e.N, e.M, r['weights'][0], r['weights'][1], np.zeros(e.n_phi, bool), vectors, np.asarray(rmask, bool)[ids], ids, e.qs,
+                              n_particles, r['set_so_freedom'][0] if 'set_so_freedom' in r else None, r['set_real_constraints'], r['set_error_weights'][0],
+                              deg2_ref, deg2_norms, l2_weights)
+
+
+class _StepProblem:
+    """one of REFERENCE_SHAPES: the scaled problem with the orders 0 .. min(M, 6) used (the orders beyond carry no signal at these
+    shell counts: their scalar products are rounding noise whose phase is arbitrary on either side), both reciprocal metrics on, a
+    seeded guess and a random support with holes per restart"""
+
+    def __init__(self, g, lib_path, N, M, B, restarts=None, nan_in=None):
+        import resident2d_reference as RR
+        self.RR, self.shape, self.lib_path = RR, (N, M, B), lib_path
+        data, o = PC.mtip2d_scaled_problem(g, N, M)
+        o = OM.deep_update(o, RR.METRICS_ON)
+        o['projections']['reciprocal']['used_order_ids'] = np.arange(min(M, 6) + 1)
+        self.data, self.o = data, o
+        self.pick = list(range(B)) if restarts is None else list(restarts)         # (a single-restart twin of restart b: restarts=[b])
+        with _RecordedTables() as rec:
+            self.m = m = MTIP2D(o, data, n_restarts=len(self.pick), seeds=[4] * len(self.pick), lib_path=lib_path, resident=True)
+        self.e = e = m.engine
+        rhos, sups = RR.seeded_inputs(m._initial_density(0), B, _SEEDS[(N, M, B)])
+        if nan_in is not None:
+            rhos[nan_in][N // 2, M] = np.nan
+        self.rhos, self.sups = [rhos[b] for b in self.pick], [sups[b] for b in self.pick]
+        self.mask = np.array([b % 3 != 1 for b in self.pick])
+        ref = m._deg2_ref.copy()                                                  # as MTIP2D._loop_resident hands them over
+        ref[m.rsetup.used_orders[0]] = m._deg2_ref[m.rsetup.used_orders[0]] / m.rsetup.number_of_particles
+        from xframe_amd.fxs.reconstruct2d import polar_integrator_weights
+        w_l2 = polar_integrator_weights(e.rs, e.phis)
+        w_l2[N - 2, :] = 0.0
+        self.metrics = (ref, m._deg2_norm, w_l2)
+        self.t = rec.tables(e, *self.metrics)
+        for b, r in enumerate(self.rhos):
+            e.set_density(b, r)
+        e.set_initial_support(m.initial_support)
+        self.prepare(True)
+        self.rho_in, self.F0 = e.density(), e.reciprocal_density()
+
+    def prepare(self, fxs, kind='mean', items=('real',)):
+        e = self.e
+        e.set_reciprocal_metrics(*(self.metrics if fxs else ()))
+        e.set_main_error(kind, list(items))
+        e.init_state()
+        for b, s in enumerate(self.sups):
+            e.set_support(b, s)
+
+    def run(self, method, ft, beta=0.45, kind='mean', items=('real',)):
+        """one step from the prepared state -> per restart the dict layout of resident2d_reference.step"""
+        e, fxs = self.e, not method.endswith('_non_FXS')
+        self.prepare(fxs, kind, items)
+        err = e.run(method, self.mask if isinstance(ft, str) else ft, [beta])
+        F, rho, main = e.reciprocal_density(), e.density(), e.fetch_main_errors(0, 1)[0]
+        unk = e.unknowns() if fxs else None
+        rec = e.fetch_reciprocal_metrics(0, 1) if fxs else {}
+        # the first step after init_state improves on the best error inf (unless its main error is NaN): its pair and support are kept
+        kept = ~np.isnan(main)
+        for latest, best in ((F, e.reciprocal_density(True)), (rho, e.density(True)), (np.array(self.sups), e.support(True))):
+            assert np.array_equal(latest[kept], best[kept]), (self.shape, method)
+        assert np.array_equal(e.best_error()[0][kept], main[kept])
+        return [dict(F_new=F[b], rho_new=rho[b], err=err[0, b], main=main[b], unknowns=unk[b] if fxs else None,
+                     rl2=rec['l2_projection_diff'][0, b] if fxs else None, deg2=rec['deg2_invariant_l2_diff'][0, b] if fxs else None)
+                for b in range(len(self.pick))]
+
+    def reference(self, method, ft, b, beta=0.45):
+        """the restatement's step of restart b (position in `pick`) from the state the device holds; conditions on the inputs asserted"""
+        RR, fxs = self.RR, not method.endswith('_non_FXS')
+        flag = bool(self.mask[b]) if isinstance(ft, str) else ft
+        ref = RR.step(self.t, method, flag, beta, self.rho_in[b], self.sups[b], None if fxs else RR.modulus(self.F0[b]))
+        assert ref['err'] > 0 and rel_l2(np.asarray(ref['rho_new'], complex), self.rho_in[b]) > 1e-3, (self.shape, method, b)
+        if fxs:
+            assert ref['conditioning'].min() >= 1e-6, (self.shape, method, b, ref['conditioning'])
+            assert ref['rl2'] > 0 and (ref['deg2'][self.t['deg2_norm'] != 0] > 0).all() and (ref['deg2'][self.t['deg2_norm'] == 0] == -1).all()
+        ref['main'] = RR.main_error('mean', ['real'], ref['err'], ref['rl2'], ref['deg2'])
+        return ref
+
+    def close(self):
+        self.m.close()
+
+
+def _distance(RR, got, ref, fxs):
+    d = RR.step_distance(got, ref, fxs)
+    if 'main' in got:
+        d['main'] = RR.deviation(got['main'], ref['main'])
+    return d
+
+
+def check_step_vs_restatement(g, lib_path, N, M, B):
+    """one step of HIO (ft_stab per restart, b % 3 != 1: the mask alternates inside and across the groups), ER, HIO_non_FXS and
+    ER_non_FXS from one state against the restatement: every shell row of every restart, every scalar, bound BOUND_STEP; then the
+    restarts 0, 7, 8 and B - 1 of the batch against single-restart runs of the resident engine, bit for bit"""
+    import resident2d_reference as RR
+    p = _StepProblem(g, lib_path, N, M, B)
+    assert np.isfinite(p.rho_in).all()
+    worst = dict.fromkeys(QUANTITIES, 0.0)
+    batch = {}
+    for method, ft in STEP_RUNS:
+        fxs = not method.endswith('_non_FXS')
+        refs = [p.reference(method, ft, b) for b in range(B)]       # (conditions first: nothing is compared on a degenerate input)
+        if fxs:
+            print(f'{N} x M{M} x {B} {method}: smallest conditioning %.2e' % min(r['conditioning'].min() for r in refs))
+        batch[method] = got = p.run(method, ft)
+        for b in range(B):
+            d = _distance(RR, got[b], refs[b], fxs)
+            print(f'{N} x M{M} x {B} {method} restart {b}: ' + ' '.join(f'{k} {v:.2e}' for k, v in d.items()))
+            for k, v in d.items():
+                worst[k] = max(worst[k], v)
+        assert max(worst.values()) <= BOUND_STEP, (method, worst, BOUND_STEP)
+    p.close()
+    print(f'{N} x M{M} x {B} worst ' + ' '.join(f'{k} {v:.2e}' for k, v in worst.items()), 'bound %.2e' % BOUND_STEP)
+    for b in sorted({0, 7, 8, B - 1} & set(range(B))):
+        p1 = _StepProblem(g, lib_path, N, M, B, restarts=[b])
+        assert np.array_equal(p1.rho_in[0], p.rho_in[b])
+        for method, ft in STEP_RUNS:
+            one = p1.run(method, ft)[0]
+            for k, v in one.items():
+                assert v is None or np.array_equal(v, batch[method][b][k]), (N, M, B, method, b, k)
+        p1.close()
+    return worst
+
+
+def oracle_distance(g, lib_path, N, M, B):
+    """how ORACLE_DISTANCE was measured: oracle/mtip2d.py's step from the states of check_step_vs_restatement against the restatement
+    with the oracle's own tables (the state comes from the engine: any build will do, the figures are the oracle's)"""
+    import resident2d_reference as RR
+    from oracle import mtip2d as O2
+    p = _StepProblem(g, lib_path, N, M, B)
+    mo = O2.MTIP2D(p.o, p.data)
+    t = RR.tables_from_oracle(mo)
+    worst = dict.fromkeys(QUANTITIES, 0.0)
+    for method, ft in STEP_RUNS:
+        fxs = not method.endswith('_non_FXS')
+        for b in range(B):
+            flag = bool(p.mask[b]) if isinstance(ft, str) else ft
+            fixed = None if fxs else RR.modulus(p.F0[b])
+            ref = RR.step(t, method, flag, 0.45, p.rho_in[b], p.sups[b], fixed)
+            got = RR.oracle_step(mo, method, flag, 0.45, p.rho_in[b], p.sups[b], None if fxs else np.asarray(fixed, float))
+            got['main'], ref['main'] = got['err'], ref['err']
+            for k, v in _distance(RR, got, ref, fxs).items():
+                worst[k] = max(worst[k], v)
+    p.close()
+    return worst
+
+
+def check_main_error_kinds(g, lib_path=None, N=5, M=6, B=9):
+    """mean / min / max / prod over ['real'], ['real', 'l2_projection_diff'] and ['deg2_invariant_l2_diff'] in k2d_rs_finish against the
+    restatement (numpy's functions on its values), nine restarts: a wave of the finish kernel takes more than one.  Then NaN as
+    data: one NaN in the guess of restart 4 -- its error, main error and best error are what numpy's functions give (NaN; the best
+    error stays inf, nothing is kept as better), the other eight restarts are bit-equal to the run without it; and a NaN in the deg2
+    reference of one order behind finite ones -- min and max over the orders are NaN as numpy's are"""
+    import resident2d_reference as RR
+    p = _StepProblem(g, lib_path, N, M, B)
+    refs = [p.reference('HIO', 'mask', b) for b in range(B)]
+    item_sets = (['real'], ['real', 'l2_projection_diff'], ['deg2_invariant_l2_diff'])
+    clean = {}
+    for kind in ('mean', 'min', 'max', 'prod'):
+        for items in item_sets:
+            got = p.run('HIO', 'mask', kind=kind, items=items)
+            best = p.e.best_error()[0]
+            for b in range(B):
+                want = RR.main_error(kind, items, refs[b]['err'], refs[b]['rl2'], refs[b]['deg2'])
+                d = RR.deviation(got[b]['main'], want)
+                print(f'{kind} {items} restart {b}: {d:.2e}')
+                assert d <= BOUND_STEP and best[b] == got[b]['main'], (kind, items, b, d)
+            clean[kind, tuple(items)] = got
+    # the kinds differ on these values (a swap of two of them would show)
+    for b in range(B):
+        vals = {k: clean[k, ('deg2_invariant_l2_diff',)][b]['main'] for k in ('mean', 'min', 'max', 'prod')}
+        assert len(set(vals.values())) == 4 and vals['min'] < vals['mean'] < vals['max'], vals
+    p.close()
+    q = _StepProblem(g, lib_path, N, M, B, nan_in=4)
+    assert np.isnan(q.rho_in[4]).all() and np.isfinite(np.delete(q.rho_in, 4, axis=0)).all()
+    for kind in ('mean', 'min', 'max', 'prod'):
+        for items in item_sets:
+            got = q.run('HIO', 'mask', kind=kind, items=items)
+            best, best_rho = q.e.best_error()[0], q.e.density(True)
+            want = RR.main_error(kind, items, got[4]['err'], got[4]['rl2'], got[4]['deg2'])         # numpy's function on the device's values
+            assert np.isnan(got[4]['err']) and np.isnan(want) and np.isnan(got[4]['main']), (kind, items, got[4])
+            assert best[4] == np.inf and np.array_equal(best_rho[4], q.rho_in[4], equal_nan=True)          # not "better": nothing was kept
+            for b in range(B):
+                if b != 4:
+                    for k, v in got[b].items():
+                        assert np.array_equal(v, clean[kind, tuple(items)][b][k]), (kind, items, b, k)
+                    assert best[b] == got[b]['main']
+    # a NaN behind finite values: order 2 of the deg2 reference (orders 0 .. 6 used, the odd ones have no norm: -1)
+    ref, norms, w_l2 = q.metrics
+    bad = ref.copy()
+    bad[2, 1, 1] = np.nan
+    q.metrics = (bad, norms, w_l2)
+    for kind in ('mean', 'min', 'max', 'prod'):
+        got = q.run('HIO', 'mask', kind=kind, items=['deg2_invariant_l2_diff'])
+        for b in range(B):
+            d2 = got[b]['deg2']
+            assert np.isnan(d2[2]) and (b == 4 or (np.isfinite(d2[0]) and d2[1] == -1.0)), (b, d2)
+            assert np.isnan(RR.KINDS[kind](d2)) and np.isnan(got[b]['main']), (kind, b, d2, got[b]['main'])
+    q.close()
+
+
+def check_schedule_nine_restarts(g, name, lib_path=None):
+    """check_shadowed_schedule_2d with nine restarts (two groups, the second with one restart): its own bound, supports equal"""
+    sh = check_shadowed_schedule_2d(g, name, lib_path, n_restarts=9)
+    assert sh.e.B == 9 and sh.flips == 0
+    return sh
+
+
+def check_select_where_both_groups(g, lib_path=None, N=5, M=6, B=9):
+    """select_best with a `where` mask that picks restarts of both groups (1, 7, 8 of nine), at a moment when every restart's best
+    pair is NOT its latest one: the picked restarts take their best pair and support, the others keep theirs, bit for bit"""
+    p = _StepProblem(g, lib_path, N, M, B)
+    e = p.e
+    p.prepare(True)
+    e.run('ER', False, [0.5, 0.5], fetch=False)
+    rng = np.random.default_rng(77)
+    for b in range(B):
+        e.set_support(b, rng.random(e.shape) > 0.7)                 # far fewer points allowed: the next step's error is larger
+    e.run('HIO', p.mask, [0.5], fetch=False)
+    main = e.fetch_main_errors(0, 3)
+    assert (main[2] > main[:2].min(axis=0)).all(), main
+    where = np.array([b in (1, 7, 8) for b in range(B)])
+    before = (e.reciprocal_density(), e.density(), e.support())
+    best = (e.reciprocal_density(True), e.density(True), e.support(True))
+    assert all(not np.array_equal(before[1][b], best[1][b]) for b in range(B))
+    assert np.array_equal(e.best_error()[0], main.min(axis=0))
+    e.select_best(where)
+    for a, b_, c in zip(before, best, (e.reciprocal_density(), e.density(), e.support())):
+        assert np.array_equal(np.where(where[:, None, None], b_, a), c)
+    err = e.run('ER', False, [0.5])                                  # and the loop goes on from the selected state (coefficients refreshed)
+    assert np.isfinite(err).all()
+    p.close()
+
+
+def check_lds_limit(g, lib_path=None):
+    """rows of 175 values (M = 87) need more LDS than the fused step kernels may take: the resident calls refuse with error -1 and launch
+    nothing, the operator-level step of the same context still works; 173 values (M = 86) are accepted"""
+    import resident2d_reference as RR
+    rng = np.random.default_rng(8)
+
+    def build(M):
+        data, o = PC.mtip2d_scaled_problem(g, 4, M)
+        o['projections']['reciprocal']['used_order_ids'] = np.arange(7)
+        with _RecordedTables() as rec:
+            m = MTIP2D(o, data, n_restarts=1, seeds=[4], lib_path=lib_path, resident=True)
+        top = np.abs(m._initial_density(0)).max()
+        rho = top * (rng.random(m.shape) - 0.3) + 0.01j * top * rng.standard_normal(m.shape)
+        return m, m.engine, rec, rho, rng.random(m.shape) > 0.3
+    m, e, rec, rho, sup = build(87)
+    assert e.n_phi == 175
+    launch_log(e)
+    for call in (lambda: e.set_density(0, rho), lambda: e.set_initial_support(sup), lambda: e.set_support(0, sup)):
+        try:
+            call()
+            raise AssertionError('no error')
+        except MtipError as ex:
+            assert 'error -1' in str(ex) and 'LDS' in str(ex), ex
+    try:
+        e.init_state()
+        raise AssertionError('no error')
+    except MtipError as ex:
+        assert 'error -5' in str(ex), ex
+    assert launch_log(e) in (None, ())
+    t = rec.tables(e)
+    for method in ('HIO', 'ER_non_FXS'):                                 # the operator-level step of this context is not concerned
+        fxs = method == 'HIO'
+        fixed = None if fxs else np.asarray(RR.modulus(1.5 * e.fourier_transform(rho)[0]), float)
+        got = e.step(method, True, 0.5, rho, sup, fixed_intensity=fixed)
+        ref = RR.step(t, method, True, 0.5, rho, sup, fixed)
+        assert ref['err'] > 0 and (not fxs or ref['conditioning'].min() >= 1e-6)
+        d = RR.step_distance(dict(F_new=got[0][0], rho_new=got[1][0], err=got[2][0], unknowns=got[3][0] if fxs else None), ref, fxs)
+        print('4 x M87 operator-level', method, d)
+        assert max(d.values()) <= BOUND_STEP, (method, d)
+    m.close()
+    m, e, rec, rho, sup = build(86)
+    assert e.n_phi == 173
+    e.set_density(0, rho)
+    e.set_initial_support(sup)
+    e.init_state()
+    assert np.isfinite(e.run('HIO', True, [0.5])).all() and np.isfinite(e.density()).all()
+    m.close()

@@ -76,3 +76,26 @@ def test_worker_default_unchanged(emul_lib, golden_mtip2d):
 
 def test_launch_budget(emul_lib, golden_mtip2d):
     RC.check_launch_budget(golden_mtip2d, emul_lib)
+
+
+# ---- the step kernels past one restart group and one row round (the same cases as tests/test_gpu_resident2d.py)
+@pytest.mark.parametrize('N,M,B', sorted(RC.REFERENCE_SHAPES))
+def test_step_vs_restatement(emul_lib, golden_mtip2d, N, M, B):
+    RC.check_step_vs_restatement(golden_mtip2d, emul_lib, N, M, B)
+
+
+def test_main_error_kinds(emul_lib, golden_mtip2d):
+    RC.check_main_error_kinds(golden_mtip2d, emul_lib)
+
+
+@pytest.mark.parametrize('name', sorted(RC.SCHEDULES))
+def test_shadowed_schedule_nine_restarts(emul_lib, golden_mtip2d, name):
+    RC.check_schedule_nine_restarts(golden_mtip2d, name, emul_lib)
+
+
+def test_select_where_both_groups(emul_lib, golden_mtip2d):
+    RC.check_select_where_both_groups(golden_mtip2d, emul_lib)
+
+
+def test_lds_limit(emul_lib, golden_mtip2d):
+    RC.check_lds_limit(golden_mtip2d, emul_lib)

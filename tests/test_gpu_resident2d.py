@@ -61,3 +61,32 @@ def test_worker_vs_oracle(golden_mtip2d, N, M):
 
 def test_worker_default_unchanged(golden_mtip2d):
     RC.check_worker_default_unchanged(golden_mtip2d)
+
+
+def test_wide_rows(golden_mtip2d):
+    """8 shells x M = 64 and 16 shells x M = 64: rows of 129 values, the left-over column on the wave-per-output path"""
+    RC.check_ft_stab_per_restart(golden_mtip2d, None, 8, 64)
+    RC.check_wide_rows(golden_mtip2d, None, 16, 64)
+
+
+# ---- the step kernels past one restart group and one row round, against the longdouble restatement (tests/resident2d_reference.py)
+@pytest.mark.parametrize('N,M,B', sorted(RC.REFERENCE_SHAPES))
+def test_step_vs_restatement(golden_mtip2d, N, M, B):
+    RC.check_step_vs_restatement(golden_mtip2d, None, N, M, B)
+
+
+def test_main_error_kinds(golden_mtip2d):
+    RC.check_main_error_kinds(golden_mtip2d)
+
+
+@pytest.mark.parametrize('name', sorted(RC.SCHEDULES))
+def test_shadowed_schedule_nine_restarts(golden_mtip2d, name):
+    RC.check_schedule_nine_restarts(golden_mtip2d, name)
+
+
+def test_select_where_both_groups(golden_mtip2d):
+    RC.check_select_where_both_groups(golden_mtip2d)
+
+
+def test_lds_limit(golden_mtip2d):
+    RC.check_lds_limit(golden_mtip2d)
