@@ -391,6 +391,35 @@ int mtip_op_cc_harmonic_filter(mtip_ctx* ctx, int n_q, int n_delta, int max_orde
                                const double* average_intensity, double* cc_out);
 int mtip_op_cc_binned_mean(mtip_ctx* ctx, int n_q, int n_delta, int n_bins, const int32_t* bin_start, int n_roll, const double* cc,
                            const uint8_t* cc_mask, const double* average_intensity, double* cc_out, uint8_t* mask_out);
+/* The other back-substitution modes of ccd_to_deg2_invariant_3d (csrc/k_extract_psd.h; mode table fxs_invariant_tools.py:440).
+ * mtip_op_nearest_psd: nearest_positive_semidefinite_matrix (mathLibrary.py:872-892, limit = 0) of a stack.  A, out (n_mat, n, n)
+ *   complex128, row major, out must not alias A; only the Hermitian part H = (A + A^+) / 2 counts (878); n_clipped (n_mat) int32:
+ *   the eigenvalues set to zero.  All on the device: H and sigma = |H|_F, the one-sided Jacobi of mtip_op_hermitian_eig on
+ *   H + sigma 1 (positive semi-definite: no +x / -x eigenvalue pairs, so no repeat and nothing per matrix through the host;
+ *   eigenvalues to eps |H|_F absolute, as LAPACK's), out = sum_k max(lambda_k, 0) v_k v_k^+, Hermitian to the bit.
+ *   1 <= n <= 1024, else MTIP_EINVAL with the limit and the value in the message and untouched outputs.
+ * mtip_op_cm_backsub: back-substitution on harmonic coefficients.  cm (max_order + 1, n_q, n_q) complex128, order major: what
+ *   mtip_op_cc_to_deg2[_wide] writes with dimensions = 2 and order_stride = 1; qq_mask (n_q, n_q) uint8, 1 = keep, or null;
+ *   b_out (max_order + 1, n_q, n_q), the orders that are not multiples of order_stride (1 or 2) as zeros; must not alias cm.
+ *   mode MTIP_BS_PLAIN: back_substitution (mathLibrary.py:1509-1517) on the harmonics m = 0, stride, .. per pair, from the highest
+ *     order down  B_l = C_l / c_l^l,  C_m -= B_l c_l^m;  masked pairs are zeroed first (fxs_invariant_tools.py:560): the mode
+ *     back_substitution_memory_hungry (519-576).  With the flag MTIP_BS_HERMITIAN_MEAN  C_m = (C_m + C_m^+) / 2 over (q1, q2) before
+ *     that (688-690): back_substitution_qqsym (646-694).  legendre as for mtip_op_cc_to_deg2 at order_stride; info is not touched.
+ *     n_q <= 4096.
+ *   mode MTIP_BS_PSD: back_substitution_psd (710-761).  Every C_m becomes its nearest PSD matrix (755), masked pairs are zeroed
+ *     (759), then psd_back_substitution (mathLibrary.py:1499-1507) over ALL orders from max_order down:
+ *     B_l = nearest_psd(C_l / c_l^l),  C_m -= B_l c_l^m (m < l);  b_out gets the orders that are multiples of order_stride (760).
+ *     legendre is the table at stride 1, (n_q, (max_order + 1)(max_order + 2) / 2).  info (max_order + 1) int32: eigenvalues
+ *     clipped at step l.  Per order two launches -- the eigen-decomposition and one kernel that rebuilds B_l, updates every lower
+ *     harmonic and prepares the next input with its shift -- and nothing crosses to the host between the steps.  n_q <= 1024.
+ *   Both: max_order <= 128; beyond the limits MTIP_EINVAL with the limit and the values in the message and untouched outputs;
+ *   every buffer may be host memory or memory of the context's device. */
+#define MTIP_BS_PLAIN 0
+#define MTIP_BS_PSD 1
+#define MTIP_BS_HERMITIAN_MEAN 1u
+int mtip_op_nearest_psd(mtip_ctx* ctx, int n, int n_mat, const mtip_cdouble* A, mtip_cdouble* out, int32_t* n_clipped);
+int mtip_op_cm_backsub(mtip_ctx* ctx, int n_q, int max_order, int order_stride, int mode, uint32_t flags, const mtip_cdouble* cm,
+                       const double* legendre, const uint8_t* qq_mask, mtip_cdouble* b_out, int32_t* info);
 /* degree-2 invariants -> cross-correlation, the inverse of mtip_op_cc_to_deg2 and the back half of the worker `simulate_ccd`
  * (csrc/k_simulate.h; fxs_invariant_tools.py:941-990 deg2_invariant_to_cc_3d, 934-939 deg2_invariant_to_cc_2d).
  * bl (max_order + 1, n_q, n_q) complex128.

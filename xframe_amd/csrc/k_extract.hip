@@ -937,6 +937,8 @@ extern "C" int mtip_op_cc_to_deg2_wide(mtip_ctx* c, int n_q, int n_delta, int ma
 #include "k_extract_lsq.h"
 // ---- the rest of modify_cross_correlation: low pass in q, harmonic filter, binned mean -------------------------------------
 #include "k_extract_cond.h"
+// ---- the other back-substitution modes (psd, qqsym, memory_hungry) on harmonics that are on the device; nearest PSD matrix ----
+#include "k_extract_psd.h"
 // ---- patterns -> cross-correlation (the stage in front of the one above) -----------------------------------------------
 #include "k_correlate.h"
 // ---- B_l -> cross-correlation (simulate_ccd: the inverse of mtip_op_cc_to_deg2) ------------------------------------------

@@ -170,6 +170,8 @@ _SIGNATURES = {
     'mtip_op_cc_lowpass_q': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void]),
     'mtip_op_cc_harmonic_filter': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void]),
     'mtip_op_cc_binned_mean': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, c_void, c_void, c_void]),
+    'mtip_op_nearest_psd': (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void]),
+    'mtip_op_cm_backsub': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, c_void, c_void, c_void, c_void, c_void]),
     'mtip_op_deg2_to_cc': (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void]),
     'mtip_correlate_create': (c_void, [c_void, C.POINTER(MtipCorrelateCfg), c_void, c_void, c_void]),
     'mtip_correlate_create_ex': (c_void, [c_void, C.POINTER(MtipCorrelateCfg), c_void, c_void, c_void, C.c_uint32]),

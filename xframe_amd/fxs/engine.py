@@ -399,6 +399,74 @@ class Engine(_lib.TensorOperands):
                        _lib.ptr(leg), p_out))
         return out
 
+    # ------------------------------------------------------------------ extract: the other back-substitution modes (fxs_invariant_tools.py:519-576, 646-761)
+    def _c128_stack(self, name, a):
+        """a complex128 stack (K, n, n): a numpy array, or a tensor on this engine's device"""
+        on_device = not isinstance(a, np.ndarray) and hasattr(a, 'data_ptr')
+        if on_device:
+            import torch
+            if a.dtype != torch.complex128 or not a.is_cuda:
+                raise TypeError('%s: a tensor must be complex128 on the GPU' % name)
+            a = a.contiguous()
+        else:
+            a = _lib.as_c128(a)
+        if a.ndim != 3 or a.shape[1] != a.shape[2]:
+            raise ValueError('%s: expected a stack of square matrices (K, n, n), got %r' % (name, tuple(a.shape)))
+        return on_device, a
+
+    def nearest_psd(self, mats):
+        """mtip_op_nearest_psd: nearest_positive_semidefinite_matrix (mathLibrary.py:872-892, limit 0) of one matrix or a stack
+        (K, n, n), a numpy array or a complex128 tensor on this engine's device (then the matrices come back as a tensor on it).
+        Only the Hermitian part counts.  Returns (out, n_clipped (K) int32 numpy: eigenvalues set to zero)."""
+        single = len(mats.shape) == 2
+        on_device, a = self._c128_stack('nearest_psd', mats[None] if single else mats)
+        K, n = int(a.shape[0]), int(a.shape[1])
+        clipped = np.empty(K, np.int32)
+        # the limits first: the call then writes nothing
+        if on_device:
+            import torch
+            out = torch.empty_like(a)
+            p_in, p_out = self._tp(a), self._tp(out)
+        else:
+            out = np.empty(a.shape if 1 <= n <= 1024 else (1,), complex)
+            p_in, p_out = _lib.ptr(a), _lib.ptr(out)
+        self._ck(self.lib.mtip_op_nearest_psd(self.ctx, n, K, p_in, p_out, _lib.ptr(clipped)))
+        return (out[0] if single else out), clipped
+
+    def cm_backsub(self, cm, legendre, order_stride=2, mode='plain', hermitian_mean=False, qq_mask=None):
+        """mtip_op_cm_backsub: back-substitution on harmonic coefficients cm (max_order + 1, Nq, Nq) complex128 (``cc_to_deg2`` with
+        dimensions=2, order_stride=1), a numpy array or a tensor on this engine's device (then B_l comes back as a tensor on it).
+        mode 'plain': mathLibrary.py:1509-1517 on the harmonics m = 0, order_stride, ..; legendre the table of
+        ``extract.legendre_table`` at order_stride; hermitian_mean: C_m = (C_m + C_m^+) / 2 first (back_substitution_qqsym).
+        mode 'psd': back_substitution_psd (fxs_invariant_tools.py:755-760); legendre the table at stride 1.  qq_mask (Nq, Nq) bool:
+        pairs to keep.  Returns (B_l (max_order + 1, Nq, Nq), info (max_order + 1) int32 numpy: eigenvalues clipped per step; None
+        for 'plain')."""
+        if mode not in ('plain', 'psd'):
+            raise ValueError('cm_backsub: mode %r (plain, psd)' % (mode,))
+        if hermitian_mean and mode != 'plain':
+            raise ValueError('cm_backsub: hermitian_mean belongs to mode plain')
+        on_device, cm = self._c128_stack('cm_backsub', cm)
+        L, nq = int(cm.shape[0]) - 1, int(cm.shape[1])
+        stride = int(order_stride)
+        n_m = L + 1 if mode == 'psd' else L // max(stride, 1) + 1
+        leg = _lib.as_f64(legendre)
+        assert leg.shape == (nq, n_m * (n_m + 1) // 2), leg.shape
+        mask = None
+        if qq_mask is not None:
+            mask = _lib.as_u8(np.asarray(qq_mask, dtype=bool))
+            assert mask.shape == (nq, nq), mask.shape
+        info = np.empty(L + 1, np.int32) if mode == 'psd' else None
+        if on_device:
+            import torch
+            out = torch.empty_like(cm)
+            p_in, p_out = self._tp(cm), self._tp(out)
+        else:
+            out = np.empty(cm.shape, complex)
+            p_in, p_out = _lib.ptr(cm), _lib.ptr(out)
+        self._ck_memory(self.lib.mtip_op_cm_backsub(self.ctx, nq, L, stride, 1 if mode == 'psd' else 0, 1 if hermitian_mean else 0, p_in,
+                                                    _lib.ptr(leg), _lib.ptr(mask), p_out, _lib.ptr(info)))
+        return out, info
+
     # ------------------------------------------------------------------ simulate_ccd: B_l -> cross-correlation (fxs_invariant_tools.py:934-1001)
     def deg2_to_cc(self, bl, mode='back_substitution', dimensions=3, legendre_t=None, cos_sin_theta=None, cos_delta=None):
         """mtip_op_deg2_to_cc: bl (max_order + 1, Nq, Nq) complex128, a numpy array or a torch tensor on this engine's device (then

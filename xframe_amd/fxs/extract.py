@@ -259,7 +259,8 @@ def cross_correlation_to_deg2_invariant(engine, cc, dim, **metadata):
 # above stays the unmasked operator and keeps refusing these options; extract_from_cross_correlation sends a data set whose settings
 # ask for a mask, for lstsq or for interpolate_masked here.  The masks are settings-derived tables computed once per data set (numpy);
 # the arithmetic on C runs in the two kernels of csrc/k_extract_lsq.h.
-_MASKED_MODES = ('back_substitution', 'lstsq')
+_MASKED_MODES = ('back_substitution', 'lstsq', 'back_substitution_memory_hungry', 'back_substitution_qqsym', 'back_substitution_psd')
+_CM_MODES = ('back_substitution_qqsym', 'back_substitution_psd')      # C_m by the dimensions = 2 entry, then Engine.cm_backsub
 _LSTSQ_RCOND_MIN = 1e-12               # about one decade above LAPACK's own cut eps max(M, N) (2e-13 .. 9e-13 for M = 1024 .. 4096)
 
 
@@ -456,6 +457,15 @@ def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, rank_deficient='
     arithmetic on the device.  metadata as for ``cross_correlation_to_deg2_invariant``; modes: 'back_substitution' (578-645: the masked
     samples are interpolated first, 605-608; qq_mask = mask'.all(-1)) and 'lstsq' (452-517: a fit over the unmasked samples of every
     pair; a pair without any gets zeros; qq_mask = mask'.any(-1)).  Returns (b_coeff (max_order + 1, Nq, Nq) complex, qq_mask).
+    The other back-substitutions of the mode table (440) live here too, as 'lstsq' does: 'back_substitution_memory_hungry' (519-576)
+    is the same elimination as 'back_substitution', interpolation implied (546-549), and returns that kernel's bits;
+    'back_substitution_qqsym' (646-694: Hermitian mean of the harmonics over (q1, q2)) and 'back_substitution_psd' (710-761: every
+    C_m and every B_l replaced by its nearest positive-semidefinite matrix inside the elimination) imply no interpolation, take
+    qq_mask = mask'.all(-1), zero the masked pairs, and run on the harmonics of ``Engine.cc_to_deg2`` (dimensions 2, stride 1) through
+    ``Engine.cm_backsub``; with an odd max_order and zero odd orders the solved system ends at max_order - 1.  For these two modes a
+    conditioning stage of modify_cc (low_pass_order_in_q, enforce_max_order, enforce_zero_odd_harmonics, apply_binned_mean) together
+    with a mask that removes samples raises NotImplementedError: they transform the masked samples as they are, and what those stages
+    leave at masked positions is not pinned to the reference.
 
     Raises ValueError where scipy's interp1d does (335-351; scipy 1.15.3): a row that has a valid sample and a masked sample outside
     the range of its valid ones -- every mask that removes Delta = 0 or the last angle of such a row, and every row with a single
@@ -499,17 +509,41 @@ def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, rank_deficient='
     cc_mask = np.asarray(cross_correlation_mask(data_grid, metadata), dtype=bool)
     if cc_mask.shape != tuple(cc.shape):
         raise ValueError('cc_mask has shape %r, the cross-correlation %r' % (cc_mask.shape, tuple(cc.shape)))
-    # interpolation: the setting, or implied by back_substitution (605-608; a no-op on a mask that is all true)
-    mod['interpolate_masked'] = bool(mod.get('interpolate_masked', False)) or mode == 'back_substitution'
+    # interpolation: the setting, or implied by back_substitution and its memory_hungry twin (605-608, 546-549; a no-op on a mask that
+    # is all true).  qqsym and psd transform the masked samples as they are (no interpolation upstream, 677 / 742): what
+    # cc_prepare_masked leaves at masked positions is pinned against modify_cross_correlation for subtract_average_intensity,
+    # pi_periodicity and q1q2_symmetric (G27 compares whole arrays, G31 the modes on top); the conditioning stages are not
+    implied = mode in ('back_substitution', 'back_substitution_memory_hungry')
+    if mode in _CM_MODES and not cc_mask.all() and not bool(mod.get('interpolate_masked', False)):
+        for key in _CONDITIONING_KEYS:
+            if not _is_off(mod.get(key, False)):
+                raise NotImplementedError('modify_cc.%s with masked data and bl_extraction_method %r: the mode transforms the masked samples '
+                                          'as they are (fxs_invariant_tools.py:677, 742), and what this stage leaves at masked positions is '
+                                          'not pinned to the reference' % (key, mode))
+    mod['interpolate_masked'] = bool(mod.get('interpolate_masked', False)) or implied
     cc2, mask2, phis = modify_masked_cross_correlation(engine, cc, cc_mask, phis, max_order,
                                                        average_intensity=metadata.get('average_intensity', False), **mod)
     if mod.get('apply_binned_mean', False):
         data_grid['phis'] = phis                                                                         # 395
     stride = 2 if metadata['assume_zero_odd_orders'] else 1
-    if mode == 'back_substitution':
+    if mode in ('back_substitution', 'back_substitution_memory_hungry'):                                 # (the same elimination: one kernel)
         leg = legendre_table(qs, metadata['xray_wavelength'], max_order, stride)
         b = engine.cc_to_deg2(cc2, max_order, order_stride=stride, dimensions=3, legendre=leg, wide=_wants_wide_entry(max_order, stride))
-        return np.asarray(b), np.asarray(mask2).all(-1)                                                  # 609
+        return np.asarray(b), np.asarray(mask2).all(-1)                                                  # 609, 550
+    if mode in _CM_MODES:
+        # the solved system ends at the highest extracted order (orders[order_mask].max(), 396-399, 675 / 740): max_order - 1 for an
+        # odd max_order with zero odd orders; the orders above come back as zeros (417-419)
+        l_max = (max_order // stride) * stride
+        psd = mode == 'back_substitution_psd'
+        qq_mask = np.asarray(mask2).all(-1)                                                              # 677, 742
+        cm = engine.cc_to_deg2(cc2, l_max, order_stride=1, dimensions=2, wide=_wants_wide_entry(l_max, 1))
+        leg = legendre_table(qs, metadata['xray_wavelength'], l_max, 1 if psd else stride)
+        b, _ = engine.cm_backsub(cm, leg, order_stride=stride, mode='psd' if psd else 'plain', hermitian_mean=not psd,
+                                 qq_mask=None if qq_mask.all() else qq_mask)
+        b = np.asarray(b)
+        if b.shape[0] < max_order + 1:
+            b = np.concatenate([b, np.zeros((max_order + 1 - b.shape[0],) + b.shape[1:], complex)])
+        return b, qq_mask
     extracted = np.arange(0, max_order + 1, stride)                                                      # orders[order_mask], 396-399
     thetas = np.arccos(qs * metadata['xray_wavelength'] / (4 * np.pi))                                   # 471, physicsLibrary.py:94-95
     if not np.isfinite(thetas).all():
@@ -536,7 +570,7 @@ def masked_cross_correlation_to_deg2_invariant(engine, cc, dim, rank_deficient='
 def _wants_masked_route(dopt):
     mask_type = (dopt.get('cc_mask') or {'type': 'none'}).get('type', 'none')
     mod = dopt.get('modify_cc') or {}
-    return (mask_type != 'none' or dopt.get('bl_extraction_method') == 'lstsq' or bool(mod.get('interpolate_masked', False))
+    return (mask_type != 'none' or dopt.get('bl_extraction_method') in ('lstsq',) + _MASKED_MODES[2:] or bool(mod.get('interpolate_masked', False))
             or any(not _is_off(mod.get(key, False)) for key in _CONDITIONING_KEYS))
 
 
