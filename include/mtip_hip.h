@@ -470,8 +470,15 @@ mtip_correlate* mtip_correlate_create(mtip_ctx* ctx, const mtip_correlate_cfg* c
  * made once per handle; a power of two up to 1024 runs the same kernels as without the flag and gives the same bits.  A refused
  * length (odd, below 16, above 2048, a prime factor above 5) is a null return whose message states the rule and the nearest accepted
  * lengths below and above; so is any other flag bit (the message names `flags`).  add, add_detector, get_partial, merge and finalize
- * take either kind of handle. */
+ * take either kind of handle.
+ * MTIP_CORRELATE_ANY_NPHI (alone or with the bit above: the same): n_phi is any even length in 16 .. 2048, the ring pixel counts of
+ * phi_range's 'max' and 'min' modes among them (1256 = 2^3 157, 1030 = 2 5 103 ..).  A power of two up to 1024 and a length with
+ * prime factors 2, 3, 5 only run the kernels and give the bits of the handles above; every other length runs chirp-z (Bluestein)
+ * transforms: a circular convolution of the smallest 2-3-5-smooth length >= n_phi - 1 by the same mixed-radix stages, its tables
+ * made once per handle.  Refused, with the rule and the value in the message, before anything is allocated: an odd length, one
+ * below 16 or above 2048.  Partial results merge between handles of one shape whatever their kind. */
 #define MTIP_CORRELATE_GENERAL_NPHI 1u
+#define MTIP_CORRELATE_ANY_NPHI 4u
 mtip_correlate* mtip_correlate_create_ex(mtip_ctx* ctx, const mtip_correlate_cfg* cfg, const int32_t* q1_pos, const int32_t* q2_pos,
                                          const double* factor, uint32_t flags);
 void mtip_correlate_destroy(mtip_correlate* h);

@@ -5,7 +5,7 @@ in a synchronise; five windows after a warm-up: median, min .. max), and inside 
 families corr_ring (k_corr_stats + k_corr_ring) and corr_pair (k_corr_pair).  Derived, with the counts stated where they are printed:
 the achieved FFT rate of k_corr_pair against the fp64 vector peak, and the accumulator bytes per pattern against HBM.
 The numpy restatement of the route (tests/correlate_cases.r_correlate) on this host with 1 and with 8 processes, as context.
-usage: python scripts/bench_correlate.py [--small] [--n-phi N [--rings R]] [--filter KIND] [--batch B]
+usage: python scripts/bench_correlate.py [--small] [--n-phi N [--rings R]] [--any-n-phi] [--filter KIND] [--batch B]
   --small       the small shape only
   --filter KIND the radial pixel filter: none (default), average_sigma (k_corr_stats) or median_mad (k_corr_stats_mad,
                 csrc/k_ringfilter.h; Correlator(..., median_mad=True)), each at 3 sigmas / MADs.  With a filter 4 % of the samples are
@@ -14,7 +14,10 @@ usage: python scripts/bench_correlate.py [--small] [--n-phi N [--rings R]] [--fi
   --batch B     that batch size only
   --n-phi N     one shape only: R rings (default 256) x N angles.  A length the radix-2 kernels do not take (1536, the default settings'
                 length, 1920, 2000, 2048 ..) goes through a handle made with general_n_phi=True (k_corr_pair_g, csrc/k_correlate_mr.h);
-                the operation count 5 m log2 m is kept for it as the convention the rates are stated in."""
+                the operation count 5 m log2 m is kept for it as the convention the rates are stated in.
+  --any-n-phi   the handles are made with any_n_phi=True: every even N in 16 .. 2048; a length with a prime factor above 5 (1256, 2042 ..)
+                runs the chirp-z kernels (k_corr_pair_b, csrc/k_correlate_bs.h), every other length the kernels it runs without the
+                switch.  The FFT rate is still stated in 5 m log2 m per transform, not in the convolution's own operations."""
 import multiprocessing as mp
 import os
 import sys
@@ -96,24 +99,26 @@ def main():
     if filt not in FILTERS:
         raise SystemExit('--filter takes one of ' + ', '.join(FILTERS))
     batches = (int(sys.argv[sys.argv.index('--batch') + 1]),) if '--batch' in sys.argv else BATCHES
+    any_n_phi = '--any-n-phi' in sys.argv
     if '--n-phi' in sys.argv:
         rings = int(sys.argv[sys.argv.index('--rings') + 1]) if '--rings' in sys.argv else 256
         shapes = ((rings, int(sys.argv[sys.argv.index('--n-phi') + 1])),)
     for n_q, n_phi in shapes:
         settings = settings_for(n_q, n_phi, filt)
-        general = n_phi not in CR.SUPPORTED_N_PHI
+        general = n_phi not in CR.SUPPORTED_N_PHI and not any_n_phi
+        route = ' (any_n_phi)' if any_n_phi else ' (general_n_phi: mixed-radix kernels)' if general else ''
         images, masks = patterns(n_q, n_phi, max(batches), outliers=filt != 'none')
         d_img = torch.from_numpy(images).cuda()
         d_mask = torch.from_numpy(masks).cuda()
         n_acc = n_q * n_q * n_phi
         print('%d rings x %d angles%s, %d x %d pairs: accumulator %.1f MB (sum f64 + count int32), shared-mask table %.1f MB' %
-              (n_q, n_phi, ' (general_n_phi: mixed-radix kernels)' if general else '', n_q, n_q, 12e-6 * n_acc, 8e-6 * n_acc))
+              (n_q, n_phi, route, n_q, n_q, 12e-6 * n_acc, 8e-6 * n_acc))
         if filt != 'none':
             print('  intensity_radial_pixel_filter: %s, 3' % filt)
         for shared in ((True, False) if filt == 'none' else (False,)):
             per_pattern = {}
             for B in batches:
-                c = CR.Correlator(e, settings, shared_mask=shared, general_n_phi=general, median_mad=filt == 'median_mad')
+                c = CR.Correlator(e, settings, shared_mask=shared, general_n_phi=general, any_n_phi=any_n_phi, median_mad=filt == 'median_mad')
                 m = d_mask[0] if shared else d_mask[:B]
                 t0 = time.perf_counter()
                 c.add(d_img[:B], m)                                    # warm-up (code objects, the shared mask's table)

@@ -22,7 +22,13 @@
 // registers across the chunk, the transform in a wave-private piece of LDS with no workgroup barrier in the pattern loop; rows of
 // 64 lanes may be partial (n_phi / 2 need not be a multiple of 64, nor even), its LDS is dynamic (49 n_phi bytes: 98 KB at 2048).
 // Such a handle with a power of two up to 1024 launches the radix-2 kernels.  Still refused: odd lengths, lengths below 16 or
-// above 2048, prime factors above 5.
+// above 2048, prime factors above 5.  A handle made with MTIP_CORRELATE_ANY_NPHI takes those prime factors too, every even n_phi in
+// 16 .. 2048: k_corr_ring_b / k_corr_pair_b / k_corr_final_b are the same bodies again with the chirp-z (Bluestein) transform of
+// k_correlate_bs.h, a circular convolution of Mc >= n_phi - 1 points (Mc the smallest 2-3-5-smooth length) by the mixed-radix stages.
+// The route follows from n_phi alone: a power of two up to 1024 launches the radix-2 kernels, a 2-3-5-smooth length the _g kernels,
+// anything else the _b kernels (n_phi is smooth exactly when n_phi / 2 is, so one test serves all three).  The pair kernel keeps
+// its shape there as well; a wave's buffer is Mc points, its LDS 80 Mc bytes (all 160 KB of a compute unit at Mc = 2048), and the
+// read-only tables a transform touches once per point (chirp, B, the fold's twiddles) are read from global memory.
 //
 // THE ONE DEVIATION from the reference: it tests M != 0 on a value that is an integer pair count plus FFT rounding, and so divides
 // noise by noise where the true count is 0 without a whole ring being masked.  Here the test is |M| >= 0.5: masks are 0 / 1, M is an
@@ -42,6 +48,11 @@
 #define COR_MODE_MASK_ONLY 2           // fill that table
 
 #include "k_correlate_mr.h"
+#include "k_correlate_bs.h"
+
+#define COR_XF_R2 0                    // the transform of a kernel body: radix 2,
+#define COR_XF_MR 1                    // the handle's mixed-radix plan (k_correlate_mr.h),
+#define COR_XF_BS 2                    // or its chirp-z convolution (k_correlate_bs.h)
 
 struct mtip_correlate {
     mtip_ctx* c = nullptr;
@@ -50,6 +61,9 @@ struct mtip_correlate {
     bool general = false;              // the mixed-radix kernels (create_ex with MTIP_CORRELATE_GENERAL_NPHI, n_phi not 16, 32, .. 1024)
     CorPlanArgs pl_n{}, pl_m{};        // their plans for n_phi and for n_phi / 2 points
     DevBuf<uint16_t> d_perm;           // the two digit-reversal tables: n_phi entries, then n_phi / 2
+    bool bluestein = false;            // the chirp-z kernels (create_ex with MTIP_CORRELATE_ANY_NPHI, n_phi / 2 has a prime factor above 5)
+    CorBsArgs bs{};                    // their plan for n_phi / 2 points
+    DevBuf<double2> d_bs;              // its tables: Mc twiddles, B (Mc), the chirp (n_phi / 2)
     size_t n_acc = 0;                  // n_q1 n_q2 n_phi
     DevBuf<double> d_sum;
     DevBuf<int> d_cnt;
@@ -158,21 +172,31 @@ __global__ void __launch_bounds__(COR_RT) k_corr_stats(CorRingArgs a) {
 
 #include "k_ringfilter.h"
 
-// where input point j of an n_phi-point transform is stored, and that transform: radix 2, or the handle's mixed-radix plan
-template <bool GEN>
-__device__ __forceinline__ int cor_store_pos(const CorPlanArgs* pl, int j, int log2n) {
-    if constexpr (GEN) return pl->perm[j];
-    else return cor_brev((unsigned)j, log2n);
+// sample j of a real row of n_phi points on its way into the transform, that transform, and point k of its spectrum: radix 2 or the
+// handle's mixed-radix plan (the sample at its bit- or digit-reversed place, an n_phi-point transform), or the chirp-z convolution
+// (sample j is part j & 1 of point j / 2 of an n_phi / 2-point transform, whose spectrum cor_bs_unfold takes apart)
+template <int XF>
+__device__ __forceinline__ void cor_store_sample(const CorPlanArgs* pl, double2* buf, int j, int log2n, double v) {
+    if constexpr (XF == COR_XF_BS) ((double*)buf)[j] = v;
+    else if constexpr (XF == COR_XF_MR) buf[pl->perm[j]] = make_double2(v, 0.0);
+    else buf[cor_brev((unsigned)j, log2n)] = make_double2(v, 0.0);
 }
-template <bool GEN>
-__device__ __forceinline__ void cor_ring_fft(const CorPlanArgs* pl, double2* buf, int n, int log2n, const double2* tw, int tid) {
-    if constexpr (GEN) cor_block_fft_g(buf, pl->st, tw, tid, COR_RT);
+template <int XF>
+__device__ __forceinline__ void cor_ring_fft(const CorPlanArgs* pl, const CorBsArgs* bs, double2* buf, int n, int log2n, const double2* tw,
+                                             int tid) {
+    if constexpr (XF == COR_XF_BS) cor_block_fft_b(buf, n >> 1, *bs, tid, COR_RT);
+    else if constexpr (XF == COR_XF_MR) cor_block_fft_g(buf, pl->st, tw, tid, COR_RT);
     else cor_block_fft(buf, n, log2n, tw, tid);
+}
+template <int XF>
+__device__ __forceinline__ double2 cor_spectrum(const double2* buf, const double2* tw, int n, int k) {
+    if constexpr (XF == COR_XF_BS) return cor_bs_unfold(buf, tw, n >> 1, k);
+    else return buf[k];
 }
 
 // correlate.py:416-450 for one ring of one pattern, then rfft of the image and of the mask along phi
-template <bool GEN>
-__device__ __forceinline__ void cor_ring_body(const CorRingArgs a, const CorPlanArgs* pl, double2* s_buf, double* s_red) {
+template <int XF>
+__device__ __forceinline__ void cor_ring_body(const CorRingArgs a, const CorPlanArgs* pl, const CorBsArgs* bs, double2* s_buf, double* s_red) {
     const int tid = threadIdx.x, q = blockIdx.x, p = blockIdx.y, m = a.n_phi >> 1;
     const uint8_t* mrow = a.filter ? a.mw + ((size_t)p * a.n_q + q) * a.n_phi : a.mask + (size_t)p * a.mask_stride + (size_t)q * a.n_phi;
     if (a.img != nullptr) {
@@ -209,7 +233,7 @@ __device__ __forceinline__ void cor_ring_body(const CorRingArgs a, const CorPlan
             if (a.roi_norm) v = v / roi_mean;                           // 431-432
             if (frow) v *= frow[j];                                     // 434-438
             if (mrow[j]) ws += v;
-            s_buf[cor_store_pos<GEN>(pl, j, a.log2n)] = make_double2(v, 0.0);
+            cor_store_sample<XF>(pl, s_buf, j, a.log2n, v);
         }
         ws = cor_block_sum(ws, s_red, tid);
         if (tid == 0) {
@@ -217,27 +241,33 @@ __device__ __forceinline__ void cor_ring_body(const CorRingArgs a, const CorPlan
             if (q == 0) a.good[p] = good;
         }
         if (!good) return;                                              // the pair kernel skips the pattern
-        cor_ring_fft<GEN>(pl, s_buf, a.n_phi, a.log2n, a.tw, tid);
+        cor_ring_fft<XF>(pl, bs, s_buf, a.n_phi, a.log2n, a.tw, tid);
         double2* F = a.F + ((size_t)p * a.n_q + q) * (m + 1);
-        for (int k = tid; k <= m; k += COR_RT) F[k] = s_buf[k];
+        for (int k = tid; k <= m; k += COR_RT) F[k] = cor_spectrum<XF>(s_buf, a.tw, a.n_phi, k);
         __syncthreads();
     }
     if (a.do_G) {
-        for (int j = tid; j < a.n_phi; j += COR_RT) s_buf[cor_store_pos<GEN>(pl, j, a.log2n)] = make_double2(mrow[j] ? 1.0 : 0.0, 0.0);
-        cor_ring_fft<GEN>(pl, s_buf, a.n_phi, a.log2n, a.tw, tid);
+        for (int j = tid; j < a.n_phi; j += COR_RT) cor_store_sample<XF>(pl, s_buf, j, a.log2n, mrow[j] ? 1.0 : 0.0);
+        cor_ring_fft<XF>(pl, bs, s_buf, a.n_phi, a.log2n, a.tw, tid);
         double2* G = a.G + ((size_t)p * a.n_q + q) * (m + 1);
-        for (int k = tid; k <= m; k += COR_RT) G[k] = s_buf[k];
+        for (int k = tid; k <= m; k += COR_RT) G[k] = cor_spectrum<XF>(s_buf, a.tw, a.n_phi, k);
     }
 }
 __global__ void __launch_bounds__(COR_RT) k_corr_ring(CorRingArgs a) {
     __shared__ double2 s_buf[COR_MAX_NPHI];
     __shared__ double s_red[COR_WAVES];
-    cor_ring_body<false>(a, nullptr, s_buf, s_red);
+    cor_ring_body<COR_XF_R2>(a, nullptr, nullptr, s_buf, s_red);
 }
 __global__ void __launch_bounds__(COR_RT) k_corr_ring_g(CorRingArgs a, CorPlanArgs pl) {
     __shared__ double2 s_buf[COR_G_MAX_NPHI];
     __shared__ double s_red[COR_WAVES];
-    cor_ring_body<true>(a, &pl, s_buf, s_red);
+    cor_ring_body<COR_XF_MR>(a, &pl, nullptr, s_buf, s_red);
+}
+// (s_buf: the Mc <= 2048 points of the convolution)
+__global__ void __launch_bounds__(COR_RT) k_corr_ring_b(CorRingArgs a, CorBsArgs bs) {
+    __shared__ double2 s_buf[COR_G_MAX_NPHI];
+    __shared__ double s_red[COR_WAVES];
+    cor_ring_body<COR_XF_BS>(a, nullptr, &bs, s_buf, s_red);
 }
 
 struct CorPairArgs {
@@ -298,22 +328,32 @@ __device__ __forceinline__ void cor_wave_irfft(double2* buf, const double2* s_tw
     MTIP_WAVE_LDS_SYNC();
 }
 
-// NPL: rows of 64 lanes that hold the m points of a pair (the last one may be partial).  GEN: s_tw has n_phi entries, s_perm the
-// plan's digit reversal of m points
-template <int NPL, bool GEN>
+// NPL: rows of 64 lanes that hold the m points of a pair (the last one may be partial).  COR_XF_MR: s_tw has n_phi entries, s_perm the
+// plan's digit reversal of m points.  COR_XF_BS: s_tw has the Mc twiddles of the convolution, a wave's buffer Mc points; the
+// read-only tables that are touched once per point (a.tw, the chirp, B) stay in global memory
+template <int NPL, int XF>
 __device__ __forceinline__ void cor_pair_irfft(double2* buf, const double2* s_tw, const uint16_t* s_perm, const CorPlanArgs* pl,
-                                               const double2* a1, const double2* a2, int m, int log2m, int lane, double* out) {
-    if constexpr (GEN) cor_wave_irfft_g<NPL>(buf, s_tw, s_perm, pl->st, a1, a2, m, lane, out);
+                                               const CorBsArgs* bs, const double2* tw_n, const double2* a1, const double2* a2, int m,
+                                               int log2m, int lane, double* out) {
+    if constexpr (XF == COR_XF_BS) cor_wave_irfft_b<NPL>(buf, s_tw, tw_n, *bs, a1, a2, m, lane, out);
+    else if constexpr (XF == COR_XF_MR) cor_wave_irfft_g<NPL>(buf, s_tw, s_perm, pl->st, a1, a2, m, lane, out);
     else cor_wave_irfft<NPL>(buf, s_tw, a1, a2, m, log2m, lane, out);
 }
-template <int NPL, bool GEN>
-__device__ __forceinline__ void cor_pair_body(const CorPairArgs a, const CorPlanArgs* pl, double2* s_fft, double2* s_tw, uint16_t* s_perm) {
+template <int NPL, int XF>
+__device__ __forceinline__ void cor_pair_body(const CorPairArgs a, const CorPlanArgs* pl, const CorBsArgs* bs, double2* s_fft, double2* s_tw,
+                                              uint16_t* s_perm) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), m = a.m;
-    for (int k = tid; k < (GEN ? 2 * m : m); k += COR_WAVES * 64) s_tw[k] = a.tw[k];
-    if constexpr (GEN)
+    if constexpr (XF == COR_XF_BS) {
+        for (int k = tid; k < bs->Mc; k += COR_WAVES * 64) s_tw[k] = bs->tw[k];
+    } else {
+        for (int k = tid; k < (XF == COR_XF_MR ? 2 * m : m); k += COR_WAVES * 64) s_tw[k] = a.tw[k];
+    }
+    if constexpr (XF == COR_XF_MR)
         for (int k = tid; k < m; k += COR_WAVES * 64) s_perm[k] = pl->perm[k];
     __syncthreads();
-    double2* buf = s_fft + wave * m;
+    double2* buf;
+    if constexpr (XF == COR_XF_BS) buf = s_fft + wave * bs->Mc;
+    else buf = s_fft + wave * m;
     const size_t row_len = (size_t)(m + 1), pat_len = (size_t)a.n_q * row_len;
     for (long long base = (long long)blockIdx.x * COR_WAVES; base < a.npairs; base += (long long)gridDim.x * COR_WAVES) {
         const long long pair = base + wave;
@@ -326,7 +366,7 @@ __device__ __forceinline__ void cor_pair_body(const CorPairArgs a, const CorPlan
         double sum[2 * NPL], d[2 * NPL], mm[2 * NPL];
         int cnt[2 * NPL];
         if (a.mode == COR_MODE_MASK_ONLY) {
-            cor_pair_irfft<NPL, GEN>(buf, s_tw, s_perm, pl, a.G + r1, a.G + r2, m, a.log2m, lane, mm);
+            cor_pair_irfft<NPL, XF>(buf, s_tw, s_perm, pl, bs, a.tw, a.G + r1, a.G + r2, m, a.log2m, lane, mm);
 #pragma unroll
             for (int r = 0; r < NPL; ++r) {
                 const int j = lane + 64 * r;
@@ -353,10 +393,10 @@ __device__ __forceinline__ void cor_pair_body(const CorPairArgs a, const CorPlan
         for (int p = 0; p < a.P; ++p) {
             if (!a.good[p]) continue;                                   // bad patterns contribute nothing (correlate.py:347)
             const double2* Fp = a.F + (size_t)p * pat_len;
-            cor_pair_irfft<NPL, GEN>(buf, s_tw, s_perm, pl, Fp + r1, Fp + r2, m, a.log2m, lane, d);
+            cor_pair_irfft<NPL, XF>(buf, s_tw, s_perm, pl, bs, a.tw, Fp + r1, Fp + r2, m, a.log2m, lane, d);
             if (a.mode == COR_MODE_PATTERN) {
                 const double2* Gp = a.G + (size_t)p * pat_len;
-                cor_pair_irfft<NPL, GEN>(buf, s_tw, s_perm, pl, Gp + r1, Gp + r2, m, a.log2m, lane, mm);
+                cor_pair_irfft<NPL, XF>(buf, s_tw, s_perm, pl, bs, a.tw, Gp + r1, Gp + r2, m, a.log2m, lane, mm);
 #pragma unroll
                 for (int e = 0; e < 2 * NPL; ++e) mm[e] *= a.inv_n;
             }
@@ -381,16 +421,24 @@ template <int NPL>
 __global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair(CorPairArgs a) {
     __shared__ double2 s_fft[COR_WAVES * (COR_MAX_NPHI / 2)];
     __shared__ double2 s_tw[COR_MAX_NPHI / 2];
-    cor_pair_body<NPL, false>(a, nullptr, s_fft, s_tw, nullptr);
+    cor_pair_body<NPL, COR_XF_R2>(a, nullptr, nullptr, s_fft, s_tw, nullptr);
 }
 // dynamic LDS: twiddles (n_phi), COR_WAVES wave-private transforms (m each), the digit reversal (m uint16): cor_pair_lds bytes.  Four
 // waves are one per SIMD, so the 16 rows of n_phi = 2048 (64 accumulator doubles and 32 counts per lane) have the whole register file.
 template <int NPL>
 __global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair_g(CorPairArgs a, CorPlanArgs pl) {
     HIP_DYNAMIC_SHARED(double2, sm)
-    cor_pair_body<NPL, true>(a, &pl, sm + 2 * a.m, sm, (uint16_t*)(sm + (2 + COR_WAVES) * a.m));
+    cor_pair_body<NPL, COR_XF_MR>(a, &pl, nullptr, sm + 2 * a.m, sm, (uint16_t*)(sm + (2 + COR_WAVES) * a.m));
 }
 static inline size_t cor_pair_lds(int m) { return (size_t)(2 + COR_WAVES) * m * sizeof(double2) + (((size_t)m * sizeof(uint16_t) + 15) & ~(size_t)15); }
+// dynamic LDS: the Mc twiddles, then COR_WAVES wave-private convolutions of Mc points: cor_pair_lds_b bytes, 80 Mc (all 160 KB of a
+// compute unit at Mc = 2048, n_phi = 2018 .. 2046)
+template <int NPL>
+__global__ void __launch_bounds__(COR_WAVES * 64) k_corr_pair_b(CorPairArgs a, CorBsArgs bs) {
+    HIP_DYNAMIC_SHARED(double2, sm)
+    cor_pair_body<NPL, COR_XF_BS>(a, nullptr, &bs, sm + bs.Mc, sm, nullptr);
+}
+static inline size_t cor_pair_lds_b(int Mc) { return (size_t)(1 + COR_WAVES) * Mc * sizeof(double2); }
 
 __global__ void k_corr_merge(double* sum, int* cnt, const double* sum_in, const int* cnt_in, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -409,8 +457,8 @@ struct CorFinalArgs {
 };
 
 // correlate.py:258-270: sum / count with NaN where nothing was counted, symmetrize_ccf (cross_correlation.py:67-78), fft[..., :fc_n]
-template <bool GEN>
-__device__ __forceinline__ void cor_final_body(const CorFinalArgs& a, const CorPlanArgs* pl, double2* s_buf) {
+template <int XF>
+__device__ __forceinline__ void cor_final_body(const CorFinalArgs& a, const CorPlanArgs* pl, const CorBsArgs* bs, double2* s_buf) {
     const int tid = threadIdx.x;
     const size_t row = (size_t)blockIdx.x * a.n_phi;
     for (int j = tid; j < a.n_phi; j += COR_RT) {
@@ -422,19 +470,23 @@ __device__ __forceinline__ void cor_final_body(const CorFinalArgs& a, const CorP
         const int n = a.cnt[row + src];
         const double v = n != 0 ? a.sum[row + src] / (double)n : __builtin_nan("");
         if (a.ccf) a.ccf[row + j] = v;
-        s_buf[cor_store_pos<GEN>(pl, j, a.log2n)] = make_double2(v, 0.0);
+        cor_store_sample<XF>(pl, s_buf, j, a.log2n, v);
     }
     if (a.fc == nullptr) return;
-    cor_ring_fft<GEN>(pl, s_buf, a.n_phi, a.log2n, a.tw, tid);
-    for (int k = tid; k < a.fc_n; k += COR_RT) a.fc[(size_t)blockIdx.x * a.fc_n + k] = s_buf[k];
+    cor_ring_fft<XF>(pl, bs, s_buf, a.n_phi, a.log2n, a.tw, tid);
+    for (int k = tid; k < a.fc_n; k += COR_RT) a.fc[(size_t)blockIdx.x * a.fc_n + k] = cor_spectrum<XF>(s_buf, a.tw, a.n_phi, k);
 }
 __global__ void __launch_bounds__(COR_RT) k_corr_final(CorFinalArgs a) {
     __shared__ double2 s_buf[COR_MAX_NPHI];
-    cor_final_body<false>(a, nullptr, s_buf);
+    cor_final_body<COR_XF_R2>(a, nullptr, nullptr, s_buf);
 }
 __global__ void __launch_bounds__(COR_RT) k_corr_final_g(CorFinalArgs a, CorPlanArgs pl) {
     __shared__ double2 s_buf[COR_G_MAX_NPHI];
-    cor_final_body<true>(a, &pl, s_buf);
+    cor_final_body<COR_XF_MR>(a, &pl, nullptr, s_buf);
+}
+__global__ void __launch_bounds__(COR_RT) k_corr_final_b(CorFinalArgs a, CorBsArgs bs) {
+    __shared__ double2 s_buf[COR_G_MAX_NPHI];
+    cor_final_body<COR_XF_BS>(a, nullptr, &bs, s_buf);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
@@ -458,19 +510,29 @@ extern "C" mtip_correlate* mtip_correlate_create_ex(mtip_ctx* c, const mtip_corr
         c->err = "correlate_create: null argument or a ring count outside 1 .. 65535";
         return nullptr;
     }
-    if (flags & ~(uint32_t)MTIP_CORRELATE_GENERAL_NPHI) {
-        snprintf(msg, sizeof msg, "correlate_create_ex: flags = 0x%x: only MTIP_CORRELATE_GENERAL_NPHI (bit 0) is defined", (unsigned)flags);
+    if (flags & ~(uint32_t)(MTIP_CORRELATE_GENERAL_NPHI | MTIP_CORRELATE_ANY_NPHI)) {
+        snprintf(msg, sizeof msg,
+                 "correlate_create_ex: flags = 0x%x: only MTIP_CORRELATE_GENERAL_NPHI (bit 0) and MTIP_CORRELATE_ANY_NPHI (bit 2) are defined",
+                 (unsigned)flags);
         c->err = msg;
         return nullptr;
     }
     const int n = cfg->n_phi;
     const bool radix2 = n >= COR_MIN_NPHI && n <= COR_MAX_NPHI && !(n & (n - 1));
-    if (!(flags & MTIP_CORRELATE_GENERAL_NPHI) && !radix2) {
+    const bool any = (flags & MTIP_CORRELATE_ANY_NPHI) != 0;
+    if (any && !cor_any_ok(n)) {
+        snprintf(msg, sizeof msg, "correlate_create: n_phi = %d is not built; with MTIP_CORRELATE_ANY_NPHI: every even length %d .. %d", n,
+                 COR_MIN_NPHI, COR_G_MAX_NPHI);
+        c->err = msg;
+        return nullptr;
+    }
+    const bool bluestein = any && !radix2 && !cor_general_ok(n);       // (n is smooth exactly when n / 2 is)
+    if (!any && !(flags & MTIP_CORRELATE_GENERAL_NPHI) && !radix2) {
         snprintf(msg, sizeof msg, "correlate_create: n_phi = %d is not built; supported: 16, 32, 64, 128, 256, 512, 1024", n);
         c->err = msg;
         return nullptr;
     }
-    if (!radix2 && !cor_general_ok(n)) {
+    if (!any && !radix2 && !cor_general_ok(n)) {
         int below, above;
         char lo[16] = "none", hi[16] = "none";
         cor_general_near(n, &below, &above);
@@ -508,7 +570,11 @@ extern "C" mtip_correlate* mtip_correlate_create_ex(mtip_ctx* c, const mtip_corr
     const size_t rows = (size_t)COR_CHUNK * cfg->n_q, n_spec = rows * (h->m + 1), spec = n_spec * sizeof(double2);
     const size_t acc = h->n_acc * 12, tab = shared ? h->n_acc * 8 : 0;
     // (a mixed-radix handle's plan: twiddles of n_phi entries, digit reversals of n_phi and of n_phi / 2 points)
-    const size_t plan = radix2 ? 0 : (size_t)n * sizeof(double2) + ((size_t)n + h->m) * sizeof(uint16_t);
+    // (a chirp-z handle's: twiddles of n_phi entries, and of the convolution's Mc; B; the chirp)
+    const int Mc = bluestein ? cor_bs_length(h->m) : 0;
+    const size_t plan = radix2      ? 0
+                        : bluestein ? ((size_t)n + 2 * (size_t)Mc + h->m) * sizeof(double2)
+                                    : (size_t)n * sizeof(double2) + ((size_t)n + h->m) * sizeof(uint16_t);
     const size_t work = spec * (shared ? 1 : 2) + spec / COR_CHUNK + rows * n + rows * 16 + (factor ? (size_t)cfg->n_q * n * 8 : 0) + plan;
     const size_t fr = mtip_free_memory();
     if (acc + tab + work > fr) {
@@ -521,8 +587,9 @@ extern "C" mtip_correlate* mtip_correlate_create_ex(mtip_ctx* c, const mtip_corr
         delete h;
         return nullptr;
     }
-    h->general = !radix2;
-    std::vector<double2> tw((size_t)(h->general ? n : h->m));
+    h->general = !radix2 && !bluestein;
+    h->bluestein = bluestein;
+    std::vector<double2> tw((size_t)(radix2 ? h->m : n));
     for (int k = 0; k < (int)tw.size(); ++k) {
         const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
         tw[k] = make_double2((double)cosl(ang), (double)sinl(ang));
@@ -535,7 +602,21 @@ extern "C" mtip_correlate* mtip_correlate_create_ex(mtip_ctx* c, const mtip_corr
         cor_make_perm(h->pl_n.st, n, perm.data());
         cor_make_perm(h->pl_m.st, h->m, perm.data() + n);
     }
+    std::vector<double2> bst;
+    if (bluestein) {                                                    // the plan of the convolution and its tables
+        h->bs.Mc = Mc;
+        h->bs.st = cor_make_stages(Mc, Mc);
+        bst.resize(2 * (size_t)Mc + h->m);
+        cor_bs_tables(h->m, Mc, h->bs.st, bst.data(), bst.data() + Mc, bst.data() + 2 * (size_t)Mc);
+    }
     hipError_t e = h->d_sum.alloc(h->n_acc);
+    if (e == hipSuccess && bluestein) e = h->d_bs.alloc(bst.size());
+    if (e == hipSuccess && bluestein) e = mtip_copy(c, h->d_bs, bst.data(), bst.size() * sizeof(double2), hipMemcpyHostToDevice);
+    if (e == hipSuccess && bluestein) {
+        h->bs.tw = h->d_bs;
+        h->bs.B = h->d_bs + Mc;
+        h->bs.chirp = h->d_bs + 2 * (size_t)Mc;
+    }
     if (e == hipSuccess && h->general) e = h->d_perm.alloc(perm.size());
     if (e == hipSuccess && h->general) e = mtip_copy(c, h->d_perm, perm.data(), perm.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && h->general) {
@@ -582,7 +663,8 @@ extern "C" void mtip_correlate_destroy(mtip_correlate* h) {
 
 static inline void cor_launch_ring(mtip_correlate* h, unsigned n_patterns, const CorRingArgs& r) {
     const dim3 g((unsigned)h->cfg.n_q, n_patterns), b(COR_RT);
-    if (h->general) hipLaunchKernelGGL(k_corr_ring_g, g, b, 0, h->c->stream, r, h->pl_n);
+    if (h->bluestein) hipLaunchKernelGGL(k_corr_ring_b, g, b, 0, h->c->stream, r, h->bs);
+    else if (h->general) hipLaunchKernelGGL(k_corr_ring_g, g, b, 0, h->c->stream, r, h->pl_n);
     else hipLaunchKernelGGL(k_corr_ring, g, b, 0, h->c->stream, r);
 }
 
@@ -590,6 +672,17 @@ static inline void cor_launch_pair(mtip_correlate* h, const CorPairArgs& a) {
     mtip_ctx* c = h->c;
     const unsigned grid = (unsigned)std::min<long long>(div_up(a.npairs, COR_WAVES), (long long)c->n_cu * 8);
     const dim3 g(grid), b(COR_WAVES * 64);
+    if (h->bluestein) {
+        const int rows = div_up(a.m, 64);
+        const size_t lds = cor_pair_lds_b(h->bs.Mc);
+        if (rows <= 1) hipLaunchKernelGGL(k_corr_pair_b<1>, g, b, lds, c->stream, a, h->bs);
+        else if (rows <= 2) hipLaunchKernelGGL(k_corr_pair_b<2>, g, b, lds, c->stream, a, h->bs);
+        else if (rows <= 4) hipLaunchKernelGGL(k_corr_pair_b<4>, g, b, lds, c->stream, a, h->bs);
+        else if (rows <= 8) hipLaunchKernelGGL(k_corr_pair_b<8>, g, b, lds, c->stream, a, h->bs);
+        else if (rows <= 12) hipLaunchKernelGGL(k_corr_pair_b<12>, g, b, lds, c->stream, a, h->bs);
+        else hipLaunchKernelGGL(k_corr_pair_b<16>, g, b, lds, c->stream, a, h->bs);
+        return;
+    }
     if (h->general) {
         const int rows = div_up(a.m, 64);
         const size_t lds = cor_pair_lds(a.m);
@@ -803,7 +896,8 @@ extern "C" int mtip_correlate_finalize(mtip_correlate* h, int symmetrize, int po
         a.pos_3pi2 = pos_3pi2;
         a.fc_n = fc ? fc_n_max : 0;
         ProfScope ps(c, "corr_final");
-        if (h->general) hipLaunchKernelGGL(k_corr_final_g, dim3((unsigned)pairs), dim3(COR_RT), 0, c->stream, a, h->pl_n);
+        if (h->bluestein) hipLaunchKernelGGL(k_corr_final_b, dim3((unsigned)pairs), dim3(COR_RT), 0, c->stream, a, h->bs);
+        else if (h->general) hipLaunchKernelGGL(k_corr_final_g, dim3((unsigned)pairs), dim3(COR_RT), 0, c->stream, a, h->pl_n);
         else hipLaunchKernelGGL(k_corr_final, dim3((unsigned)pairs), dim3(COR_RT), 0, c->stream, a);
         e = hipGetLastError();
     }

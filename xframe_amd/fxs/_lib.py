@@ -27,6 +27,7 @@ class MtipCfg(C.Structure):
 
 
 MTIP_CORRELATE_GENERAL_NPHI = 1   # mtip_correlate_create_ex flags bit 0: every even 5-smooth n_phi in 16 .. 2048
+MTIP_CORRELATE_ANY_NPHI = 4       # bit 2: every even n_phi in 16 .. 2048 (chirp-z transforms where n_phi has a prime factor above 5)
 MTIP_CFG_LOOP_BIG_L = 1          # MtipCfg.reserved bit 0 (include/mtip_hip.h): the phasing loop and the projection beyond L = 63
 
 

@@ -44,6 +44,15 @@ def general_n_phi_ok(n):
     return n == 1
 
 
+def any_n_phi_ok(n):
+    """n_phi a ``Correlator`` made with any_n_phi=True takes: every even length in 16 .. 2048"""
+    n = int(n)
+    return GENERAL_N_PHI_MIN <= n <= GENERAL_N_PHI_MAX and n % 2 == 0
+
+
+ANY_N_PHI_HINT = ' (any_n_phi=True takes this length: every even one in 16 .. 2048)'
+
+
 def general_n_phi_near(n):
     """(below, above): the nearest lengths general_n_phi=True takes on either side of n (None: there is none), e.g. to pick the
     n_phi of phi_range where its 'max' / 'min' mode would give the ring's pixel count"""
@@ -318,10 +327,15 @@ class Correlator:
     prime factors are 2, 3 and 5 -- the default settings' 1536 among them -- through ``mtip_correlate_create_ex``; without it the
     lengths are SUPPORTED_N_PHI.  ``general_n_phi_near`` names the nearest such lengths.
 
+    any_n_phi=True (None: settings['GPU']['any_n_phi'], default False): n_phi may be any even length in 16 .. 2048 (``any_n_phi_ok``),
+    as phi_range's 'max' and 'min' modes make them from the outermost ring's pixel count.  The lengths above run the same kernels
+    and give the same bits as without it; a length with a prime factor above 5 runs chirp-z transforms (``csrc/k_correlate_bs.h``).
+
     median_mad=True (None: settings['GPU']['median_mad'], default False): intensity_radial_pixel_filter [True, ['median_mad', k]] runs
     on the device (``csrc/k_ringfilter.h``: exact medians, numpy's and scipy's bit for bit); without it that setting raises."""
 
-    def __init__(self, engine, settings=None, shared_mask=False, binary_mask=None, background=None, general_n_phi=None, median_mad=None):
+    def __init__(self, engine, settings=None, shared_mask=False, binary_mask=None, background=None, general_n_phi=None, median_mad=None,
+                 any_n_phi=None):
         self.engine = engine
         self._frame_arrays = (binary_mask, background)
         self.resampler = None
@@ -333,14 +347,22 @@ class Correlator:
         if general_n_phi is None:
             general_n_phi = (opt.get('GPU') or {}).get('general_n_phi', False)
         self.general_n_phi = bool(general_n_phi)
-        if self.general_n_phi:
+        if any_n_phi is None:
+            any_n_phi = (opt.get('GPU') or {}).get('any_n_phi', False)
+        self.any_n_phi = bool(any_n_phi)
+        hint = ANY_N_PHI_HINT if any_n_phi_ok(self.n_phi) else ''
+        if self.any_n_phi:
+            if not any_n_phi_ok(self.n_phi):
+                raise NotImplementedError(f'correlate: n_phi = {self.n_phi} is not built; any_n_phi takes every even length '
+                                          f'{GENERAL_N_PHI_MIN} .. {GENERAL_N_PHI_MAX}')
+        elif self.general_n_phi:
             if not general_n_phi_ok(self.n_phi):
                 below, above = general_n_phi_near(self.n_phi)
                 raise NotImplementedError(f'correlate: n_phi = {self.n_phi} is not built; general_n_phi takes even lengths '
                                           f'{GENERAL_N_PHI_MIN} .. {GENERAL_N_PHI_MAX} whose only prime factors are 2, 3 and 5; the '
-                                          f'nearest below: {below}, above: {above}')
+                                          f'nearest below: {below}, above: {above}' + hint)
         elif self.n_phi not in SUPPORTED_N_PHI:
-            raise NotImplementedError(f'correlate: n_phi = {self.n_phi} is not built; supported lengths: {SUPPORTED_N_PHI}')
+            raise NotImplementedError(f'correlate: n_phi = {self.n_phi} is not built; supported lengths: {SUPPORTED_N_PHI}' + hint)
         filt = opt['intensity_radial_pixel_filter']
         self.filter = bool(filt[0])
         if median_mad is None:
@@ -376,8 +398,9 @@ class Correlator:
                                     1 if roi_f[0] else 0, 1 if roi_n[0] else 0, 1 if self.shared_mask else 0,
                                     float(filt[1][1]) if self.filter else 0.0, float(roi_f[1]), float(roi_f[2]))
         tables = (engine.ctx, C.byref(cfg), _lib.ptr(self.q1), _lib.ptr(self.q2), _lib.ptr(self.factor))
-        if self.general_n_phi:
-            self.handle = self.lib.mtip_correlate_create_ex(*tables, _lib.MTIP_CORRELATE_GENERAL_NPHI)
+        flags = (_lib.MTIP_CORRELATE_GENERAL_NPHI if self.general_n_phi else 0) | (_lib.MTIP_CORRELATE_ANY_NPHI if self.any_n_phi else 0)
+        if flags:
+            self.handle = self.lib.mtip_correlate_create_ex(*tables, flags)
         else:
             self.handle = self.lib.mtip_correlate_create(*tables)
         if not self.handle:

@@ -121,9 +121,11 @@ def correlate_default_settings():
     ``Resampler``, interpolation_order (0 .. 5) is the spline order of the polar resampling.  File lists and process splitting stay
     with the caller (``read_raw_images`` reads the frames).  GPU.general_n_phi (this project's key): ``Correlator`` takes every even
     n_phi in 16 .. 2048 with prime factors 2, 3, 5 -- the default's 1536 among them -- instead of the powers of two up to 1024.
-    GPU.median_mad (this project's key): ``Correlator`` takes intensity_radial_pixel_filter [True, ['median_mad', k]]."""
+    GPU.any_n_phi (this project's key): ``Correlator`` takes every even n_phi in 16 .. 2048, the ring pixel counts of phi_range's
+    'max' and 'min' modes among them.  GPU.median_mad (this project's key): ``Correlator`` takes intensity_radial_pixel_filter
+    [True, ['median_mad', k]]."""
     return {
-        'GPU': {'general_n_phi': False, 'median_mad': False},
+        'GPU': {'general_n_phi': False, 'any_n_phi': False, 'median_mad': False},
         'intensity_pixel_threshold': [False, 4.0, 1e4],
         'use_binary_mask': False,
         'subtract_background': False,
