@@ -107,6 +107,16 @@ int mtip_set_deg2_metric(mtip_ctx* ctx, int enable);
  * scalar: every type returns it); 1: the per-order values of deg2_invariant_l2_diff (one entry per used order, -1 where
  * the reference invariant vanishes).  Mixing both makes the reference itself raise (np.array of a scalar and a vector). */
 int mtip_set_main_error(mtip_ctx* ctx, int use_reciprocal_deg2, int type);
+/* the same routine over any of the metrics the loop records (fxs_IO_methods.py:753-760: the last values of main.metrics.real, then
+ * of main.metrics.reciprocal, each in the order the settings list them): items[n_items <= 8] = 0 real l2_projection_diff,
+ * 1 deg2_invariant_l2_diff (the per-order vector: the only item then, as the reference raises on a mix), 2 reciprocal
+ * l2_projection_diff, 3 II_error, 4 ccd_diff, 5 deg2_ranked_invariant_l2_diff = the entry of order deg2_ranked_column (0 .. L) of
+ * the deg2 metric (fxs_IO_methods.py:330-366).  Reduced as numpy does: mean = the sum in list order / n, and a NaN item makes every
+ * type NaN, which never becomes the best error (reconstruct.py:934).  A *_non_FXS step records no reciprocal value and reads
+ * the last FXS step's; while there is none -- none since mtip_init_state, or since one of the metrics was switched on -- the main
+ * error is -1 (762-764).  An item whose metric is off fails the run with MTIP_ESTATE before anything is launched.
+ * mtip_set_main_error(ctx, u, type) is items = {u ? 1 : 0}. */
+int mtip_set_main_error_ex(mtip_ctx* ctx, int type, int n_items, const int* items, int deg2_ranked_column);
 /* the non-default reciprocal metrics II_error / ccd_diff / fqc_error (fxs_IO_methods.py:587-627, 651-683, 507-550), evaluated in
  * every FXS step from B_l of the current intensity coefficients.  which: 1 | 2 | 4 (0 switches them off); zero_mask (L+1, Nq, Nq):
  * 1 = entry of B_l outside the invariant mask (zeroed); II: masked reference sum_{l>=1} B_l^ref (Nq, Nq), qq = (q q')^2;

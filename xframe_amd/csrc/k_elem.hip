@@ -89,12 +89,15 @@ __global__ void __launch_bounds__(256) k_real_update(RealUpdateArgs a) {
 // track the best pair (reconstruct.py:934-938) and rotate the pair slots.
 // main error (generate_main_error_routine, fxs_IO_methods.py:746-765): main_mode 0 = the real l2 metric itself (any
 // reduction of one value), 1 = mean / min / max / prod (main_type 0..3) over the per-order values of the reciprocal
-// deg2_invariant_l2_diff metric of this step (one entry per used order, -1 where the reference invariant vanishes).
+// deg2_invariant_l2_diff metric of this step (one entry per used order, -1 where the reference invariant vanishes),
+// 2 = numpy's mean / min / max / prod over the scalar metrics mi lists, in list order (MAIN_ITEM_*, mtip_set_main_error_ex): a NaN
+// item makes the result NaN for every type; the reciprocal ones are read from the rows of the last step that recorded them (this one
+// in an FXS step), and while none has (mi.n < 0) the main error is -1 (the reference's IndexError branch, fxs_IO_methods.py:762-764).
 __global__ void __launch_bounds__(256) k_finish_step(const double* __restrict__ partial, int nblk, int* __restrict__ slot,
                                                      double* __restrict__ best_err, double* __restrict__ last_err,
                                                      double* __restrict__ err_hist, int B, int update_slots, int main_mode,
                                                      int main_type, const double* __restrict__ deg2_step,
-                                                     const int* __restrict__ used, int L, double* __restrict__ main_hist) {
+                                                     const int* __restrict__ used, int L, double* __restrict__ main_hist, MainItems mi) {
     __shared__ double red0[256];
     __shared__ double red1[256];
     const int b = blockIdx.x;
@@ -131,6 +134,23 @@ __global__ void __launch_bounds__(256) k_finish_step(const double* __restrict__ 
                 ++cnt;
             }
             err = (main_type == 0) ? acc / (double)cnt : acc;
+            main_hist[b] = err;
+        } else if (main_mode == 2 && update_slots) {
+            double acc = -1.0;
+            for (int i = 0; i < mi.n; ++i) {
+                const int item = mi.items[i];
+                const double v = item == MAIN_ITEM_REAL_L2 ? real_err
+                               : item == MAIN_ITEM_RECIPROCAL_L2 ? mi.rl2[b]
+                               : item == MAIN_ITEM_II ? mi.im[b]
+                               : item == MAIN_ITEM_CCD ? mi.im[B + b]
+                               : mi.deg2[(size_t)b * (L + 1) + mi.ranked_col];
+                if (i == 0) acc = v;
+                else if (main_type == 0) acc += v;
+                else if (main_type == 1) acc = (v < acc || v != v) ? v : acc;
+                else if (main_type == 2) acc = (v > acc || v != v) ? v : acc;
+                else acc *= v;
+            }
+            err = (main_type == 0 && mi.n > 0) ? acc / (double)mi.n : acc;
             main_hist[b] = err;
         }
         if (update_slots) {
@@ -186,12 +206,29 @@ void launch_real_update(mtip_ctx* c, const double2* rho_p, const double2* prev, 
 void launch_finish_step(mtip_ctx* c, long long step_index, int nblk) {
     double* hist = step_index >= 0 ? c->d_err_hist + (size_t)step_index * c->B : c->d_op_err;
     const bool loop_step = step_index >= 0;
-    const int mode = (loop_step && c->main_mode == 1) ? 1 : 0;
+    const int mode = loop_step ? c->main_mode : 0;
+    MainItems mi{};
+    if (mode == 2) {
+        // the reciprocal items of a *_non_FXS step are those of the last FXS step of this reconstruction (errors[..][-1] upstream)
+        const long long row = c->last_fxs_step;
+        bool reciprocal = false;
+        for (int i = 0; i < c->main_n; ++i) {
+            mi.items[i] = c->main_items[i];
+            reciprocal = reciprocal || c->main_items[i] != MAIN_ITEM_REAL_L2;
+        }
+        mi.n = (reciprocal && row < 0) ? -1 : c->main_n;
+        mi.ranked_col = c->main_ranked_col;
+        if (reciprocal && row >= 0) {
+            mi.rl2 = c->d_rl2_hist ? c->d_rl2_hist + (size_t)row * c->B : nullptr;
+            mi.im = c->d_im_hist ? c->d_im_hist + (size_t)row * c->B * (2 + c->N) : nullptr;
+            mi.deg2 = c->d_deg2_hist + (size_t)row * c->B * (c->L + 1);
+        }
+    }
     hipLaunchKernelGGL(k_finish_step, dim3((unsigned)c->B), dim3(256), 0, c->stream, (const double*)c->d_partial,
                        nblk > 0 ? nblk : c->n_partial_blocks, c->d_slot, c->d_best_err, c->d_last_err, hist, c->B, loop_step ? 1 : 0,
                        mode, c->main_type,
-                       mode ? (const double*)(c->d_deg2_hist + (size_t)step_index * c->B * (c->L + 1)) : (const double*)nullptr,
-                       (const int*)c->d_used, c->L, mode ? c->d_main_hist + (size_t)step_index * c->B : (double*)nullptr);
+                       mode == 1 ? (const double*)(c->d_deg2_hist + (size_t)step_index * c->B * (c->L + 1)) : (const double*)nullptr,
+                       (const int*)c->d_used, c->L, mode ? c->d_main_hist + (size_t)step_index * c->B : (double*)nullptr, mi);
 }
 
 // ---- non-FXS variants: fixed = |F'| of the pair the stale `hist` ends with (reconstruct.py:899-902), F' = F sqrt(fixed/|F|^2) ----

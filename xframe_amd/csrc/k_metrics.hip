@@ -311,6 +311,7 @@ int mtip_set_invariant_metrics(mtip_ctx* c, uint32_t which, const uint8_t* zero_
     (void)hipSetDevice(c->device);
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     free_invariant_tables(c);
+    c->last_fxs_step = -1;                       // the new history has no row of an earlier step (main error items of a *_non_FXS step)
     if (which == 0) return MTIP_OK;
     if (which > 7 || !zero_mask || ((which & 1) && (!II_reference || !qq)) || ((which & 2) && (!ccd_weights || !ccd_reference || !(ccd_norm != 0.0))) ||
         ((which & 4) && (!fqc_P || !fqc_reference_average || !fqc_reference_weights))) {
@@ -371,6 +372,7 @@ int mtip_set_reciprocal_l2_metric(mtip_ctx* c, const double* radial_w, const dou
     if (!c) return MTIP_EINVAL;
     (void)hipSetDevice(c->device);
     free_reciprocal_l2_metric(c);
+    c->last_fxs_step = -1;                       // as in mtip_set_invariant_metrics
     if (!radial_w || !theta_w) return MTIP_OK;
     MTIP_HIP_CHECK(c, c->d_rl2_wr.alloc(c->N));
     MTIP_HIP_CHECK(c, c->d_rl2_wt.alloc(c->nt));

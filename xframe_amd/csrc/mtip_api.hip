@@ -403,16 +403,40 @@ static int build_bref(mtip_ctx* c) {
 
 int mtip_set_deg2_metric(mtip_ctx* c, int enable) {
     CTX_CHECK(c);
+    if (enable && !c->deg2_enable) c->last_fxs_step = -1;         // no step of this reconstruction has recorded it yet (main error items)
     c->deg2_enable = enable ? 1 : 0;
     return MTIP_OK;
 }
 
-int mtip_set_main_error(mtip_ctx* c, int use_reciprocal_deg2, int type) {
+int mtip_set_main_error_ex(mtip_ctx* c, int type, int n_items, const int* items, int deg2_ranked_column) {
     CTX_CHECK(c);
     if (type < 0 || type > 3) FAIL(c, MTIP_EINVAL, "main error type: 0 mean, 1 min, 2 max, 3 prod");
-    c->main_mode = use_reciprocal_deg2 ? 1 : 0;
+    if (n_items < 1 || !items) FAIL(c, MTIP_EINVAL, "main error: at least one item");
+    if (n_items > MAIN_ITEMS_MAX) FAIL(c, MTIP_EINVAL, "main error: at most 8 items");
+    bool vec = false, scalar = false, ranked = false;
+    for (int i = 0; i < n_items; ++i) {
+        if (items[i] < MAIN_ITEM_REAL_L2 || items[i] > MAIN_ITEM_DEG2_RANKED)
+            FAIL(c, MTIP_EINVAL, "main error: items 0 (real l2_projection_diff), 1 (deg2_invariant_l2_diff), 2 (reciprocal l2_projection_diff), "
+                                 "3 (II_error), 4 (ccd_diff), 5 (deg2_ranked_invariant_l2_diff)");
+        (items[i] == MAIN_ITEM_DEG2 ? vec : scalar) = true;
+        ranked = ranked || items[i] == MAIN_ITEM_DEG2_RANKED;
+    }
+    if (vec && (scalar || n_items > 1))
+        FAIL(c, MTIP_EINVAL, "main error over deg2_invariant_l2_diff (one value per order) and anything else: the reference raises "
+                             "(np.array of an inhomogeneous list, fxs_IO_methods.py:760)");
+    if (ranked && (deg2_ranked_column < 0 || deg2_ranked_column > c->L))
+        FAIL(c, MTIP_EINVAL, "main error: deg2_ranked_column must be an order 0 .. L");
     c->main_type = type;
+    c->main_n = n_items;
+    for (int i = 0; i < n_items; ++i) c->main_items[i] = items[i];
+    c->main_ranked_col = ranked ? deg2_ranked_column : 0;
+    c->main_mode = vec ? 1 : ((n_items == 1 && items[0] == MAIN_ITEM_REAL_L2) ? 0 : 2);
     return MTIP_OK;
+}
+
+int mtip_set_main_error(mtip_ctx* c, int use_reciprocal_deg2, int type) {
+    const int item = use_reciprocal_deg2 ? MAIN_ITEM_DEG2 : MAIN_ITEM_REAL_L2;
+    return mtip_set_main_error_ex(c, type, 1, &item, 0);
 }
 
 int mtip_set_real_constraints(mtip_ctx* c, uint32_t flags, double lo, double hi, double imag_thr, uint32_t hio_flags) {
@@ -553,6 +577,7 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
             if (!chain) TRY(launch_sht_forward(c, c->d_F, cc[2], MTIP_PRE_SQUARE));
             if (c->deg2_enable) launch_deg2_metric(c, cc[2], c->d_deg2_hist + (size_t)c->n_steps_done * c->B * (c->L + 1));
             if (c->im_which) TRY(launch_invariant_metrics(c, cc[2], c->n_steps_done));
+            c->last_fxs_step = c->n_steps_done;
         }
     }
     if (phases & STEP_PROJ) {
@@ -639,6 +664,23 @@ static int enqueue_step(mtip_ctx* c, int method, int ft_stab, double beta, int p
     return MTIP_OK;
 }
 
+// every metric the main error lists must be switched on: k_finish_step reads this step's row of its history
+static int require_main_items(mtip_ctx* c) {
+    if (c->main_mode == 2)
+        for (int i = 0; i < c->main_n; ++i) {
+            const int item = c->main_items[i];
+            if (item == MAIN_ITEM_RECIPROCAL_L2 && !c->d_rl2_hist)
+                FAIL(c, MTIP_ESTATE, "main error over the reciprocal l2_projection_diff needs that metric enabled (mtip_set_reciprocal_l2_metric)");
+            if (item == MAIN_ITEM_II && !(c->im_which & 1))
+                FAIL(c, MTIP_ESTATE, "main error over II_error needs that metric enabled (mtip_set_invariant_metrics, flag 1)");
+            if (item == MAIN_ITEM_CCD && !(c->im_which & 2))
+                FAIL(c, MTIP_ESTATE, "main error over ccd_diff needs that metric enabled (mtip_set_invariant_metrics, flag 2)");
+            if (item == MAIN_ITEM_DEG2_RANKED && !c->deg2_enable)
+                FAIL(c, MTIP_ESTATE, "main error over deg2_ranked_invariant_l2_diff needs the deg2 metric enabled (mtip_set_deg2_metric)");
+        }
+    return MTIP_OK;
+}
+
 // checks and one-time work in front of the steps of a run (shared by mtip_run_async and mtip_run_group_async); every check comes
 // before the first launch, so a run that cannot be done enqueues nothing
 static int run_prelude(mtip_ctx* c, int method, int ft_stab, int n_steps, const double* betas) {
@@ -649,6 +691,8 @@ static int run_prelude(mtip_ctx* c, int method, int ft_stab, int n_steps, const 
     const bool fxs = (method == MTIP_HIO || method == MTIP_ER);
     if (c->main_mode == 1 && !(c->deg2_enable && fxs))
         FAIL(c, MTIP_ESTATE, "main error over deg2_invariant_l2_diff needs that metric enabled (mtip_set_deg2_metric) and an FXS method");
+    r = require_main_items(c);
+    if (r) return r;
     if (ft_stab && c->ftmask_mixed && !(c->cfg.fused && hankel_has_difference(c) && c->sht.real_update))
         FAIL(c, MTIP_ESTATE, "a per-restart ft_stab mask needs the fused one-pass step (cfg.fused, tiled Hankel kernel, real update in the SHT epilogue)");
     (void)hipSetDevice(c->device);
@@ -703,6 +747,10 @@ int mtip_run_group_async(mtip_ctx* const* ctxs, int n_ctx, int method, int ft_st
             if (ctxs[j] == ctxs[i]) FAIL(ctxs[i], MTIP_EINVAL, "a context appears twice in the group");
     }
     if (n_ctx == 1) return mtip_run_async(ctxs[0], method, ft_stab, n_steps, betas);
+    for (int i = 0; i < n_ctx; ++i) {                // (before any member's prelude launches its one-time work)
+        const int r = require_main_items(ctxs[i]);
+        if (r) return r;
+    }
     for (int i = 0; i < n_ctx; ++i) {
         mtip_ctx* c = ctxs[i];
         const int r = run_prelude(c, method, ft_stab, n_steps, betas);
@@ -791,7 +839,7 @@ int mtip_fetch_main_errors(mtip_ctx* c, int64_t first, int64_t n, double* main_e
     if (first < 0 || n < 0 || first + n > c->n_steps_done || !main_err) FAIL(c, MTIP_EINVAL, "step range out of bounds / null output");
     (void)hipSetDevice(c->device);
     MTIP_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    const double* src = c->main_mode == 1 ? c->d_main_hist : c->d_err_hist;
+    const double* src = c->main_mode != 0 ? c->d_main_hist : c->d_err_hist;
     if (n) MTIP_HIP_CHECK(c, mtip_copy(c, main_err, src + (size_t)first * c->B, (size_t)n * c->B * sizeof(double), hipMemcpyDeviceToHost));
     return post_launch(c, "mtip_fetch_main_errors");
 }
@@ -850,6 +898,7 @@ int mtip_init_state(mtip_ctx* c) {
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_best_err, inf.data(), c->B * sizeof(double), hipMemcpyHostToDevice));
     MTIP_HIP_CHECK(c, mtip_copy(c, c->d_last_err, inf.data(), c->B * sizeof(double), hipMemcpyHostToDevice));
     c->n_steps_done = 0;
+    c->last_fxs_step = -1;
     c->fixed_valid = false;
     c->c0n_valid = false;
     c->vr = VR_NONE;                     // a fresh reconstruction does not warm-start its polar factors

@@ -72,6 +72,17 @@ __device__ __forceinline__ double2 cmul_ipow(double2 a, int l, int sign) {
 // fixed amplitudes of the *_non_FXS variants (901)
 enum { SL_CUR = 0, SL_OUT = 1, SL_BEST = 2, SL_SUP = 3, SL_SUP_BEST = 4, SL_ENFORCE = 5, SL_HAS_ERR = 6, SL_HIST = 7, SL_N = 8 };
 
+// the metrics a main error can list (mtip_set_main_error_ex), and what k_finish_step is handed to read them
+enum { MAIN_ITEM_REAL_L2 = 0, MAIN_ITEM_DEG2 = 1, MAIN_ITEM_RECIPROCAL_L2 = 2, MAIN_ITEM_II = 3, MAIN_ITEM_CCD = 4, MAIN_ITEM_DEG2_RANKED = 5 };
+#define MAIN_ITEMS_MAX 8
+struct MainItems {
+    int n, ranked_col;              // n < 0: a listed metric has no value yet; ranked_col: column of the deg2 row (item 5)
+    int items[MAIN_ITEMS_MAX];
+    const double* rl2;              // (B) row of d_rl2_hist
+    const double* im;               // (B, 2 + Nq) row of d_im_hist: II (B) | ccd (B) | fqc
+    const double* deg2;             // (B, L+1) row of d_deg2_hist
+};
+
 // real-space constraint flags (mtip_set_real_constraints)
 enum { RC_SUPPORT = 1, RC_VALUE_LO = 2, RC_VALUE_HI = 4, RC_LIMIT_IMAG = 8 };
 
@@ -382,8 +393,11 @@ struct mtip_ctx {
     DevBuf<double> d_op_err;                       // (B) error of the single-operator entry point (never the loop's)
     DevBuf<double> d_gq;                           // (Nq) shrink-wrap Gaussian G_sigma(q)
     DevBuf<double> d_err_hist;                     // (cap, B) real l2 metric per step
-    DevBuf<double> d_main_hist;                    // (cap, B) main error per step when it is not the real metric (main_mode 1)
-    int main_mode = 0, main_type = 0;                 // mtip_set_main_error
+    DevBuf<double> d_main_hist;                    // (cap, B) main error per step when it is not the real metric (main_mode 1, 2)
+    // mtip_set_main_error_ex: main_mode 0 = items [0], 1 = items [1] (the per-order vector), 2 = any other list of scalar items
+    int main_mode = 0, main_type = 0;
+    int main_n = 1, main_items[MAIN_ITEMS_MAX] = {0, 0, 0, 0, 0, 0, 0, 0}, main_ranked_col = 0;
+    long long last_fxs_step = -1;                     // last FXS step of this reconstruction: the rows its reciprocal metrics were recorded in
     DevBuf<double> d_deg2_hist;                    // (cap, B, L+1)
     long long err_cap = 0, n_steps_done = 0;
     bool state_ready = false, fixed_valid = false;

@@ -66,6 +66,7 @@ _SIGNATURES = {
     'mtip_op_invariant_metrics': (C.c_int, [c_void, c_void, c_void, c_void, c_void]),
     'mtip_set_deg2_metric': (C.c_int, [c_void, C.c_int]),
     'mtip_set_main_error': (C.c_int, [c_void, C.c_int, C.c_int]),
+    'mtip_set_main_error_ex': (C.c_int, [c_void, C.c_int, C.c_int, c_void, C.c_int]),
     'mtip_set_real_constraints': (C.c_int, [c_void, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_uint32]),
     'mtip_set_initial_support': (C.c_int, [c_void, c_void]),
     'mtip_set_error_weights': (C.c_int, [c_void, c_void, c_void, C.c_int]),

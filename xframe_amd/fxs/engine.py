@@ -141,14 +141,23 @@ class Engine(_lib.TensorOperands):
         # II_error / ccd_diff / fqc_error (fxs_IO_methods.py:587-627, 651-683, 507-550): per step on the device from B_l
         self.invariant_metrics = [n for n in ('II_error', 'ccd_diff', 'fqc_error') if n in em['reciprocal']['calculate']]
         if self.invariant_metrics:
-            if sorted(self.rsetup.used_orders.values()) != list(range(self.L + 1)):
-                raise NotImplementedError('II_error / ccd_diff / fqc_error with a subset of the orders (upstream masks B_l of ALL orders with '
-                                          'arrays shaped by the used ones, fxs_IO_methods.py:594-597, 610)')
+            used_ids = sorted(self.rsetup.used_orders.values())
+            subset = used_ids != list(range(self.L + 1))
+            if subset:
+                # ccd_diff indexes B_l, its weights and the mask by the used orders and runs upstream (fxs_IO_methods.py:653-677); the
+                # other two mask B_l of ALL orders with arrays shaped by the used ones (594-597, 612; 514-516)
+                refused = [n for n in self.invariant_metrics if n != 'ccd_diff']
+                if refused:
+                    raise NotImplementedError('%s with a subset of the orders: upstream raises in its first evaluation (IndexError: boolean '
+                                              'index did not match indexed array along axis 0, fxs_IO_methods.py:612 / 535)' % ' / '.join(refused))
+                if 0 not in self.rsetup.used_orders:
+                    raise NotImplementedError('ccd_diff without order 0 among the used orders: upstream raises (KeyError: 0, zero_id = '
+                                              'used_orders[0], fxs_IO_methods.py:654)')
             if self.xray_wavelength is None:
                 raise KeyError("II_error / ccd_diff / fqc_error need data['xray_wavelength'] (fxs_IO_methods.py:511, 590, 657)")
-            t = hs.invariant_metric_tables(self.invariant_metrics, self.qs, [self.rsetup.projection_matrices[l] for l in range(self.L + 1)],
-                                           self.rsetup.radial_mask, float(self.xray_wavelength),
-                                           em['reciprocal'].get('ccd_diff', {}).get('C_order', None))
+            pms = [self.rsetup.projection_matrices.get(l, np.zeros((self.N, min(self.N, 2 * l + 1)), complex)) for l in range(self.L + 1)]
+            t = hs.invariant_metric_tables(self.invariant_metrics, self.qs, pms, self.rsetup.radial_mask, float(self.xray_wavelength),
+                                           em['reciprocal'].get('ccd_diff', {}).get('C_order', None), used_ids if subset else None)
             flags = sum(f for f, n in ((1, 'II_error'), (2, 'ccd_diff'), (4, 'fqc_error')) if n in self.invariant_metrics)
 
             def pp(key, conv):
@@ -164,19 +173,28 @@ class Engine(_lib.TensorOperands):
         types = {'mean': 0, 'min': 1, 'max': 2, 'prod': 3}
         if main.get('type', 'mean') not in types:
             raise ValueError('main error type %r (mean / min / max / prod)' % (main.get('type'),))
-        if real_m == ['l2_projection_diff'] and not rec_m:
-            self.main_is_reciprocal = False
-        elif not real_m and rec_m == ['deg2_invariant_l2_diff']:
-            if not self.deg2_listed:
-                raise KeyError("main error uses 'deg2_invariant_l2_diff' but main_loop.error.methods.reciprocal.calculate does not list it")
-            self.main_is_reciprocal = True
-        elif real_m == ['l2_projection_diff'] and rec_m == ['deg2_invariant_l2_diff']:
-            raise NotImplementedError('main error over l2_projection_diff (a scalar) AND deg2_invariant_l2_diff (one value per order): the '
-                                      'reference itself raises there (np.array of an inhomogeneous list, fxs_IO_methods.py:760)')
-        else:
-            raise NotImplementedError('main error metrics %r / %r: only l2_projection_diff and deg2_invariant_l2_diff are on the '
-                                      'accelerated path' % (real_m, rec_m))
-        self._ck(self.lib.mtip_set_main_error(self.ctx, int(self.main_is_reciprocal), types[main.get('type', 'mean')]))
+        codes = {('real', 'l2_projection_diff'): 0, ('reciprocal', 'deg2_invariant_l2_diff'): 1, ('reciprocal', 'l2_projection_diff'): 2,
+                 ('reciprocal', 'II_error'): 3, ('reciprocal', 'ccd_diff'): 4, ('reciprocal', 'deg2_ranked_invariant_l2_diff'): 5}
+        named = [('real', n) for n in real_m] + [('reciprocal', n) for n in rec_m]        # the reference's order (753-757)
+        for name in rec_m:                                           # (the real metric is recorded whether it is listed or not)
+            if name not in rec_calc:
+                raise KeyError("main error uses %r but main_loop.error.methods.reciprocal.calculate does not list it" % (name,))
+        if ('reciprocal', 'fqc_error') in named:
+            raise NotImplementedError('main error over fqc_error: one value per shell, NaN throughout in three dimensions upstream '
+                                      '(0 / 0 at shell 0, fxs_IO_methods.py:507-550); not built as a main metric (DESIGN section 6)')
+        vector = ('reciprocal', 'deg2_invariant_l2_diff') in named
+        if vector and len(named) > 1:
+            raise NotImplementedError('main error over deg2_invariant_l2_diff (one value per order) AND %r: the '
+                                      'reference itself raises there (np.array of an inhomogeneous list, fxs_IO_methods.py:760)'
+                                      % ([n for n in named if n != ('reciprocal', 'deg2_invariant_l2_diff')],))
+        unknown = [n for n in named if n not in codes]
+        if unknown or not named or len(named) > 8:
+            raise NotImplementedError('main error metrics %r / %r: one to eight of %s' % (real_m, rec_m, ', '.join('%s %s' % k for k in codes)))
+        self.main_items = [codes[n] for n in named]
+        # item 5 reads a column of the per-order history, which has a column for every order: the one of the ranked used order
+        column = int(tuple(self.rsetup.used_orders.values())[self.deg2_ranked_id]) if 5 in self.main_items else 0
+        items = np.ascontiguousarray(self.main_items, dtype=np.int32)
+        self._ck(self.lib.mtip_set_main_error_ex(self.ctx, types[main.get('type', 'mean')], len(items), _lib.ptr(items), column))
 
     def autocorrelation_guess(self):
         """reconstruct.py:400-420: ift(icht(V_l padded)).real"""

@@ -308,15 +308,24 @@ def sph_plm(l, m, x):
     return sph_harm_y(np.asarray(l), np.asarray(m), np.arccos(np.clip(x, -1.0, 1.0)), 0.0).real
 
 
-def invariant_metric_tables(which, qs, projection_matrices, radial_mask, xray_wavelength, C_order=None):
+def invariant_metric_tables(which, qs, projection_matrices, radial_mask, xray_wavelength, C_order=None, used_ids=None):
     """Constant tables of the non-default reciprocal metrics for mtip_set_invariant_metrics (fxs_IO_methods.py:507-550 fqc_error,
     587-627 II_error, 651-683 ccd_diff; Legendre products fxs_invariant_tools.py:23-33, 48-58).  projection_matrices: list over all
-    orders 0..L of the modified V_l (the reference's rp.projection_matrices; its reference invariants are V_l V_l^+, 631-637)."""
+    orders 0..L of the modified V_l (the reference's rp.projection_matrices; its reference invariants are V_l V_l^+, 631-637).
+    used_ids (None: all orders): the used orders of a subset, for ccd_diff alone -- it sums over `order_array` (653, 674-677), so the
+    weights and the reference of the other orders are zero and their B_l is masked out; the other two raise upstream."""
     qs = np.asarray(qs, dtype=float)
     N, L = len(qs), len(projection_matrices) - 1
     ref = np.array([np.asarray(p) @ np.asarray(p).conj().T for p in projection_matrices])
     rm = np.asarray(radial_mask, dtype=bool)
     zero = ~(rm[:, :, None] & rm[:, None, :])                     # entries of B_l outside the invariant mask
+    unused = np.zeros(L + 1, bool)
+    if used_ids is not None:
+        if [n for n in which if n != 'ccd_diff']:
+            raise NotImplementedError('II_error / fqc_error with a subset of the orders: upstream raises (IndexError, fxs_IO_methods.py:612, 535)')
+        unused[:] = True
+        unused[np.asarray(used_ids, dtype=int)] = False
+        zero[unused] = True
     ref[zero] = 0
     out = {'zero_mask': zero.astype(np.uint8)}
     orders = np.arange(L + 1)
@@ -332,6 +341,7 @@ def invariant_metric_tables(which, qs, projection_matrices, radial_mask, xray_wa
         T = np.moveaxis(pl[None, :, :] * pl[:, None, :] / (2 * orders + 1)[None, None, :], -1, 0).copy()    # (l, q, q')
         T[0] = 0
         T[orders < int(C_order)] = 0
+        T[unused] = 0
         T[np.isnan(T)] = 0
         refC = np.sum(ref * T, axis=0)
         norm = np.sum(refC * refC.conj())
